@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ScalableFHVAE training-step throughput on MI355X (contract: see the task statement).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
@@ -162,6 +162,43 @@ def synth_cpu(cfg, B, rank=0, idx_dist="uniform"):
         idx = torch.randint(0, cfg["S"], (B,), generator=gi)
     ns = torch.randint(20, 200, (B,), generator=torch.Generator().manual_seed(1236 + rank))
     return x, idx, ns
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed step computed, for output-for-output comparison of two builds
+# ---------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 * 1024 * 1024  # bytes, all files together
+DUMP_HEADER = 4096  # bytes reserved per file for the .npy header
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """Write {name: tensor} as path/<name>.npy: float64 tensors as float64, everything else as float32, at most `limit` bytes
+    in all.  Arrays are written smallest first, each whole if it fits its share of what is left (the rest divided by the
+    arrays still to come), else as a fixed sample of that many of its elements: flat indices drawn without replacement by
+    a generator seeded with 0 and sorted, the same in every run for the same shape.  -> {name: "whole" | "sample k of n"}"""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    left, todo, what = limit, len(host), {}
+    for name in sorted(host, key=lambda n: (host[n].nbytes, n)):
+        a = host[name]
+        share = left // todo - DUMP_HEADER
+        if a.nbytes > share:
+            k = max(0, share // a.itemsize)
+            pick = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            what[name] = "sample %d of %d" % (k, a.size)
+            a = np.ascontiguousarray(a.reshape(-1)[pick])
+        else:
+            what[name] = "whole"
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= os.path.getsize(os.path.join(path, name + ".npy"))
+        todo -= 1
+    return what
 
 
 # ---------------------------------------------------------------------------------------------
@@ -388,9 +425,10 @@ def cpu_baseline(cfg, dtype, budget_s=45.0, sample_B=256):
 # one GPU measurement
 # ---------------------------------------------------------------------------------------------
 def run_gpu(cfg_name, B, dtype, steps, warmup, device, rank, world, use_dist, no_graph, want_roofline, idx_dist, dist_graph=False,
-            on_eager=None):
+            on_eager=None, dump_dir=None):
     """on_eager(result): called with the EAGER measurement of a distributed step before its capture into a hipGraph is
-    attempted (main arms the watchdog with it)."""
+    attempted (main arms the watchdog with it).  dump_dir: rank 0 writes what the last timed step returned (loss, lower
+    bound per segment) there (dump_outputs)."""
     import torch
 
     import hip_binding as hb
@@ -509,6 +547,9 @@ def run_gpu(cfg_name, B, dtype, steps, warmup, device, rank, world, use_dist, no
                 return g_loss, g_lb
 
     dt, loss, lb = timed(step)
+    dumped = None
+    if dump_dir and rank == 0:  # before anything below runs more steps on the model
+        dumped = dump_outputs(dump_dir, {"loss": loss, "lower_bound": lb})
     elbo = (lb.mean() / T).item()
     ok = bool(torch.isfinite(loss).item())
     if hb.lstm_sync_status() != 0:
@@ -517,6 +558,8 @@ def run_gpu(cfg_name, B, dtype, steps, warmup, device, rank, world, use_dist, no
            "launch": "hipGraph replay of the whole step" if use_graph else eager_note, "dtype": dtype, "batch": B}
     if eager is not None:
         res["eager"] = {"value": eager["value"], "ms_per_step": eager["ms_per_step"]}
+    if dumped is not None:
+        res["dump"] = {"dir": dump_dir, "arrays": dumped}
     if os.environ.get("FHVAE_BENCH_RETRY"):
         res["launch"] += " (second attempt: the first %d-rank run did not finish within --launch-timeout)" % world
 
@@ -612,7 +655,12 @@ def main():
     ap.add_argument("--phase-timeout", type=int, default=240,
                     help="N > 1: seconds a captured (hipGraph) phase may take before the watchdog prints the eager record and ends "
                          "the ranks (0 = no watchdog)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline run, write what its last step returned (loss, lower bound per "
+                         "segment) as DIR/<name>.npy, float32/float64, 64 MB at most")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -668,7 +716,7 @@ def main():
                                    "intended objective, mu_idx %s" % (cfg_name, cfg["desc"], B, T, F, args.idx),
                        "global_batch": world * B, "parallelism": "dp%d+mu2-row-shard" % world if use_dist else "single"},
         }
-        for k in ("roofline", "idx", "eager"):
+        for k in ("roofline", "idx", "eager", "dump"):
             if k in main_res:
                 rec[k] = main_res[k]
         if state["alts"]:
@@ -694,7 +742,8 @@ def main():
             watchdog_arm(args.phase_timeout, "hipGraph capture + replay of the %s step" % cfg_name)
 
     main_res = run_gpu(cfg_name, B, dtype, args.steps, args.warmup, device, rank, world, use_dist, args.no_graph,
-                       not args.no_roofline, args.idx, use_dist and not args.no_dist_graph, on_eager=on_eager_main)
+                       not args.no_roofline, args.idx, use_dist and not args.no_dist_graph, on_eager=on_eager_main,
+                       dump_dir=args.dump_outputs)
     watchdog_disarm()
     state["main"] = main_res
 

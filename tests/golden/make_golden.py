@@ -24,9 +24,15 @@ Fixtures:
         follows utils.py:131-146 key by key; the values all come from reference objects.)
   disc_{8x12,256x4600}.npz : the discriminative block alone (simple_fhvae.py:119-122): q=z2_mu, table,
         idx -> log_qy, d log_qy/dq, d log_qy/dtable, taken from inside a reference forward.
+
+The reference runs in a fresh interpreter with ``pinned_env()``: the math libraries on paths that give the same bits on
+every x86-64 host.  tests/test_oracle_golden.py compares the oracle against these fixtures bit for bit in the same
+environment; with the host's own choices (MKL's per-vendor and AVX-512 kernels, ATen's and numpy's AVX2 / AVX-512 loops,
+the thread count) the last bit of some outputs moves from one machine to the next.
 """
 import importlib.util
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -38,9 +44,25 @@ sys.path.insert(0, ROOT)
 from oracle.ref_cpu import det_index, det_tensor, fill_state_dict_det  # noqa: E402
 
 REF = "/root/reference/simple_fhvae.py"
-spec = importlib.util.spec_from_file_location("_reference_simple_fhvae", REF)
-ref = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(ref)
+ref = None  # the reference module (load_reference)
+
+
+def pinned_env():
+    """Environment variables for a reproducible CPU run: one thread, MKL's conditional-numerical-reproducibility mode for
+    any x86 CPU, ATen's and oneDNN's baseline kernels, and none of numpy's dispatched SIMD loops (its SSE3 baseline)."""
+    try:
+        from numpy._core._multiarray_umath import __cpu_dispatch__
+    except ImportError:  # numpy < 2
+        from numpy.core._multiarray_umath import __cpu_dispatch__
+    return {"OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1", "MKL_CBWR": "COMPATIBLE", "ATEN_CPU_CAPABILITY": "default",
+            "ONEDNN_MAX_CPU_ISA": "SSE41", "NPY_DISABLE_CPU_FEATURES": " ".join(__cpu_dispatch__)}
+
+
+def load_reference():
+    global ref
+    spec = importlib.util.spec_from_file_location("_reference_simple_fhvae", REF)
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
 
 
 def ref_loss_function(lower_bound, log_qy, alpha=10.0):
@@ -197,6 +219,10 @@ def disc(B, S, name):
 
 
 if __name__ == "__main__":
+    env = pinned_env()
+    if any(os.environ.get(k) != v for k, v in env.items()):  # numpy and torch are loaded already: run in a fresh interpreter
+        sys.exit(subprocess.run([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=dict(os.environ, **env)).returncode)
+    load_reference()
     if "--checkpoint-only" in sys.argv:
         ref_checkpoint()
         sys.exit(0)

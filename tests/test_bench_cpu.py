@@ -1,5 +1,5 @@
 """bench.py's protection of the first multi-GPU run (no GPU needed): the watchdog that prints what was already measured when a
-phase does not come back, and the self-launcher's time limit with one fresh retry."""
+phase does not come back, and the self-launcher's time limit with one fresh retry; --dump-outputs' writer."""
 import os
 import subprocess
 import sys
@@ -64,3 +64,28 @@ def test_self_launch_kills_a_stuck_rank_tree_and_retries_once():
     assert "rc 124" in r.stdout, (r.stdout, r.stderr[-2000:])
     assert "starting a fresh one with --no-dist-graph --no-alt" in r.stderr and "second attempt did not finish either" in r.stderr
     assert time.time() - t0 < 200
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor(3.5, dtype=torch.float64), "small": torch.randn(7, 5, generator=g).bfloat16(),
+              "big": torch.randn(1000, 64, generator=g), "bigger": torch.randn(4000, 32, generator=g)}
+    limit = 700_000
+    what = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    files = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in arrays) <= limit
+    assert files["loss"].dtype == np.float64 and files["loss"] == 3.5
+    assert files["small"].dtype == np.float32 and np.array_equal(files["small"], arrays["small"].float().numpy())
+    assert what["loss"] == what["small"] == what["big"] == "whole"
+    np.testing.assert_array_equal(files["big"], arrays["big"].numpy())
+    assert what["bigger"].startswith("sample ") and files["bigger"].dtype == np.float32
+    assert np.isin(files["bigger"], arrays["bigger"].numpy()).all()
+    # the same arrays give the same sample
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "bigger.npy"), files["bigger"])

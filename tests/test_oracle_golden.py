@@ -1,6 +1,12 @@
 """The CPU oracle (oracle/ref_cpu.py) against the golden vectors taken from the reference
-(tests/golden/make_golden.py).  Pins the restatement: forward 6-tuple, loss and gradients."""
+(tests/golden/make_golden.py).  Pins the restatement: forward 6-tuple, loss and gradients.
+
+The comparisons with the vectors run in a fresh interpreter with the environment the reference ran in
+(make_golden.pinned_env: math libraries on paths that give the same bits on every x86-64 host)."""
+import importlib.util
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -9,14 +15,33 @@ import torch
 from oracle import ref_cpu as R
 
 OUT = ["lower_bound", "log_qy", "log_px_z", "neg_kld_z1", "neg_kld_z2", "log_pmu2"]
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 
 
 def _load(golden_dir, name):
     return dict(np.load(os.path.join(golden_dir, name)))
 
 
+def _pinned(golden_dir, check, *args):
+    """check(golden_dir, *args) of this module, run in a fresh interpreter with make_golden.pinned_env()."""
+    spec = importlib.util.spec_from_file_location("_make_golden", os.path.join(golden_dir, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    code = "import sys; sys.path[:0] = %r; import test_oracle_golden as t; t.%s(*%r)" % (
+        [HERE, ROOT], check.__name__, (golden_dir,) + args)
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, **mg.pinned_env()), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
+
+
 @pytest.mark.parametrize("name,dtype", [("simple_tiny_f32.npz", torch.float32), ("simple_tiny_f64.npz", torch.float64)])
 def test_simple_tiny_forward_loss_grads(golden_dir, name, dtype):
+    _pinned(golden_dir, check_simple_tiny, name, str(dtype).replace("torch.", ""))
+
+
+def check_simple_tiny(golden_dir, name, dtype):
+    dtype = getattr(torch, dtype)
     g = _load(golden_dir, name)
     m = R.SimpleFHVAERef(4 * 8, [16, 16], [16, 16], 16, 16, [16, 16]).to(dtype)
     m.load_state_dict({k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd_")})
@@ -39,6 +64,10 @@ def test_simple_tiny_forward_loss_grads(golden_dir, name, dtype):
 
 
 def test_simple_refshape_forward(golden_dir):
+    _pinned(golden_dir, check_simple_refshape)
+
+
+def check_simple_refshape(golden_dir):
     g = _load(golden_dir, "simple_refshape_f32.npz")
     T, F, D, B, S = [int(v) for v in g["meta_TFDBS"]]
     m = R.SimpleFHVAERef(T * F)
@@ -56,6 +85,10 @@ def test_simple_refshape_forward(golden_dir):
 
 @pytest.mark.parametrize("name", ["disc_8x12.npz", "disc_256x4600.npz"])
 def test_disc_block(golden_dir, name):
+    _pinned(golden_dir, check_disc_block, name)
+
+
+def check_disc_block(golden_dir, name):
     g = _load(golden_dir, name)
     q = torch.from_numpy(g["q"]).requires_grad_(True)
     t = torch.from_numpy(g["table"]).requires_grad_(True)
