@@ -659,7 +659,8 @@ LSTM_WORKSPACES: list = []
 
 LSTM_FORMS = {0: "one launch per wavefront step", 1: "persistent cluster kernel (waves split rows)",
               2: "persistent cluster kernel (waves split the contraction)"}
-LAST_LSTM_FORM = {"form": 0}
+# "layout": fhvae_lstm_layout_id of that forward (0 per-step cells, 1 large-tile cells, 16 + 2 * form + register-stationary forward)
+LAST_LSTM_FORM = {"form": 0, "layout": 0}
 
 
 def lstm_kernel_names(form: int, H: int) -> dict:
@@ -755,6 +756,7 @@ class _LstmSeq(torch.autograd.Function):
         ctx.dims, ctx.dtype = dims, dtype
         ctx.x_lp = x_lp
         ctx.layout_id = int(lib.fhvae_lstm_layout_id(C.byref(d)))  # the schedule this forward took (see backward)
+        LAST_LSTM_FORM["layout"] = ctx.layout_id
         ctx.save_for_backward(x_tm, xc, hs, cs, gates, lp, *params)
         if hn_lp is not None:
             hn._fh_lp = hn_lp  # the same values in bf16, written by the forward itself (fhvae_lstm_desc.hn_lp)
