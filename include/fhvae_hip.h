@@ -193,7 +193,7 @@ int64_t fhvae_lstm_pre_elems(const fhvae_lstm_desc* d);
 /* Identifies the layout of what fhvae_lstm_seq_fwd saves for the backward (gates, schedule workspaces): it follows from the
  * schedule the library picks for this descriptor AND the FHVAE_* environment switches at call time.  A caller that may change
  * either between a forward and its backward keeps the forward's value and checks it before fhvae_lstm_seq_bwd (< 0: bad
- * descriptor). */
+ * descriptor; `gates` and `cs` are not looked at). */
 int fhvae_lstm_layout_id(const fhvae_lstm_desc* d);
 
 /* Floats fhvae_lstm_bwd_desc.ws_below must hold (0: may be NULL). */
@@ -201,9 +201,17 @@ int64_t fhvae_lstm_ws_below_elems(const fhvae_lstm_desc* d);
 /* Which schedule fhvae_lstm_seq_fwd/_bwd take for this descriptor on the current device: 0 = one launch per wavefront
    step; 1 = persistent cluster kernel, waves split the batch rows; 2 = persistent cluster kernel, waves split the
    contraction (small batches).  1 and 2 need the GPU to themselves while they run (256 co-resident workgroups);
-   FHVAE_NO_CLUSTER=1 in the environment forces 0. */
+   FHVAE_NO_CLUSTER=1 in the environment forces 0.  `gates` and `cs` are not looked at (fhvae_lstm_seq_infer takes the same form). */
 int fhvae_lstm_form(const fhvae_lstm_desc* d);
 int fhvae_lstm_seq_fwd(const fhvae_lstm_desc* d, void* stream);
+/* Inference forward: same descriptor as fhvae_lstm_seq_fwd, same schedule choice, same outputs (hs, hn, hn_lp, hs_top_f32,
+   head_wl/head_wt), bit-identical values.  `gates` must be NULL (else FHVAE_ERR_SHAPE).  `cs` is a workspace of
+   fhvae_lstm_infer_cs_elems(d) floats (may be NULL when that is 0): the per-step schedules keep c^l_{t-1} in a two-slot ring
+   (L,2,B,H), the persistent ones keep c in registers / LDS and return 0.  hs stays (L,T,B,H): it is the inter-layer input and the
+   persistent kernels' exchange buffer.  F32 mode: `lp` may be NULL and is not filled.  BF16 mode: `lp` is the same workspace (the
+   transposed weight copies are not made).  No fhvae_lstm_seq_bwd may follow. */
+int64_t fhvae_lstm_infer_cs_elems(const fhvae_lstm_desc* d);
+int fhvae_lstm_seq_infer(const fhvae_lstm_desc* d, void* stream);
 
 typedef struct fhvae_lstm_bwd_desc {
   fhvae_lstm_desc f;      /* the forward descriptor (same buffers, already filled by fwd) */

@@ -66,85 +66,14 @@ __device__ __forceinline__ float load_h<u16>(const u16* p) {
 // the 4 accumulators acc[tm][0..3] of one lane.
 template <typename T, int BM, int BN, int WM, int WN, int CH>
 __global__ __launch_bounds__(kThreads) void lstm_fwd_step_kernel(FwdJobs<T> jobs) {
-  using TL = Tile<T, BM, BN, WM, WN, CH>;
-  constexpr int TM = TL::TM;
-  static_assert(TL::TN == 4, "one wave = one 64-column gate group");
-  constexpr bool kPrefetch = TM == 1;
-  constexpr int NBUF = CH >= 32 ? 2 : 1;  // wide panels = few large workgroups: double buffer; narrow: occupancy
-  using GT = GldsTile<T, BM, BN, WM, WN, CH, NBUF>;
-  __shared__ __attribute__((aligned(16))) char smem[TL::SMEM > GT::SMEM ? TL::SMEM : GT::SMEM];
-  const FwdJob<T>& J = jobs.job[blockIdx.z];
-  const int B = jobs.B, H = jobs.H;
-  // blockIdx.x walks the ROW tiles: workgroups are dealt round-robin over the 8 XCDs by linear id, so every XCD
-  // (private 4 MB L2) sees 1/8 of the activations and all of the (small) weight slice, instead of all activations
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  f32x4 acc[TM][4];
-  zero_acc(acc);
-  RowIdent arm{B};
-  GateRowMap brm{H};
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int unit = (n0 / 64 + wn) * 16 + (lane & 15);
-  const bool uok = unit < H;
-  auto row_of = [&](int tm, int r) { return m0 + wm * (TM * 16) + tm * 16 + (lane >> 4) * 4 + r; };
-  auto fetch_add = [&](int row, int g) -> float {
-    float v = 0.f;
-    if (J.pre) v = J.pre[(int64_t)row * J.pre_ld + g * H + unit];
-    if (J.bias_a) v += J.bias_a[g * H + unit] + J.bias_b[g * H + unit];
-    return v;
-  };
-  // small tile: epilogue operands are fetched BEFORE the contraction so their latency hides under it
-  float padd[kPrefetch ? 4 : 1][4], cprev[kPrefetch ? 4 : 1];
-  if constexpr (kPrefetch) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = row_of(0, r);
-      const bool ok = uok && row < B;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) padd[r][g] = ok ? fetch_add(row, g) : 0.f;
-      cprev[r] = (ok && J.c_prev) ? J.c_prev[(int64_t)row * H + unit] : 0.f;
-    }
-  }
-  const int nkb = num_kblocks<T, CH>(J.seg);
-  // interior tiles with panel-aligned K take the LDS-DMA path; edges / odd shapes the register-staged one
-  const bool dma = jobs.glds && m0 + BM <= B && brm.all_valid(n0, BN) && seg_glds_ok<T>(J.seg[0], TL::BK) &&
-                   seg_glds_ok<T>(J.seg[1], TL::BK);
-  if (dma)
-    mainloop_glds<T, BM, BN, WM, WN, CH, NBUF, false>(acc, J.seg, m0, n0, arm, brm, smem);
-  else
-    mainloop<T, BM, BN, WM, WN, CH, true, true, false>(acc, J.seg, m0, B, n0, (int)gridDim.y * BN, arm, brm, 0, nkb, smem);
-
-  if (!uok) return;
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = row_of(tm, r);
-      if (row >= B) continue;
-      float pa[4], cp;
-      if constexpr (kPrefetch) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) pa[g] = padd[r][g];
-        cp = cprev[r];
-      } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) pa[g] = fetch_add(row, g);
-        cp = J.c_prev ? J.c_prev[(int64_t)row * H + unit] : 0.f;
-      }
-      const float ig = sigmoidf_(acc[tm][0][r] + pa[0]), fg = sigmoidf_(acc[tm][1][r] + pa[1]);
-      const float gg = tanhf_(acc[tm][2][r] + pa[2]), og = sigmoidf_(acc[tm][3][r] + pa[3]);
-      const float c = __builtin_fmaf(fg, cp, ig * gg);
-      const float h = og * tanhf_(c);
-      J.c_out[(int64_t)row * H + unit] = c;
-      store_h<T>(J.h_out + (int64_t)row * H + unit, h);
-      if (J.h_out_f32) J.h_out_f32[(int64_t)row * H + unit] = h;
-      T* go = J.gates_out + (int64_t)row * 4 * H + unit;
-      store_h<T>(go, ig);
-      store_h<T>(go + H, fg);
-      store_h<T>(go + 2 * H, gg);
-      store_h<T>(go + 3 * H, og);
-      if (J.hn_out) J.hn_out[(int64_t)row * J.hn_ld + unit] = h;
-    }
+  constexpr bool kSave = true;
+#include "lstm_fwd_step_body.h"
+}
+// the inference twin (fhvae_lstm_seq_infer): no gate stores; c goes to the caller's two-slot ring (fwd_jobs)
+template <typename T, int BM, int BN, int WM, int WN, int CH>
+__global__ __launch_bounds__(kThreads) void lstm_fwd_step_infer_kernel(FwdJobs<T> jobs) {
+  constexpr bool kSave = false;
+#include "lstm_fwd_step_body.h"
 }
 
 // Tile shapes: <32,32,2,2> and <128,64,4,1> (very large batches only, as for the forward cell).
@@ -311,7 +240,10 @@ __global__ void zero_f32_kernel(float* p, int64_t n) {
 
 using namespace fh;
 
-static int check_desc(const fhvae_lstm_desc* d) {
+// what a descriptor must carry beyond its shape: kCheckFwd (fhvae_lstm_seq_fwd: cs and gates), kCheckInfer (fhvae_lstm_seq_infer:
+// gates NULL, cs checked there against fhvae_lstm_infer_cs_elems), kCheckShape (the schedule queries: neither is looked at)
+enum { kCheckFwd = 0, kCheckInfer = 1, kCheckShape = 2 };
+static int check_desc(const fhvae_lstm_desc* d, int mode = kCheckFwd) {
   FH_CHECK_PTR(d);
   if (d->dtype != FHVAE_F32 && d->dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
   if (d->L < 1 || d->L > FHVAE_MAX_LAYERS) return FHVAE_ERR_SHAPE;
@@ -331,8 +263,12 @@ static int check_desc(const fhvae_lstm_desc* d) {
     FH_CHECK_PTR(d->b_hh[l]);
   }
   FH_CHECK_PTR(d->hs);
-  FH_CHECK_PTR(d->cs);
-  FH_CHECK_PTR(d->gates);
+  if (mode == kCheckFwd) {
+    FH_CHECK_PTR(d->cs);
+    FH_CHECK_PTR(d->gates);
+  } else if (mode == kCheckInfer && d->gates) {
+    return FHVAE_ERR_SHAPE;
+  }
   FH_CHECK_PTR(d->pre);
   // the step cells stage h / W rows in 16-byte chunks: H must be a multiple of 4 (f32) / 8 (bf16)
   if (d->dtype == FHVAE_BF16) {
@@ -469,10 +405,12 @@ static int cast_operands(const fhvae_lstm_desc* d, hipStream_t st) {
   };
   if (!d->x_lp) add(d->x, base + L.x, nullptr, d->T * d->B, d->I);
   add(d->xc, base + L.xc, nullptr, d->B, d->Ic);
+  // the transposed copies are the backward's operands: an inference forward (gates == NULL) skips them, no forward schedule reads them
+  const bool bwd = d->gates != nullptr;
   for (int l = 0; l < d->L; ++l) {
     const int64_t kin = l == 0 ? d->I + d->Ic : d->H;
-    add(d->w_ih[l], base + L.w_ih[l], l == 0 ? nullptr : base + L.w_ih_t[l], 4 * d->H, kin);
-    add(d->w_hh[l], base + L.w_hh[l], base + L.w_hh_t[l], 4 * d->H, d->H);
+    add(d->w_ih[l], base + L.w_ih[l], (l == 0 || !bwd) ? nullptr : base + L.w_ih_t[l], 4 * d->H, kin);
+    add(d->w_hh[l], base + L.w_hh[l], bwd ? base + L.w_hh_t[l] : nullptr, 4 * d->H, d->H);
   }
   if (d->head_w_mu) {  // the stacked operands of the Gaussian head behind this net (fhvae_lstm_desc.head_*)
     const int64_t D = d->head_D, K = d->head_K, ldt = d->head_ldt;
@@ -525,11 +463,16 @@ static FwdJobs<T> fwd_jobs(const fhvae_lstm_desc* d, const Ops<T>& op, int64_t w
       if (I > 0) J.xseg[0] = Seg{op.x + t * B * I, I, 1, w0, K0, 1, (int)I, 0};
       if (Ic > 0) J.xseg[1] = Seg{op.xc, Ic, 1, w0 + I, K0, 1, (int)Ic, 0};
     }
-    J.c_prev = t > 0 ? d->cs + (lt - 1) * B * H : nullptr;
-    J.c_out = d->cs + lt * B * H;
+    if (d->gates) {
+      J.c_prev = t > 0 ? d->cs + (lt - 1) * B * H : nullptr;
+      J.c_out = d->cs + lt * B * H;
+      J.gates_out = (T*)d->gates + lt * B * 4 * H;
+    } else {  // inference (fhvae_lstm_seq_infer): c in a two-slot ring per layer (L,2,B,H), no gates
+      J.c_prev = t > 0 ? d->cs + ((int64_t)l * 2 + ((t - 1) & 1)) * B * H : nullptr;
+      J.c_out = d->cs + ((int64_t)l * 2 + (t & 1)) * B * H;
+    }
     J.h_out = hs + lt * B * H;
     if (l == L - 1 && d->hs_top_f32) J.h_out_f32 = d->hs_top_f32 + t * B * H;
-    J.gates_out = (T*)d->gates + lt * B * 4 * H;
     if (d->hn && t == T_ - 1) {
       J.hn_out = d->hn + (int64_t)l * H;
       J.hn_ld = (int64_t)L * H;
@@ -630,16 +573,26 @@ static int lstm_fwd_impl(const fhvae_lstm_desc* d, const Ops<T>& op, hipStream_t
     // (measured at B = 2048, H = 512, bf16: 128x128 tiles 1.3-1.8 ms per net forward against 1.0-1.3 ms with 64x64: the
     //  heuristic stays "B >= 16384")
     const bool big_fwd = B >= 16384;
+    const bool save = d->gates != nullptr;  // (NULL: fhvae_lstm_seq_infer, the kernels' inference twins)
     if (big_fwd) {
       dim3 grid((unsigned)fh_cdiv(B, 128), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 128, 128, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
+      if (save)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 128, 128, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_infer_kernel<T, 128, 128, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
     } else if (B >= 1024) {
       // many workgroups per CU: 256-byte panels (32 KB LDS) so 2 workgroups per CU keep twice the bytes in flight
       dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 16), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, 16>), grid, dim3(kThreads), 0, st, jobs);
+      if (save)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, 16>), grid, dim3(kThreads), 0, st, jobs);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_infer_kernel<T, 64, 64, 4, 1, 16>), grid, dim3(kThreads), 0, st, jobs);
     } else {
       dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 16), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, kCH>), grid, dim3(kThreads), 0, st, jobs);
+      if (save)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, kCH>), grid, dim3(kThreads), 0, st, jobs);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_infer_kernel<T, 64, 64, 4, 1, kCH>), grid, dim3(kThreads), 0, st, jobs);
     }
     trace_end(st, ts);
     int e = fh_launch_status();
@@ -649,7 +602,7 @@ static int lstm_fwd_impl(const fhvae_lstm_desc* d, const Ops<T>& op, hipStream_t
 }
 
 extern "C" int fhvae_lstm_form(const fhvae_lstm_desc* d) {
-  if (!d || check_desc(d) != FHVAE_OK || !cluster_eligible(d)) return 0;
+  if (!d || check_desc(d, kCheckShape) != FHVAE_OK || !cluster_eligible(d)) return 0;
   return cluster_form(d);
 }
 
@@ -658,7 +611,7 @@ extern "C" int fhvae_lstm_form(const fhvae_lstm_desc* d) {
 // unit-major gates).  The schedule is re-derived per call from the descriptor and the environment: a caller keeps the forward's
 // value and compares it before the backward (hip_binding does; a mismatch would otherwise be silently wrong gradients).
 extern "C" int fhvae_lstm_layout_id(const fhvae_lstm_desc* d) {
-  if (!d || check_desc(d) != FHVAE_OK) return -1;
+  if (!d || check_desc(d, kCheckShape) != FHVAE_OK) return -1;
   if (d->dtype == FHVAE_BF16 && cluster_eligible(d)) return 16 + cluster_form(d) * 2 + (cluster_fwd_wr_ok(d) ? 1 : 0);
   return big_cells(d->B, d->H, d->dtype) && big_shape_ok(d) ? 1 : 0;
 }
@@ -681,12 +634,12 @@ __global__ void cast_hn_kernel(const float* __restrict__ s, u16* __restrict__ d,
   if (i < n) d[i] = f2bf(s[i]);
 }
 
-extern "C" int fhvae_lstm_seq_fwd(const fhvae_lstm_desc* d, void* stream) {
-  int e = check_desc(d);
-  if (e) return e;
+// the forward of a checked descriptor; gates == NULL: the inference forward (fhvae_lstm_seq_infer)
+static int lstm_seq_fwd_checked(const fhvae_lstm_desc* d, void* stream) {
+  int e;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == FHVAE_F32) {
-    if (d->lp) {
+    if (d->lp && d->gates) {  // (the transposed weights are the backward cells' operands)
       const Lp32Layout Y = lp32_layout(d);
       float* base = (float*)d->lp;
       TransBatch tb = {};
@@ -709,6 +662,25 @@ extern "C" int fhvae_lstm_seq_fwd(const fhvae_lstm_desc* d, void* stream) {
   const int64_t n = d->B * d->L * d->H;
   hipLaunchKernelGGL(cast_hn_kernel, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, st, d->hn, (u16*)d->hn_lp, n);
   return fh_launch_status();
+}
+
+extern "C" int fhvae_lstm_seq_fwd(const fhvae_lstm_desc* d, void* stream) {
+  const int e = check_desc(d);
+  return e ? e : lstm_seq_fwd_checked(d, stream);
+}
+
+// the persistent schedules keep c in registers / LDS; the per-step cells need c_{t-1} of every layer: a two-slot ring (L,2,B,H)
+extern "C" int64_t fhvae_lstm_infer_cs_elems(const fhvae_lstm_desc* d) {
+  if (!d || check_desc(d, kCheckShape) != FHVAE_OK) return 0;
+  if (d->dtype == FHVAE_BF16 && cluster_eligible(d)) return 0;
+  return 2 * (int64_t)d->L * d->B * d->H;
+}
+
+extern "C" int fhvae_lstm_seq_infer(const fhvae_lstm_desc* d, void* stream) {
+  int e = check_desc(d, kCheckInfer);
+  if (e) return e;
+  if (fhvae_lstm_infer_cs_elems(d) > 0 && !d->cs) return FHVAE_ERR_NULL;
+  return lstm_seq_fwd_checked(d, stream);
 }
 
 // the backward jobs of wavefront step w (layer l at time T-1-(w-(L-1-l)))

@@ -1,0 +1,125 @@
+"""eval_model.py -- what the reference's eval_model.py leaves as TODOs (eval_model.py:57-59: load data, evaluate, visualise),
+without the plotting: load a checkpoint, then write as .npy files under --out
+
+  z1_mu.npy, z2_mu.npy        per-segment posterior means (model.encode)
+  seq_ids.npy                 the sequence index of every segment
+  mu2.npy, mu2_seqs.npy       the closed-form per-sequence mu2 (utils.estimate_mu2_dict) and the sequences it covers
+  recon_x.npy, recon_mu.npy, recon_logvar.npy   the first --max-recon segments and model.reconstruct of them
+  convert_mu.npy, convert_logvar.npy            with --convert-to Y: those segments decoded with sequence Y's mu2
+  summary.json                the mean lower bound per frame over the data (forward() with zero noise: the ELBO at the
+                              posterior means), segment / sequence counts
+
+Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
+split of train_model.py (its dev split for the same --seed).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Evaluate a trained (Simple)FHVAE checkpoint: latents, mu2, reconstructions, conversion")
+    p.add_argument("--checkpoint", required=True)
+    p.add_argument("--out", required=True, help="output directory (created)")
+    p.add_argument("--feat-scp", default=None)
+    p.add_argument("--len-scp", default=None)
+    p.add_argument("--min-len", type=int, default=None)
+    p.add_argument("--mvn-path", default=None)
+    p.add_argument("--seg-shift", type=int, default=8)
+    # synthetic data (train_model.py's flags)
+    p.add_argument("--seg-len", type=int, default=20)
+    p.add_argument("--mels", type=int, default=80)
+    p.add_argument("--num-seqs", type=int, default=100)
+    p.add_argument("--segments", type=int, default=250)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--batch-size", type=int, default=2048)
+    p.add_argument("--convert-to", type=int, default=None, help="sequence index whose mu2 replaces z2 of the reconstructed segments")
+    p.add_argument("--max-recon", type=int, default=16)
+    return p
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        print("evaluation runs on a MI355X only (no CPU fallback)", file=sys.stderr)
+        return 1
+    import hip_binding as hb
+    import utils
+    from train_model import synthetic_split
+
+    dev = torch.device("cuda:0")
+    model = utils.load_checkpoint_file(args.checkpoint, finetune=True)[0].to(dev).eval()
+    T = getattr(model, "seg_len", args.seg_len)
+    undo = lambda a: a  # noqa: E731
+    if args.feat_scp is not None:
+        from datasets import NumpyDataset, ResidentSegmentPool
+
+        ds = NumpyDataset(args.feat_scp, args.len_scp, args.min_len if args.min_len is not None else T, args.mvn_path, T,
+                          args.seg_shift, False)
+        pool = ResidentSegmentPool(ds, dev)
+        S = len(ds)
+        undo = ds.undo_mvn
+
+        def batches():
+            return pool.epoch(args.batch_size, shuffle=False)
+    else:
+        S = args.num_seqs
+        x_all, i_all, n_all = synthetic_split(args.segments, T, args.mels, S, args.seed + 2)
+        x_all = x_all.to(dev)
+
+        def batches():
+            for s0 in range(0, x_all.shape[0], args.batch_size):
+                yield i_all[s0:s0 + args.batch_size], x_all[s0:s0 + args.batch_size], n_all[s0:s0 + args.batch_size]
+
+    if model.mu2_table is not None:
+        S = model.mu2_table.shape[0]
+    z1s, z2s, ids, lbs, frames = [], [], [], [], 0
+    recon_x = []
+    with torch.no_grad():
+        for idxs, x, nsegs in batches():
+            z1, z2 = model.encode(x)
+            z1s.append(z1.cpu().numpy()), z2s.append(z2.cpu().numpy()), ids.append(torch.as_tensor(idxs).cpu().numpy())
+            zero = (torch.zeros(x.shape[0], model.z2_dim, device=dev), torch.zeros(x.shape[0], model.z1_dim, device=dev))
+            lb = model(x, idxs, S, nsegs, eps=zero)[0]
+            lbs.append(float(lb.double().sum()))
+            frames += x.shape[0] * x.shape[1]
+            if sum(r.shape[0] for r in recon_x) < args.max_recon:
+                recon_x.append(x[: args.max_recon - sum(r.shape[0] for r in recon_x)])
+        mu2 = utils.estimate_mu2_dict(model, batches(), S)
+        os.makedirs(args.out, exist_ok=True)
+        out = lambda name, a: np.save(os.path.join(args.out, name), a)  # noqa: E731
+        out("z1_mu.npy", np.concatenate(z1s)), out("z2_mu.npy", np.concatenate(z2s)), out("seq_ids.npy", np.concatenate(ids))
+        seqs = sorted(mu2)
+        out("mu2_seqs.npy", np.asarray(seqs, dtype=np.int64))
+        out("mu2.npy", np.stack([mu2[y].cpu().numpy() for y in seqs]) if seqs else np.zeros((0, model.z2_dim), np.float32))
+        if recon_x and args.max_recon > 0:
+            xr = torch.cat(recon_x)
+            x_mu, x_lv = model.reconstruct(xr)
+            out("recon_x.npy", undo(xr.cpu().numpy())), out("recon_mu.npy", undo(x_mu.cpu().numpy()))
+            out("recon_logvar.npy", x_lv.cpu().numpy())  # (in the normalised feature space)
+            if args.convert_to is not None:
+                if args.convert_to not in mu2:
+                    print("--convert-to %d: no segment of that sequence in the data" % args.convert_to, file=sys.stderr)
+                    return 1
+                c_mu, c_lv = model.convert(xr, mu2[args.convert_to])
+                out("convert_mu.npy", undo(c_mu.cpu().numpy())), out("convert_logvar.npy", c_lv.cpu().numpy())
+    if hb.lstm_sync_status() != 0:
+        print("a persistent recurrence launch gave up: the results are invalid", file=sys.stderr)
+        return 3
+    summary = {"checkpoint": os.path.basename(args.checkpoint), "segments": int(sum(z.shape[0] for z in z1s)),
+               "sequences": len(mu2), "lower_bound_per_frame": sum(lbs) / max(frames, 1)}
+    with open(os.path.join(args.out, "summary.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    print(json.dumps(summary))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    sys.exit(main())

@@ -86,19 +86,44 @@ class FHVAE(FHVAEBase):
         """Table + gathered rows (simple_fhvae.py:39-54); the table persists instead of being redrawn."""
         return self.table_ops.lookup(mu_idx, num_seqs, mu2_table)
 
+    @torch.no_grad()
     def encode(self, x: torch.Tensor):
         """Inference-only latent extraction (eval_model.py:57-59 TODOs; used by utils.estimate_mu2_dict, utils.py:51-52):
-        returns (z1_mu, z2_mu) with z1 conditioned on the posterior MEAN of z2."""
+        returns (z1_mu, z2_mu) with z1 conditioned on the posterior MEAN of z2.  The nets run the forward that saves nothing
+        for a backward (hip_binding.lstm_seq_infer; FHVAE_NO_INFER=1: the training forward)."""
         x, _, _ = self._prep_inputs(x, torch.zeros(x.shape[0], dtype=torch.int64), 1)
         T = x.shape[1]
-        dt = hb.BF16 if self.compute_dtype == "bf16" else hb.F32
+        dt = self._dt()
         x_tm = hb.to_time_major(x, with_bf16=dt == hb.BF16)
-        _, hn2 = self.z2_pre_encoder(x_tm, None, T, dt)
+        _, hn2 = hb.lstm_seq_eval(x_tm, None, T, self.z2_pre_encoder.lstm.flat(), dt, top=0)
         z2_mu, z2_logvar, _ = self.z2_gauss_layer(hn2, sample=False)
-        _, hn1 = self.z1_pre_encoder(x_tm, z2_mu, T, dt)
+        _, hn1 = hb.lstm_seq_eval(x_tm, z2_mu, T, self.z1_pre_encoder.lstm.flat(), dt, top=0)
         z1_mu, z1_logvar, _ = self.z1_gauss_layer(hn1, sample=False)
         self.qz2_x = [z2_mu, z2_logvar]
         return z1_mu, z2_mu
+
+    def _dt(self):
+        return hb.BF16 if self.compute_dtype == "bf16" else hb.F32
+
+    @torch.no_grad()
+    def decode(self, z1: torch.Tensor, z2: torch.Tensor):
+        """x_mu, x_logvar (B, T, F) of the decoder on [z1 || z2] (z1 (B, z1_dim); z2 (B, z2_dim) or (z2_dim,) for every row):
+        the decoder net and per-frame head of forward(), on the same operand path (bf16 mode: the head contracts the bf16
+        states), without the saved-for-backward tensors."""
+        z1, z2 = self._prep_latents(z1, z2)
+        B, T, F_ = z1.shape[0], self.seg_len, self.n_feat
+        dt = self._dt()
+        lp_head = dt == hb.BF16 and self.x_hus[-1] % 8 == 0 and F_ % 8 == 0  # (as forward(): hip_binding.gauss_head's condition)
+        head = self.dec_gauss_layer.head_weights() if dt == hb.BF16 else None
+        hs_top, _ = hb.lstm_seq_eval(None, torch.cat([z1, z2], dim=-1), T, self.pre_decoder.lstm.flat(), dt,
+                                     top=1 if lp_head else 2, head=head)
+        H = hs_top.shape[-1]
+        hs_lp = getattr(hs_top, "_fh_lp", None) if lp_head else None
+        x_mu, x_logvar, _ = self.dec_gauss_layer(hs_top.reshape(T * B, H), sample=False,
+                                                 input_lp=hs_lp.reshape(T * B, H) if hs_lp is not None else None,
+                                                 shadows=getattr(hs_top, "_fh_head", None))
+        # time-major (T*B, F) -> batch-major (B, T, F)
+        return (x_mu.reshape(T, B, F_).transpose(0, 1).contiguous(), x_logvar.reshape(T, B, F_).transpose(0, 1).contiguous())
 
     def forward(self, x: torch.Tensor, mu_idx: torch.Tensor, num_seqs: int, num_segs, *, mu2_table=None, eps=None):
         self._check_idx(mu_idx, num_seqs)

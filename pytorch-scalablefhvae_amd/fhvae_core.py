@@ -108,6 +108,34 @@ class FHVAEBase(nn.Module):
             num_segs = num_segs.to(device=dev, dtype=torch.int64).contiguous()
         return x.contiguous(), mu_idx, num_segs
 
+    def _prep_latents(self, z1, z2):
+        """decode()'s inputs: z1 (B, z1_dim), z2 (B, z2_dim) or (z2_dim,) (one z2 for every row), f32 on the device."""
+        if not z1.is_cuda or not z2.is_cuda:
+            raise RuntimeError("decode (HIP path) needs the latents on a MI355X device; no CPU fallback")
+        if z1.dtype != torch.float32 or z2.dtype != torch.float32:
+            raise RuntimeError("decode takes float32 latents; got %s / %s" % (z1.dtype, z2.dtype))
+        if z1.dim() != 2 or z1.shape[1] != self.z1_dim:
+            raise ValueError("z1 must be (B, %d); got %s" % (self.z1_dim, tuple(z1.shape)))
+        if z2.dim() == 1:
+            z2 = z2.unsqueeze(0).expand(z1.shape[0], -1)
+        if z2.dim() != 2 or z2.shape[1] != self.z2_dim or z2.shape[0] != z1.shape[0]:
+            raise ValueError("z2 must be (%d, %d) or (%d,); got %s" % (z1.shape[0], self.z2_dim, self.z2_dim, tuple(z2.shape)))
+        return z1.contiguous(), z2.contiguous()
+
+    @torch.no_grad()
+    def reconstruct(self, x: torch.Tensor):
+        """(x_mu, x_logvar) shaped like x: decode(*encode(x)), the decoder at the posterior means of z1 and z2."""
+        x_mu, x_lv = self.decode(*self.encode(x))
+        return x_mu.reshape(x.shape), x_lv.reshape(x.shape)
+
+    @torch.no_grad()
+    def convert(self, x: torch.Tensor, z2: torch.Tensor):
+        """Sequence-factor transfer: the z1 means of x (conditioned on x's own z2 mean, as encode) decoded with the given z2
+        ((B, z2_dim) or (z2_dim,), e.g. model.mu2_table[y] or a row of utils.estimate_mu2_dict).  Shaped like x."""
+        z1, _ = self.encode(x)
+        x_mu, x_lv = self.decode(z1, z2)
+        return x_mu.reshape(x.shape), x_lv.reshape(x.shape)
+
     def _draw(self, eps, B, device):
         if eps is not None:
             return eps[0].to(device), eps[1].to(device)

@@ -104,6 +104,8 @@ SIGNATURES = {
     "fhvae_lstm_pre_elems": (_i64, [C.POINTER(LstmDesc)]),
     "fhvae_lstm_ws_below_elems": (_i64, [C.POINTER(LstmDesc)]),
     "fhvae_lstm_seq_fwd": (C.c_int, [C.POINTER(LstmDesc), _vp]),
+    "fhvae_lstm_infer_cs_elems": (_i64, [C.POINTER(LstmDesc)]),
+    "fhvae_lstm_seq_infer": (C.c_int, [C.POINTER(LstmDesc), _vp]),
     "fhvae_lstm_seq_bwd": (C.c_int, [C.POINTER(LstmBwdDesc), _vp]),
     "fhvae_lstm_param_grads_multi": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "fhvae_wgrad_desc_ok": (C.c_int, [_vp]),
@@ -848,6 +850,90 @@ def lstm_seq(x_tm, xc, T, params: Sequence[torch.Tensor], dtype: int = F32, top:
     tensor carries the gradient only (values undefined, data in its `_fh_lp`); 0 = only the final states are wanted.
     head: (w_mu, w_lv) of the Gaussian head behind this net, or None (see _LstmSeq.forward)."""
     return _LstmSeq.apply(x_tm, xc, int(T), int(dtype), int(top), head, *params)
+
+
+def lstm_seq_infer(x_tm, xc, T, params: Sequence[torch.Tensor], dtype: int = F32, top: int = 2, head=None):
+    """The forward of lstm_seq without what only its backward reads (fhvae_lstm_seq_infer): no activated gates, no (L,T,B,H)
+    cell states (a two-slot ring for the per-step schedules, nothing for the persistent ones), no transposed weight copies.
+    Same arguments, same schedule, bit-identical values; returns (hs_top or None (top == 0), hn) with the same `_fh_lp` /
+    `_fh_head` attributes (bf16, top == 1: hs_top is the bf16 top-layer states, as its `_fh_lp`).  Not differentiable: for
+    inference (encode / decode)."""
+    lib = load_library()
+    _need_gpu(x_tm, xc, *params)
+    L = len(params) // 4
+    assert len(params) == 4 * L and 1 <= L <= MAX_LAYERS
+    T, dtype, top = int(T), int(dtype), int(top)
+    params = [_f32c(p.detach()) for p in params]
+    H = params[1].shape[1]
+    x_lp = getattr(x_tm, "_fh_lp", None) if x_tm is not None else None
+    x_tm = _f32c(x_tm.detach()) if x_tm is not None else None
+    xc = _f32c(xc.detach()) if xc is not None else None
+    I = x_tm.shape[2] if x_tm is not None else 0
+    Ic = xc.shape[1] if xc is not None else 0
+    B = x_tm.shape[1] if x_tm is not None else xc.shape[0]
+    if x_tm is not None:
+        assert x_tm.shape[0] == T
+    assert params[0].shape == (4 * H, I + Ic), (params[0].shape, H, I, Ic)
+    dev = params[0].device
+    f32 = dict(device=dev, dtype=torch.float32)
+    bf = dtype == BF16
+    hs = torch.empty(L, T, B, H, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
+    hn = torch.empty(B, L * H, **f32)
+    hn_lp = torch.empty(B, L * H, device=dev, dtype=torch.bfloat16) if (bf and top == 0) else None
+    if not bf:
+        top = 2
+    hs_top = torch.empty(T, B, H, **f32) if (bf and top == 2) else None
+    d = LstmDesc()
+    dims = (L, B, T, I, Ic, H)
+    _fill_lstm_desc(d, dtype, dims, x_tm, xc, params, x_lp)
+    lp = None
+    if bf:  # bf16 operand copies + the persistent kernels' sync block (f32 mode: the workspace only serves the backward)
+        lp = torch.empty(int(lib.fhvae_lstm_lp_bytes(C.byref(d))), device=dev, dtype=torch.uint8)
+        LSTM_WORKSPACES.append(lp)
+        del LSTM_WORKSPACES[:-16]
+    d.lp = _p(lp)
+    d.hs, d.gates, d.hn, d.hs_top_f32, d.hn_lp = _p(hs), None, _p(hn), _p(hs_top), _p(hn_lp)
+    shadows = None
+    if bf and head is not None and head_shadow_shapes(head[0]) is not None:
+        hw_mu, hw_lv = _f32c(head[0].detach()), _f32c(head[1].detach())
+        (sl, st_) = head_shadow_shapes(hw_mu)
+        shadows = (torch.empty(sl, device=dev, dtype=torch.bfloat16), torch.empty(st_, device=dev, dtype=torch.bfloat16))
+        d.head_w_mu, d.head_w_lv, d.head_wl, d.head_wt = _p(hw_mu), _p(hw_lv), _p(shadows[0]), _p(shadows[1])
+        d.head_D, d.head_K, d.head_ldt = hw_mu.shape[0], hw_mu.shape[1], st_[1]
+    pre = torch.empty(max(1, int(lib.fhvae_lstm_pre_elems(C.byref(d)))), **f32)
+    d.pre = _p(pre)
+    n_cs = int(lib.fhvae_lstm_infer_cs_elems(C.byref(d)))
+    cs = torch.empty(n_cs, **f32) if n_cs > 0 else None
+    d.cs = _p(cs)
+    LAST_LSTM_FORM["form"] = int(lib.fhvae_lstm_form(C.byref(d)))
+    with _Timed("fhvae_lstm_seq_infer"):
+        _check(lib.fhvae_lstm_seq_infer(C.byref(d), _stream()), "fhvae_lstm_seq_infer")
+    LAST_LSTM_FORM["layout"] = int(lib.fhvae_lstm_layout_id(C.byref(d)))
+    if hn_lp is not None:
+        hn._fh_lp = hn_lp
+    hn._fh_head = shadows
+    if top == 0:
+        return None, hn
+    # (bf16, top == 1: the returned tensor is the bf16 top-layer states themselves -- no f32 tensor to route a gradient through)
+    out = hs_top if (bf and top == 2) else hs[L - 1]
+    if bf:
+        out._fh_lp = hs[L - 1]
+    out._fh_head = shadows
+    return out, hn
+
+
+def infer_enabled() -> bool:
+    """False under FHVAE_NO_INFER=1: the inference methods (encode / decode / reconstruct / convert) then run through the
+    saving forward lstm_seq instead of lstm_seq_infer (A/B and parity switch; read per call)."""
+    return not os.environ.get("FHVAE_NO_INFER")
+
+
+def lstm_seq_eval(x_tm, xc, T, params, dtype=F32, top=2, head=None):
+    """lstm_seq_infer, or lstm_seq under FHVAE_NO_INFER=1 (with top == 0 the placeholder output becomes None)."""
+    if infer_enabled():
+        return lstm_seq_infer(x_tm, xc, T, params, dtype, top, head)
+    out, hn = lstm_seq(x_tm, xc, T, params, dtype, top, head)
+    return (None if (top == 0 and dtype == BF16) else out), hn
 
 
 def raw_gather_rows(table, idx, idx_offset=0):

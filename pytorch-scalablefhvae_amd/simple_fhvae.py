@@ -107,6 +107,7 @@ class SimpleFHVAE(FHVAEBase):
         """Table + gathered rows (simple_fhvae.py:39-54); the table persists instead of being redrawn."""
         return self.table_ops.lookup(mu_idx, num_seqs, mu2_table)
 
+    @torch.no_grad()
     def encode(self, x: torch.Tensor):
         """Inference-only latent extraction (eval_model.py:57-59 TODOs; used by utils.estimate_mu2_dict, utils.py:51-52):
         returns (z1_mu, z2_mu) with z1 conditioned on the posterior MEAN of z2."""
@@ -115,6 +116,14 @@ class SimpleFHVAE(FHVAEBase):
         z1_mu, z1_logvar, _ = self.z1_gauss_layer(self.z1_pre_encoder(x, z2_mu), sample=False)
         self.qz2_x = [z2_mu, z2_logvar]
         return z1_mu, z2_mu
+
+    @torch.no_grad()
+    def decode(self, z1: torch.Tensor, z2: torch.Tensor):
+        """x_mu, x_logvar (B, input_size) of the FC pre-decoder and head on [z1 || z2] (z2 (B, z2_dim) or (z2_dim,)); the FC
+        model does not know T, the caller reshapes."""
+        z1, z2 = self._prep_latents(z1, z2)
+        x_mu, x_logvar, _ = self.dec_gauss_layer(self.pre_decoder(z1, z2), sample=False)
+        return x_mu, x_logvar
 
     def forward(self, x: torch.Tensor, mu_idx: torch.Tensor, num_seqs: int, num_segs, *, mu2_table=None, eps=None):
         self._check_idx(mu_idx, num_seqs)
