@@ -447,6 +447,33 @@ int fhvae_mu2_accumulate(const float* z2_mu, const int64_t* idx, float* zsum, fl
 int fhvae_mu2_finalize(const float* zsum, const float* count, float* mu2, int64_t S, int64_t D,
                        float ratio, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Hierarchical sampling (Hsu & Glass 2018; csrc/hs.hip): training works through blocks of K sequences whose mu2 rows are
+ * set in closed form from the current encoder before the block starts.  Data-dependent errors set bits of the int32 device
+ * word `status` (never cleared by the library; the host reads it once per block); host-visible argument errors return
+ * FHVAE_ERR_*.
+ * select: seq_ptr (S+1) is the CSR over sequences of a segment pool grouped by sequence; block_seqs (K) the block's
+ *   sequence ids.  Writes the block's segments in block order, then segment order: seg_ids[o] = seq_ptr[s] + j and
+ *   local_idx[o] = position of s in block_seqs, for o < cap; *n_out = the total (also when it exceeds cap).  An id outside
+ *   [0, S) counts as 0 segments and sets FHVAE_HS_BAD_SEQ; a total above cap sets FHVAE_HS_CAP.
+ * accumulate_sorted: zsum[local_idx[n],:] += z2_mu[n,:], count[local_idx[n]] += 1 for local_idx non-decreasing within the
+ *   call, without float atomics: bitwise reproducible for a fixed chunking.  A sequence may continue across calls (its
+ *   partial sum is carried in zsum).  An index outside [0, K) sets FHVAE_HS_BAD_IDX, a decreasing one FHVAE_HS_UNSORTED;
+ *   either makes the call (and every later call with that status word) add nothing.  D <= 256.
+ * load_table: table = zsum / (count + ratio) (0 where count is 0), m_rows = v_rows = 0 (the table's slice of the Adam
+ *   moments), then zsum = count = 0; one launch.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_HS_BAD_SEQ 1
+#define FHVAE_HS_CAP 2
+#define FHVAE_HS_BAD_IDX 4
+#define FHVAE_HS_UNSORTED 8
+int fhvae_hs_select(const int64_t* seq_ptr, int64_t S, const int64_t* block_seqs, int64_t K, int64_t* seg_ids,
+                    int64_t* local_idx, int64_t* n_out, int64_t cap, int32_t* status, void* stream);
+int fhvae_mu2_accumulate_sorted(const float* z2_mu, const int64_t* local_idx, float* zsum, float* count, int64_t N,
+                                int64_t K, int64_t D, int32_t* status, void* stream);
+int fhvae_mu2_load_table(float* zsum, float* count, float* table, float* m_rows, float* v_rows, int64_t K, int64_t D,
+                         float ratio, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -136,6 +136,17 @@ class NumpyDataset(torch.utils.data.Dataset):
         return idx, feat, self.seq_nsegs[idx]
 
 
+def seq_csr(seq_nsegs, seg_seq):
+    """(counts (S,), ptr (S+1,)) int64 host arrays: the CSR over sequences of a segment list grouped by sequence.
+    `seq_nsegs` gives each sequence's segment count (negative counts of make_segs mean none); `seg_seq` is the sequence index
+    of every segment, which must list sequence 0's segments first, then sequence 1's, ... (raises ValueError otherwise)."""
+    counts = np.maximum(np.asarray(seq_nsegs, dtype=np.int64).reshape(-1), 0)
+    seg_seq = np.asarray(seg_seq, dtype=np.int64).reshape(-1)
+    if not np.array_equal(seg_seq, np.repeat(np.arange(counts.shape[0], dtype=np.int64), counts)):
+        raise ValueError("segments are not grouped by sequence in sequence order (or do not match seq_nsegs): no CSR")
+    return counts, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
 class ResidentSegmentPool:
     """All utterances of a NumpyDataset resident in HBM + device-side minibatch cutting (fhvae_segment_gather)."""
 
@@ -151,6 +162,9 @@ class ResidentSegmentPool:
         seq_of = np.array([dataset.seq2idx[s.seq] for s in dataset.segs], dtype=np.int64)
         self.seg_start = torch.from_numpy(offs[seq_of] + np.array([s.start for s in dataset.segs], dtype=np.int64)).to(device)
         self.seg_seq = torch.from_numpy(seq_of).to(device)
+        # CSR over sequences (hierarchical sampling): segments of sequence s are pool segments [seq_ptr[s], seq_ptr[s+1])
+        self.seq_counts, ptr = seq_csr(dataset.seq_nsegs, seq_of)
+        self.seq_ptr = torch.from_numpy(ptr).to(device)
         self.seg_nsegs = torch.from_numpy(np.array(dataset.seq_nsegs, dtype=np.int64)[seq_of]).to(device)
         if dataset.mvn_params is not None:
             self.mean = torch.from_numpy(np.asarray(dataset.mvn_params["mean"], dtype=np.float32).reshape(-1)).to(device)
@@ -161,15 +175,54 @@ class ResidentSegmentPool:
     def __len__(self):
         return self.seg_start.shape[0]
 
+    def features(self, seg_ids: torch.Tensor):
+        """seg_ids (B,) int64 on the device -> features (B,T,F) (fhvae_segment_gather, MVN fused)."""
+        return self.hb.segment_gather(self.pool, self.seg_start[seg_ids], self.T, self.mean, self.inv_std)
+
     def batch(self, seg_ids: torch.Tensor):
         """seg_ids (B,) int64 on the device -> (idxs (B,), features (B,T,F), nsegs (B,)) like the reference's collate."""
-        st = self.seg_start[seg_ids]
-        x = self.hb.segment_gather(self.pool, st, self.T, self.mean, self.inv_std)
-        return self.seg_seq[seg_ids], x, self.seg_nsegs[seg_ids]
+        return self.seg_seq[seg_ids], self.features(seg_ids), self.seg_nsegs[seg_ids]
 
     def epoch(self, batch_size: int, shuffle=True, generator=None, drop_last=False):
         n = len(self)
         order = torch.randperm(n, device=self.seg_start.device, generator=generator) if shuffle else torch.arange(n, device=self.seg_start.device)
+        for s in range(0, n, batch_size):
+            ids = order[s:s + batch_size]
+            if drop_last and ids.shape[0] < batch_size:
+                break
+            yield self.batch(ids)
+
+
+class SyntheticSegmentPool:
+    """The synthetic split of train_model.py (random segments with random sequence ids) seen as a pool grouped by sequence:
+    its segments are stable-sorted by sequence once, at construction, so that `seq_ptr` is a CSR over them.  Same surface as
+    ResidentSegmentPool (`batch`, `features`, `epoch`, `seq_ptr`, `seq_counts`, `num_seqs`); `nsegs` stays per segment, as the
+    split draws it."""
+
+    def __init__(self, x: torch.Tensor, idx: torch.Tensor, nsegs: torch.Tensor, num_seqs: int, device="cuda"):
+        idx_h = torch.as_tensor(idx).to("cpu", torch.int64)
+        if idx_h.numel() and (int(idx_h.min()) < 0 or int(idx_h.max()) >= num_seqs):
+            raise ValueError("sequence index out of range [0, %d)" % num_seqs)
+        order = torch.sort(idx_h, stable=True).indices
+        self.num_seqs = int(num_seqs)
+        self.x = torch.as_tensor(x)[order].to(device)
+        self.seg_seq = idx_h[order].to(device)
+        self.seg_nsegs = torch.as_tensor(nsegs).to("cpu", torch.int64)[order].to(device)
+        self.seq_counts, ptr = seq_csr(np.bincount(idx_h.numpy(), minlength=self.num_seqs), idx_h[order].numpy())
+        self.seq_ptr = torch.from_numpy(ptr).to(device)
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    def features(self, seg_ids: torch.Tensor):
+        return self.x[seg_ids]
+
+    def batch(self, seg_ids: torch.Tensor):
+        return self.seg_seq[seg_ids], self.x[seg_ids], self.seg_nsegs[seg_ids]
+
+    def epoch(self, batch_size: int, shuffle=True, generator=None, drop_last=False):
+        n = len(self)
+        order = torch.randperm(n, device=self.x.device, generator=generator) if shuffle else torch.arange(n, device=self.x.device)
         for s in range(0, n, batch_size):
             ids = order[s:s + batch_size]
             if drop_last and ids.shape[0] < batch_size:

@@ -77,7 +77,17 @@ def main(argv=None) -> int:
             for s0 in range(0, x_all.shape[0], args.batch_size):
                 yield i_all[s0:s0 + args.batch_size], x_all[s0:s0 + args.batch_size], n_all[s0:s0 + args.batch_size]
 
-    if model.mu2_table is not None:
+    hs_K = torch.load(args.checkpoint, map_location="cpu", weights_only=False).get("hierarchical_sequences")
+    mu2_inject = None
+    if hs_K is not None:
+        # hierarchical sampling: the table holds the last training block's K sequences, not these.  S comes from the data, and
+        # the lower bound is taken at each sequence's closed-form mu2 (estimated by the sorted, deterministic path; injected)
+        from datasets import SyntheticSegmentPool
+        from hierarchical import estimate_pool_mu2
+
+        hs_pool = pool if args.feat_scp is not None else SyntheticSegmentPool(x_all, i_all, n_all, S, dev)
+        mu2_inject = estimate_pool_mu2(model, hs_pool)
+    elif model.mu2_table is not None:
         S = model.mu2_table.shape[0]
     z1s, z2s, ids, lbs, frames = [], [], [], [], 0
     recon_x = []
@@ -86,7 +96,7 @@ def main(argv=None) -> int:
             z1, z2 = model.encode(x)
             z1s.append(z1.cpu().numpy()), z2s.append(z2.cpu().numpy()), ids.append(torch.as_tensor(idxs).cpu().numpy())
             zero = (torch.zeros(x.shape[0], model.z2_dim, device=dev), torch.zeros(x.shape[0], model.z1_dim, device=dev))
-            lb = model(x, idxs, S, nsegs, eps=zero)[0]
+            lb = model(x, idxs, S, nsegs, eps=zero, mu2_table=mu2_inject)[0]
             lbs.append(float(lb.double().sum()))
             frames += x.shape[0] * x.shape[1]
             if sum(r.shape[0] for r in recon_x) < args.max_recon:

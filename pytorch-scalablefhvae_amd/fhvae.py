@@ -102,6 +102,19 @@ class FHVAE(FHVAEBase):
         self.qz2_x = [z2_mu, z2_logvar]
         return z1_mu, z2_mu
 
+    @torch.no_grad()
+    def encode_z2(self, x: torch.Tensor):
+        """z2_mu only: the z2 half of encode() (the same launches, so bitwise equal to encode(x)[1]) without the z1 net; what
+        the closed-form mu2 estimate reads (hierarchical sampling runs it over every segment of a block)."""
+        x, _, _ = self._prep_inputs(x, torch.zeros(x.shape[0], dtype=torch.int64), 1)
+        T = x.shape[1]
+        dt = self._dt()
+        x_tm = hb.to_time_major(x, with_bf16=dt == hb.BF16)
+        _, hn2 = hb.lstm_seq_eval(x_tm, None, T, self.z2_pre_encoder.lstm.flat(), dt, top=0)
+        z2_mu, z2_logvar, _ = self.z2_gauss_layer(hn2, sample=False)
+        self.qz2_x = [z2_mu, z2_logvar]
+        return z2_mu
+
     def _dt(self):
         return hb.BF16 if self.compute_dtype == "bf16" else hb.F32
 

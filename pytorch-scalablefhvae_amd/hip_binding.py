@@ -130,6 +130,9 @@ SIGNATURES = {
     "fhvae_segment_gather": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "fhvae_mu2_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     "fhvae_mu2_finalize": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _f32, _vp]),
+    "fhvae_hs_select": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "fhvae_mu2_accumulate_sorted": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "fhvae_mu2_load_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1340,3 +1343,94 @@ class Mu2Estimator:
             _check(lib.fhvae_mu2_finalize(_p(self.zsum), _p(self.count), _p(mu2), self.S, self.D, float(ratio), _stream()),
                    "fhvae_mu2_finalize")
         return mu2, self.count
+
+
+# --- hierarchical sampling (csrc/hs.hip) ----------------------------------------------------------------------------------
+# bits of the int32 device status word the three kernels below set (include/fhvae_hip.h, FHVAE_HS_*)
+HS_BAD_SEQ, HS_CAP, HS_BAD_IDX, HS_UNSORTED = 1, 2, 4, 8
+
+
+def hs_status_message(st: int) -> str:
+    names = [n for b, n in ((HS_BAD_SEQ, "sequence id out of range"), (HS_CAP, "segment total above capacity"),
+                            (HS_BAD_IDX, "local index out of range"), (HS_UNSORTED, "local indices not sorted")) if st & b]
+    return ", ".join(names) or "ok"
+
+
+def hs_select(seq_ptr, block_seqs, seg_ids, local_idx, n_out, status):
+    """The block's segments in CSR order: seg_ids[:n], local_idx[:n] (n = *n_out, on the device; writes stop at the buffers'
+    capacity).  seq_ptr (S+1,), block_seqs (K,), seg_ids / local_idx (cap,) int64; n_out (1,) int64; status (1,) int32."""
+    _need_gpu(seq_ptr, block_seqs, seg_ids, local_idx, n_out, status)
+    for t in (seq_ptr, block_seqs, seg_ids, local_idx, n_out):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise RuntimeError("hs_select takes contiguous int64 tensors")
+    if status.dtype != torch.int32 or seg_ids.shape != local_idx.shape:
+        raise RuntimeError("hs_select: status must be int32 and seg_ids / local_idx the same length")
+    lib = load_library()
+    with _Timed("fhvae_hs_select"):
+        _check(lib.fhvae_hs_select(_p(seq_ptr), seq_ptr.shape[0] - 1, _p(block_seqs), block_seqs.shape[0], _p(seg_ids),
+                                   _p(local_idx), _p(n_out), seg_ids.shape[0], _p(status), _stream()), "fhvae_hs_select")
+
+
+def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):
+    """zsum[local_idx[n]] += z2_mu[n], count[local_idx[n]] += 1 for non-decreasing local_idx; no float atomics (bitwise
+    reproducible for a fixed chunking).  Errors in the data set bits of `status`."""
+    _need_gpu(z2_mu, local_idx, zsum, count, status)
+    z2_mu = _f32c(z2_mu.detach())
+    if local_idx.dtype != torch.int64 or not local_idx.is_contiguous() or status.dtype != torch.int32:
+        raise RuntimeError("mu2_accumulate_sorted takes contiguous int64 indices and an int32 status word")
+    N, D = z2_mu.shape
+    if local_idx.shape[0] != N or zsum.shape[1] != D or count.shape[0] != zsum.shape[0]:
+        raise RuntimeError("mu2_accumulate_sorted: shapes do not agree")
+    if N == 0:
+        return
+    lib = load_library()
+    with _Timed("fhvae_mu2_accumulate_sorted"):
+        _check(lib.fhvae_mu2_accumulate_sorted(_p(z2_mu), _p(local_idx), _p(zsum), _p(count), N, zsum.shape[0], D, _p(status),
+                                               _stream()), "fhvae_mu2_accumulate_sorted")
+
+
+def mu2_load_table(zsum, count, table, m_rows, v_rows, ratio):
+    """table = zsum / (count + ratio) (0 where count is 0), m_rows = v_rows = 0, zsum = count = 0: one launch, in place."""
+    _need_gpu(zsum, count, table, m_rows, v_rows)
+    K, D = table.shape
+    for t in (zsum, table, m_rows, v_rows):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != K * D:
+            raise RuntimeError("mu2_load_table: every row buffer must be contiguous f32 of %d x %d" % (K, D))
+    if count.shape != (K,) or count.dtype != torch.float32:
+        raise RuntimeError("mu2_load_table: count must be (%d,) f32" % K)
+    lib = load_library()
+    with _Timed("fhvae_mu2_load_table"):
+        _check(lib.fhvae_mu2_load_table(_p(zsum), _p(count), _p(table), _p(m_rows), _p(v_rows), K, D, float(ratio), _stream()),
+               "fhvae_mu2_load_table")
+
+
+class SortedMu2Estimator:
+    """Closed-form mu2 estimate (utils.py:45-60) over batches whose indices are non-decreasing ACROSS the whole run of add()
+    calls (a segment pool walked in CSR order): fhvae_mu2_accumulate_sorted, bitwise reproducible for a fixed chunking.
+    Data errors land in `status` (one int32 device word); `check()` reads it (one host sync)."""
+
+    def __init__(self, num_seqs: int, dim: int, device, status=None):
+        self.S, self.D = int(num_seqs), int(dim)
+        self.zsum = torch.zeros(self.S, self.D, device=device, dtype=torch.float32)
+        self.count = torch.zeros(self.S, device=device, dtype=torch.float32)
+        self.status = status if status is not None else torch.zeros(1, device=device, dtype=torch.int32)
+
+    def add(self, z2_mu, idx):
+        mu2_accumulate_sorted(z2_mu, idx, self.zsum, self.count, self.status)
+
+    def check(self):
+        st = int(self.status.item())
+        if st != 0:
+            raise RuntimeError("sorted mu2 estimate: %s (status %d)" % (hs_status_message(st), st))
+
+    def result(self, ratio: float):
+        lib = load_library()
+        mu2 = torch.empty_like(self.zsum)
+        with _Timed("fhvae_mu2_finalize"):
+            _check(lib.fhvae_mu2_finalize(_p(self.zsum), _p(self.count), _p(mu2), self.S, self.D, float(ratio), _stream()),
+                   "fhvae_mu2_finalize")
+        return mu2, self.count
+
+    def load_into(self, table, m_rows, v_rows, ratio: float):
+        """Write the estimate into `table` in place, zero the moment rows, clear the accumulators (fhvae_mu2_load_table)."""
+        mu2_load_table(self.zsum, self.count, table, m_rows, v_rows, ratio)

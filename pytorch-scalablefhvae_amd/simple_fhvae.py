@@ -118,6 +118,14 @@ class SimpleFHVAE(FHVAEBase):
         return z1_mu, z2_mu
 
     @torch.no_grad()
+    def encode_z2(self, x: torch.Tensor):
+        """z2_mu only (bitwise equal to encode(x)[1], without the z1 pre-encoder)."""
+        x, _, _ = self._prep_inputs(x, torch.zeros(x.shape[0], dtype=torch.int64), 1)
+        z2_mu, z2_logvar, _ = self.z2_gauss_layer(self.z2_pre_encoder(x), sample=False)
+        self.qz2_x = [z2_mu, z2_logvar]
+        return z2_mu
+
+    @torch.no_grad()
     def decode(self, z1: torch.Tensor, z2: torch.Tensor):
         """x_mu, x_logvar (B, input_size) of the FC pre-decoder and head on [z1 || z2] (z2 (B, z2_dim) or (z2_dim,)); the FC
         model does not know T, the caller reshapes."""

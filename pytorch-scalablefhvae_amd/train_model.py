@@ -82,6 +82,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--exp-dir", default=None, help="write the reference-layout checkpoint there after every epoch")
     p.add_argument("--hierarchical", dest="sample_hierarchical", action="store_true",   # train_model.py:203-214
                    help="re-estimate the mu2 table in closed form from the encoder before training (utils.py:45-60)")
+    p.add_argument("--num-hierarchical-sequences", type=int, default=None,                 # train_model.py:203-214
+                   help="hierarchical sampling (Hsu & Glass 2018): train through blocks of K sequences; before each block the "
+                        "mu2 rows of its K sequences are set in closed form from the encoder, and the steps and the "
+                        "discriminative loss use only those K rows (the model's table has K rows).  Off when not given")
     p.add_argument("--compute-dtype", default="f32", choices=["f32", "bf16"])
     p.add_argument("--hip-graph", action="store_true",
                    help="capture one training step (zero_grad, forward, loss, backward, Adam) into a hipGraph and replay it for "
@@ -139,7 +143,19 @@ def main(argv=None) -> int:
     else:
         S = args.num_seqs
     input_size = T * F  # np.prod(example_data.shape), train_model.py:396-398
-    kw = dict(num_seqs=S, reference_compat=bool(args.reference_objective))
+    hs_K, syn_tr = None, None
+    if args.num_hierarchical_sequences is not None:
+        # hierarchical sampling: the table holds one block of K sequences, K clamped to the sequences that have segments
+        from hierarchical import hs_clamp
+
+        if real:
+            counts = tr_pool.seq_counts
+        else:
+            syn_tr = synthetic_split(args.train_segments, T, F, S, args.seed + 1)
+            counts = np.bincount(syn_tr[1].numpy(), minlength=S)
+        hs_K = hs_clamp(args.num_hierarchical_sequences, counts)
+    S_model = hs_K if hs_K is not None else S  # the table's rows: forward()'s num_seqs
+    kw = dict(num_seqs=S_model, reference_compat=bool(args.reference_objective))
     if args.reference_objective:
         print("WARNING: --reference-objective trains the reference's literal loss (+CE, detached decoder); "
               "throughput/ELBO figures of this build use the default objective", file=sys.stderr)
@@ -163,6 +179,10 @@ def main(argv=None) -> int:
 
         ck_model, _values, optim_state, start_epoch, ck_best, _ = load_checkpoint_file(args.continue_from, False, input_size=input_size)
         ck_sd = ck_model.state_dict()
+        if hs_K is not None and ("mu2_table" not in ck_sd or ck_sd["mu2_table"].shape[0] != hs_K):
+            raise ValueError("--continue-from with --num-hierarchical-sequences %d needs a checkpoint with a %d-row mu2 table "
+                             "(a hierarchical checkpoint of the same K); it has %s" % (
+                                 hs_K, hs_K, tuple(ck_sd["mu2_table"].shape) if "mu2_table" in ck_sd else "none"))
         ref_layout = "mu2_table" not in ck_sd  # a checkpoint of the reference itself: it never kept a table (simple_fhvae.py:51)
         model.load_state_dict(ck_sd, strict=not ref_layout)
         if optim_state is not None:
@@ -209,7 +229,7 @@ def main(argv=None) -> int:
 
         n_train = len(tr_pool)
     else:
-        xtr, itr, ntr = synthetic_split(args.train_segments, T, F, S, args.seed + 1)
+        xtr, itr, ntr = syn_tr if syn_tr is not None else synthetic_split(args.train_segments, T, F, S, args.seed + 1)
         xdv, idv, ndv = synthetic_split(args.dev_segments, T, F, S, args.seed + 2)
         xtr, xdv = xtr.to(device), xdv.to(device)
 
@@ -225,7 +245,7 @@ def main(argv=None) -> int:
 
         n_train = xtr.shape[0]
 
-    if args.sample_hierarchical:
+    if args.sample_hierarchical and hs_K is None:
         # closed-form mu2 from the current encoder (train_model.py:424-436); unlike the reference the result is USED:
         # it initialises the persistent table
         from utils import estimate_mu2_dict
@@ -246,7 +266,7 @@ def main(argv=None) -> int:
     def train_step(idxs, features, nsegs):
         """One iteration of the reference loop body, train_model.py:446-454."""
         optimizer.zero_grad()
-        lower_bound, discrim_loss, log_px_z, neg_kld_z1, neg_kld_z2, log_pmu2 = model(features, idxs, S, nsegs)
+        lower_bound, discrim_loss, log_px_z, neg_kld_z1, neg_kld_z2, log_pmu2 = model(features, idxs, S_model, nsegs)
         loss = loss_function(lower_bound, discrim_loss, args.alpha_dis)
         hb.backward(loss)  # (loss.backward() with a cached seed)
         optimizer.step()
@@ -303,37 +323,70 @@ def main(argv=None) -> int:
             return 3
         return None
 
+    trainer = None
+    if hs_K is not None:
+        # every block: select its segments, estimate + load its K table rows, one shuffled pass (hierarchical.py); dev sequences
+        # have no table rows: their mu2 is estimated the same way and injected (step 4 of the algorithm)
+        from datasets import SyntheticSegmentPool
+        from hierarchical import HierarchicalTrainer, estimate_pool_mu2
+
+        if real:
+            hs_tr, hs_dv = tr_pool, dv_pool
+        else:
+            hs_tr = SyntheticSegmentPool(xtr, itr, ntr, S, device)
+            hs_dv = SyntheticSegmentPool(xdv, idv, ndv, S, device)
+        trainer = HierarchicalTrainer(model, optimizer, hs_tr, hs_K, args.training_batch_size, graph_step, seed=args.seed)
+
+        def dev_lower_bounds():
+            dev_mu2 = estimate_pool_mu2(model, hs_dv)
+            return [model(features, idxs, hs_dv.num_seqs, nsegs, mu2_table=dev_mu2)[0]
+                    for idxs, features, nsegs in hs_dv.epoch(args.dev_batch_size, shuffle=False)]
+    else:
+        def dev_lower_bounds():
+            return [model(features, idxs, S, nsegs)[0] for idxs, features, nsegs in dev_batches()]
+
     for epoch in range(start_epoch, args.epochs):
         model.train()
         t0 = time.time()
         train_loss = torch.zeros((), device=device)
         nb = 0
-        for idxs, features, nsegs in train_batches():
-            loss, lower_bound = graph_step(idxs, features, nsegs)
-            train_loss += loss
-            nb += 1
-            if args.check_interval > 0 and nb % args.check_interval == 0:
-                rc = healthy()
-                if rc is not None:
-                    return rc
+        if trainer is not None:
+            checked = [0]
+
+            def block_check(steps):  # the divergence / recurrence words, at the first block end past each check interval
+                if args.check_interval > 0 and steps // args.check_interval > checked[0]:
+                    checked[0] = steps // args.check_interval
+                    return healthy()
+                return None
+
+            train_loss, nb, n_train, rc = trainer.run_epoch(epoch, check=block_check)
+            if rc is not None:
+                return rc
+        else:
+            for idxs, features, nsegs in train_batches():
+                loss, lower_bound = graph_step(idxs, features, nsegs)
+                train_loss += loss
+                nb += 1
+                if args.check_interval > 0 and nb % args.check_interval == 0:
+                    rc = healthy()
+                    if rc is not None:
+                        return rc
         rc = healthy()  # end of epoch, and before anything is checkpointed
         if rc is not None:
             return rc
         dt = time.time() - t0
         print(f"====> Train set average loss: {train_loss.item() / nb:.4f}  ({n_train / dt:.0f} segments/s)")
         model.eval()
-        lbs = []
         with torch.no_grad():
-            for idxs, features, nsegs in dev_batches():
-                lbs.append(model(features, idxs, S, nsegs)[0])
-        val_lower_bound = torch.cat(lbs)
+            val_lower_bound = torch.cat(dev_lower_bounds())
         print(f"====> Validation set lower bound: {val_lower_bound.mean().item():.4f} "
               f"({val_lower_bound.mean().item() / T:.4f} nats/frame)")
         if check_best(val_lower_bound, best_val_lb):
             best_epoch, best_val_lb = epoch, val_lower_bound.mean().item()
         if args.exp_dir:
             save_checkpoint(model, optimizer, None, {"val_lower_bound": val_lower_bound.mean().item()}, "run", epoch, best_epoch,
-                            val_lower_bound.mean().item(), best_val_lb, args.exp_dir, input_size=input_size)
+                            val_lower_bound.mean().item(), best_val_lb, args.exp_dir, input_size=input_size,
+                            hierarchical_sequences=hs_K)
         if check_terminate(epoch, best_epoch, args.patience, args.epochs):
             print("Training terminated!")
             break

@@ -52,10 +52,13 @@ def load_args(exp_dir):
 
 
 def save_checkpoint(model, optimizer, summary_list, values_dict, run_info: str, epoch: int, best_epoch: int,
-                    val_lower_bound: float, best_val_lb: float, checkpoint_dir: str, input_size=None) -> None:
+                    val_lower_bound: float, best_val_lb: float, checkpoint_dir: str, input_size=None,
+                    hierarchical_sequences=None) -> None:
     """Same dict layout and file names as utils.py:116-152.  `model_params` additionally carries the input size as
     its first element (the reference stores 5 values but both constructors take 6, utils.py:75,135-141); the mu2
-    table travels inside `state_dict` (key `mu2_table`)."""
+    table travels inside `state_dict` (key `mu2_table`).  `hierarchical_sequences` (K of a hierarchical-sampling run: the
+    table then holds the last block's K sequences, not one row per corpus sequence) adds a top-level key of that name; without
+    it the layout is unchanged."""
     if input_size is None:
         input_size = getattr(model, "seg_len", 1) * getattr(model, "n_feat", 0) or model.dec_gauss_layer.mulayer.out_features
     checkpoint = {
@@ -71,6 +74,8 @@ def save_checkpoint(model, optimizer, summary_list, values_dict, run_info: str, 
         # one key beyond the reference's layout: keyword-only constructor arguments of this build
         "model_kwargs": {k: getattr(model, k) for k in ("seg_len", "compute_dtype", "reference_compat") if hasattr(model, k)},
     }
+    if hierarchical_sequences is not None:
+        checkpoint["hierarchical_sequences"] = int(hierarchical_sequences)
     f_str = f"{model.model}_{run_info}_e{epoch}"
     f_path = Path(checkpoint_dir) / f"{f_str}.tar"
     torch.save(checkpoint, f_path)
