@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ScalableFHVAE training-step throughput on MI355X (contract: see the task statement).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
@@ -10,10 +10,12 @@ passes the one JSON line of rank 0 through.
 
 A "step" = zero_grad -> forward -> loss_function -> backward -> Adam over one synthetic (B,20,80) batch
 already resident in HBM (train_model.py:446-454).  Workload at N=1: BASELINE.json configs[2], the largest
-single-GPU configuration (fhvae.FHVAE 2x256 LSTM enc/dec, z1=z2=32, 28k-row mu2 table, batch 2048, bf16);
-configs[1] (4.6k-row table) at batch 2048 and at the reference's default training batch 256, and the headline workload in the
-exact-f32 parity mode, are reported beside it as `alt`.  value = segments/s over all ranks.
-N > 1: DP over the minibatch + the row-sharded mu2 table (dist_shard.py); beside the c3 headline the `alt` list carries
+single-GPU configuration (fhvae.FHVAE 2x256 LSTM enc/dec, z1=z2=32, 28k-row mu2 table, batch 2048, bf16).
+value = segments/s over all ranks.  A plain run measures that headline and nothing else: set-up, warm-up, the timed
+steps, --dump-outputs, the record.  --full adds everything else the record can carry (extras()): the instrumented
+`roofline` repeat, `roofline.hbm`, the `cpu_baseline` and the `alt` workloads -- at N=1 configs[1] (4.6k-row table) at
+batch 2048 and at the reference's default training batch 256, and the headline workload in the exact-f32 parity mode.
+N > 1: DP over the minibatch + the row-sharded mu2 table (dist_shard.py); with --full, beside the c3 headline the `alt` list carries
 configs[3] (2x512, 100k rows) and configs[4] (1M rows, T = 40, fp32) -- the workloads north_star's 8-GPU targets are quoted on.
 The distributed step is measured EAGERLY first and then as a captured hipGraph; a watchdog prints the eager record and ends the
 ranks if the captured form (RCCL collectives inside a graph, never run at N > 1 before the first hardware run) does not come back.
@@ -627,13 +629,32 @@ def run_gpu(cfg_name, B, dtype, steps, warmup, device, rank, world, use_dist, no
     return res
 
 
-def main():
+def extras(args, world, use_dist):
+    """What this run measures beside its headline figure: a plain run nothing; --full the instrumented roofline repeat
+    (+ `roofline.hbm` of the default single-GPU run), the `alt` workloads of the default run and the CPU baseline, each
+    unless its --no-* option says otherwise.  -> set of names out of {"roofline", "hbm", "alt", "cpu_baseline"}"""
+    if not args.full:
+        return set()
+    default_run = args.config is None
+    want = set()
+    if not args.no_roofline:
+        want.add("roofline")
+        if world == 1 and default_run and not args.no_hbm:
+            want.add("hbm")
+    if default_run and not args.batch and not args.no_alt and (world > 1 or not use_dist):
+        want.add("alt")
+    if world == 1 and not args.no_cpu_baseline:
+        want.add("cpu_baseline")
+    return want
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
-                    help="default: c3 (the largest single-GPU configuration of BASELINE.json), with the c2 figures as `alt`")
+                    help="default: c3 (the largest single-GPU configuration of BASELINE.json); with --full, the c2 figures as `alt`")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "f32"],
                     help="MFMA operand type of the LSTM nets (default: the config's -- bf16, configs[4] f32; f32 = exact-f32 parity mode)")
@@ -643,12 +664,15 @@ def main():
                     help="launch every kernel eagerly instead of replaying the captured hipGraph of the whole step")
     ap.add_argument("--force-dist", action="store_true", help="use the distributed runner even with one rank (testing)")
     ap.add_argument("--dist-graph", action="store_true", help="(default now; kept for older command lines)")
-    ap.add_argument("--no-hbm", action="store_true", help="skip the roofline.hbm sub-record (achieved GB/s of the streaming kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: roofline (+ roofline.hbm), the alt workloads, the CPU "
+                         "baseline (default: the headline alone)")
+    ap.add_argument("--no-hbm", action="store_true", help="--full: skip the roofline.hbm sub-record (achieved GB/s of the streaming kernels)")
     ap.add_argument("--no-dist-graph", action="store_true",
                     help="run the distributed step eagerly instead of replaying its captured hipGraph (collectives included)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the instrumented roofline repeat")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the alt workloads")
     ap.add_argument("--launch-timeout", type=int, default=1500,
                     help="self-launched N > 1 run: seconds before the rank tree is killed and ONE fresh tree is started with "
                          "--no-dist-graph --no-alt (0 = no limit)")
@@ -658,10 +682,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps of the headline run, write what its last step returned (loss, lower bound per "
                          "segment) as DIR/<name>.npy, float32/float64, 64 MB at most")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
     if os.environ.get("FHVAE_BENCH_TEST_SLEEP"):  # tests/test_bench_cpu.py: a rank that never comes back (before anything touches a GPU)
@@ -697,7 +725,7 @@ def main():
     import hip_binding as hb
 
     hb.load_library()
-    default_run = args.config is None
+    want = extras(args, world, use_dist)
     cfg_name = args.config or "c3"
     cfg = CONFIGS[cfg_name]
     dtype = "f32" if cfg.get("simple") else (args.dtype or cfg.get("dtype", "bf16"))
@@ -742,7 +770,7 @@ def main():
             watchdog_arm(args.phase_timeout, "hipGraph capture + replay of the %s step" % cfg_name)
 
     main_res = run_gpu(cfg_name, B, dtype, args.steps, args.warmup, device, rank, world, use_dist, args.no_graph,
-                       not args.no_roofline, args.idx, use_dist and not args.no_dist_graph, on_eager=on_eager_main,
+                       "roofline" in want, args.idx, use_dist and not args.no_dist_graph, on_eager=on_eager_main,
                        dump_dir=args.dump_outputs)
     watchdog_disarm()
     state["main"] = main_res
@@ -752,12 +780,12 @@ def main():
                 "unit": "segments/s", "ms_per_step": r["ms_per_step"], "launch": r["launch"],
                 "elbo_nats_per_frame": r["elbo_nats_per_frame"], "dtype": r["dtype"], **({"eager": r["eager"]} if "eager" in r else {})}
 
-    if default_run and world == 1 and not use_dist and not args.batch and not args.no_alt:
+    if "alt" in want and world == 1:
         for name, b, dt_alt in ALT_RUNS:  # configs[1] at both reference batch sizes and the headline in f32: same method (graph replay)
             r = run_gpu(name, b, dt_alt or args.dtype or CONFIGS[name].get("dtype", "bf16"), args.steps, 3, device, rank, world, False,
                         args.no_graph, False, args.idx)
             state["alts"].append(alt_entry(name, b, r))
-    if default_run and world > 1 and not args.batch and not args.no_alt:
+    if "alt" in want and world > 1:
         # the configurations the 8-GPU targets are quoted on (row-sharded 100k / 1M-row tables), same method as the headline;
         # every rank runs them (they contain collectives); a phase that hangs ends the run with what is already measured
         for name, b, dt_alt in ALT_RUNS_DIST:
@@ -770,10 +798,10 @@ def main():
 
     if rank == 0:
         rec = build_record(main_res)
-        if "roofline" in rec and world == 1 and default_run and not args.no_hbm:
+        if "hbm" in want:
             # the HBM-bound kernels of the path beside the MFMA-bound dominant one (~2 s, 5 GB of scratch tensors)
             rec["roofline"]["hbm"] = {"peak_gbps": 8000.0, "kernels": hbm_record(device)}
-        if not args.no_cpu_baseline and world == 1:
+        if "cpu_baseline" in want:
             rec["cpu_baseline"] = cpu_baseline(cfg, main_res["dtype"])
         emit(rec)
     if use_dist:

@@ -1,5 +1,6 @@
 """bench.py's protection of the first multi-GPU run (no GPU needed): the watchdog that prints what was already measured when a
-phase does not come back, and the self-launcher's time limit with one fresh retry; --dump-outputs' writer."""
+phase does not come back, and the self-launcher's time limit with one fresh retry; --dump-outputs' writer; what a plain and a
+--full run measure beside the headline."""
 import os
 import subprocess
 import sys
@@ -89,3 +90,25 @@ def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
     # the same arrays give the same sample
     bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
     np.testing.assert_array_equal(np.load(tmp_path / "b" / "bigger.npy"), files["bigger"])
+
+
+def test_plain_run_measures_the_headline_alone_and_full_everything_else():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def want(argv, world=1, use_dist=False):
+        return bench.extras(bench.parse_args(argv), world, use_dist)
+
+    base = ["--gpus", "1", "--steps", "5", "--warmup", "2"]
+    for extra in ([], ["--config", "c4"], ["--idx", "zipf"], ["--dump-outputs", "d"], ["--batch", "256"]):
+        assert want(base + extra) == set()
+    assert want(["--gpus", "2"], world=2, use_dist=True) == set()
+    assert want(["--force-dist"], use_dist=True) == set()
+    # --full: each extra where the workload has it, unless its --no-* option is given
+    assert want(base + ["--full"]) == {"roofline", "hbm", "alt", "cpu_baseline"}
+    assert want(base + ["--full", "--no-roofline"]) == {"alt", "cpu_baseline"}
+    assert want(base + ["--full", "--no-hbm", "--no-alt", "--no-cpu-baseline"]) == {"roofline"}
+    assert want(base + ["--full", "--config", "c4"]) == {"roofline", "cpu_baseline"}
+    assert want(base + ["--full", "--batch", "256"]) == {"roofline", "hbm", "cpu_baseline"}
+    assert want(["--full", "--force-dist"], use_dist=True) == {"roofline", "hbm", "cpu_baseline"}
+    assert want(["--gpus", "2", "--full"], world=2, use_dist=True) == {"roofline", "alt"}

@@ -27,11 +27,11 @@ for w in $WHAT; do
       stats c5 --config c5
       ;;
     bench)
-      python3 $R/bench.py > $O/bench_default_c3.json 2> $O/bench_default_c3.log
-      python3 $R/bench.py --config c4 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.log
-      python3 $R/bench.py --config c5 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.log
-      python3 $R/bench.py --idx zipf --no-cpu-baseline --no-alt > $O/bench_c3_zipf.json 2> $O/bench_c3_zipf.log
-      python3 $R/bench.py --config c1 --no-cpu-baseline > $O/bench_c1.json 2> $O/bench_c1.log
+      python3 $R/bench.py --full > $O/bench_default_c3.json 2> $O/bench_default_c3.log
+      python3 $R/bench.py --config c4 --full --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.log
+      python3 $R/bench.py --config c5 --full --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.log
+      python3 $R/bench.py --idx zipf --full --no-cpu-baseline --no-alt > $O/bench_c3_zipf.json 2> $O/bench_c3_zipf.log
+      python3 $R/bench.py --config c1 --full --no-cpu-baseline > $O/bench_c1.json 2> $O/bench_c1.log
       echo bench done
       ;;
     pmc)
@@ -53,7 +53,7 @@ for w in $WHAT; do
       echo stream done
       ;;
     dist)  # the distributed runner on one rank (captured step) beside the single-GPU step
-      python3 $R/bench.py --force-dist --no-cpu-baseline --no-alt --no-hbm > $O/bench_c3_dist_world1.json 2> $O/bench_c3_dist_world1.log
+      python3 $R/bench.py --force-dist --full --no-cpu-baseline --no-alt --no-hbm > $O/bench_c3_dist_world1.json 2> $O/bench_c3_dist_world1.log
       python3 $R/bench.py --no-cpu-baseline --no-alt --no-hbm --no-roofline > $O/bench_c3_single_ref.json 2> $O/bench_c3_single_ref.log
       echo dist done
       ;;
