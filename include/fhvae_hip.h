@@ -473,6 +473,15 @@ int fhvae_mu2_accumulate_sorted(const float* z2_mu, const int64_t* local_idx, fl
                                 int64_t K, int64_t D, int32_t* status, void* stream);
 int fhvae_mu2_load_table(float* zsum, float* count, float* table, float* m_rows, float* v_rows, int64_t K, int64_t D,
                          float ratio, void* stream);
+/* Across W ranks (rank r owns rows [row0, row1) of the K-row table; every rank accumulates part of the block's segments):
+ * hs_pack_partials: out (K, D+1) = [zsum | count], then zsum = count = 0; one launch.
+ * mu2_merge_load_shard: parts (W, K, D+1) are the W ranks' packed partials in rank order.  For the rows in [row0, row1):
+ *   sum = parts[0] + parts[1] + ... + parts[W-1] (added in that order, the count column the same way),
+ *   shard[k - row0] = sum / (count + ratio) (0 where count is 0), m_rows = v_rows = 0 (the shard's slice of the Adam moments,
+ *   (row1 - row0, D)); one launch, none for an empty shard (row0 == row1).  0 <= row0 <= row1 <= K. */
+int fhvae_hs_pack_partials(float* zsum, float* count, float* out, int64_t K, int64_t D, void* stream);
+int fhvae_mu2_merge_load_shard(const float* parts, int64_t W, int64_t K, int64_t row0, int64_t row1, float* shard,
+                               float* m_rows, float* v_rows, int64_t D, float ratio, void* stream);
 
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */

@@ -5,6 +5,10 @@
 //                                bitwise reproducible for a fixed chunking
 //   fhvae_mu2_load_table       : table rows = zsum / (count + ratio) written in place, their Adam moment rows zeroed and the
 //                                accumulators cleared, in one launch
+// Across ranks (the row-sharded K-row table of dist_shard): every rank accumulates a contiguous range of the block's segments,
+//   fhvae_hs_pack_partials     : [zsum | count] into one (K, D+1) buffer (one all-gather moves it) and the accumulators cleared
+//   fhvae_mu2_merge_load_shard : the W gathered partials of the rank's own rows summed in rank order, then loaded like
+//                                fhvae_mu2_load_table: the order is fixed, so every rank loads the same bits for a given W
 // Data-dependent errors (a bad sequence id, a total above cap, unsorted or out-of-range local indices) set bits of a
 // device status word (FHVAE_HS_*) that the host reads once per block; no input makes a kernel read or write out of bounds.
 #include "common.h"
@@ -196,6 +200,41 @@ __global__ void mu2_load_table_kernel(float* __restrict__ zsum, float* __restric
   if (lane == 0) cnt[k] = n * 0.f;  // (a store whose value depends on the loaded count: issued after every lane read it)
 }
 
+// one thread per element of the (K, D+1) buffer: column D carries the count; each thread clears what it read
+__global__ void hs_pack_partials_kernel(float* __restrict__ zsum, float* __restrict__ cnt, float* __restrict__ out, int64_t K,
+                                        int64_t D) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= K * (D + 1)) return;
+  const int64_t k = e / (D + 1), d = e - k * (D + 1);
+  if (d < D) {
+    out[e] = zsum[k * D + d];
+    zsum[k * D + d] = 0.f;
+  } else {
+    out[e] = cnt[k];
+    cnt[k] = 0.f;
+  }
+}
+
+// one thread per element of the shard's rows [row0, row1): the W partials of its row are added one rank after the other
+// (rank 0 first), the count the same way, so the result does not depend on the transport that gathered them
+__global__ void mu2_merge_load_shard_kernel(const float* __restrict__ parts, int64_t W, int64_t K, int64_t row0, int64_t rows,
+                                            float* __restrict__ shard, float* __restrict__ m, float* __restrict__ v, int64_t D,
+                                            float ratio) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= rows * D) return;
+  const int64_t r = e / D, d = e - r * D;
+  const float* p = parts + (row0 + r) * (D + 1);
+  const int64_t step = K * (D + 1);
+  float s = 0.f, n = 0.f;
+  for (int64_t w = 0; w < W; ++w, p += step) {
+    s += p[d];
+    n += p[D];
+  }
+  shard[e] = n > 0.f ? s / (n + ratio) : 0.f;  // as mu2_load_table_kernel
+  m[e] = 0.f;
+  v[e] = 0.f;
+}
+
 }  // namespace fh
 
 using namespace fh;
@@ -249,5 +288,34 @@ extern "C" int fhvae_mu2_load_table(float* zsum, float* count, float* table, flo
   FH_CHECK_I32(fh_cdiv(K * 64, 256));
   hipLaunchKernelGGL(mu2_load_table_kernel, dim3((unsigned)fh_cdiv(K * 64, 256)), dim3(256), 0, (hipStream_t)stream, zsum, count,
                      table, m_rows, v_rows, K, D, ratio);
+  return fh_launch_status();
+}
+
+extern "C" int fhvae_hs_pack_partials(float* zsum, float* count, float* out, int64_t K, int64_t D, void* stream) {
+  FH_CHECK_PTR(zsum);
+  FH_CHECK_PTR(count);
+  FH_CHECK_PTR(out);
+  FH_CHECK_POS(K);
+  FH_CHECK_POS(D);
+  FH_CHECK_I32(fh_cdiv(K * (D + 1), 256));
+  hipLaunchKernelGGL(hs_pack_partials_kernel, dim3((unsigned)fh_cdiv(K * (D + 1), 256)), dim3(256), 0, (hipStream_t)stream, zsum,
+                     count, out, K, D);
+  return fh_launch_status();
+}
+
+extern "C" int fhvae_mu2_merge_load_shard(const float* parts, int64_t W, int64_t K, int64_t row0, int64_t row1, float* shard,
+                                          float* m_rows, float* v_rows, int64_t D, float ratio, void* stream) {
+  FH_CHECK_PTR(parts);
+  FH_CHECK_POS(W);
+  FH_CHECK_POS(K);
+  FH_CHECK_POS(D);
+  if (row0 < 0 || row1 < row0 || row1 > K) return FHVAE_ERR_SHAPE;
+  if (row1 == row0) return FHVAE_OK;  // an empty shard (more ranks than rows): nothing to load
+  FH_CHECK_PTR(shard);
+  FH_CHECK_PTR(m_rows);
+  FH_CHECK_PTR(v_rows);
+  FH_CHECK_I32(fh_cdiv((row1 - row0) * D, 256));
+  hipLaunchKernelGGL(mu2_merge_load_shard_kernel, dim3((unsigned)fh_cdiv((row1 - row0) * D, 256)), dim3(256), 0,
+                     (hipStream_t)stream, parts, W, K, row0, row1 - row0, shard, m_rows, v_rows, D, ratio);
   return fh_launch_status();
 }

@@ -29,6 +29,19 @@ import torch.distributed as dist
 import torch.nn as nn
 
 
+def rank_slice(n: int, world: int, rank: int) -> Tuple[int, int, int]:
+    """How a global batch of n segments is cut over `world` ranks: it is cut down to a multiple of `world` (the runner's 1/W
+    gradient scale and its all-gather need equal local batch sizes) and rank r takes the r-th of `world` equal contiguous
+    slices.  Returns (begin, end, skipped): positions [begin, end) of the batch, and the n % world segments nobody trains."""
+    per = n // world
+    return rank * per, (rank + 1) * per, n - per * world
+
+
+def rank_range(n: int, world: int, rank: int) -> Tuple[int, int]:
+    """[n*r/W, n*(r+1)/W): the contiguous share of n items of rank r (the shares cover [0, n) once, sizes differ by <= 1)."""
+    return n * rank // world, n * (rank + 1) // world
+
+
 class HipBackend:
     """Local compute on the HIP kernels (include/fhvae_hip.h)."""
 
@@ -214,16 +227,30 @@ class ShardedTableOps:
     def __init__(self, shard: nn.Parameter, sh: ShardCtx):
         self.shard, self.sh = shard, sh
         self._idx = None
+        self._injected = False
 
     def lookup(self, mu_idx, num_seqs, mu2_table=None):
+        self._injected = False
         if mu2_table is not None:
-            raise ValueError("mu2_table injection is a single-GPU parity feature")
+            # evaluation only (hierarchical sampling's dev bound: every rank holds the same whole injected table): the
+            # single-GPU arithmetic on this rank's queries, no collectives
+            if torch.is_grad_enabled():
+                raise ValueError("mu2_table injection is a single-GPU parity feature")
+            import hip_binding as hb
+
+            self._injected = True
+            return mu2_table, hb.mu2_gather(mu2_table, mu_idx)
         if int(num_seqs) != self.sh.S:
             raise ValueError("num_seqs=%d does not match the sharded table (%d rows)" % (num_seqs, self.sh.S))
         self._idx = mu_idx
         return self.shard, None  # the rows arrive with the CE in resolve(): one exchange for both
 
     def resolve(self, z2_mu, table, mu_idx, mu2, sign=1.0):
+        if self._injected:
+            import hip_binding as hb
+
+            self._injected = False
+            return mu2, hb.disc_lse(z2_mu, table, mu_idx, lp=self.sh.backend.lp, sign=sign)
         mu2, ce, _ = _ShardTable.apply(z2_mu, self.shard, self._idx if mu_idx is None else mu_idx, self.sh, float(sign))
         return mu2, ce
 
@@ -355,7 +382,9 @@ class DistributedFHVAE:
         named = self._named_net_params()
         slot = {id(p): i for i, p in enumerate(self.opt_nets._params)}
         t = tab["state"][0]
-        state = {0: {"step": t["step"], "exp_avg": self._gather_rows(t["exp_avg"]), "exp_avg_sq": self._gather_rows(t["exp_avg_sq"])}}
+        # the step count of the nets: an empty shard's opt_table never steps (adam_step_ has no elements to launch on), and
+        # one GPU's FusedAdam keeps ONE count for all parameters; every non-empty shard's count equals the nets' anyway
+        state = {0: {"step": torch.tensor(float(self.opt_nets.step_dev.item())), "exp_avg":self._gather_rows(t["exp_avg"]), "exp_avg_sq": self._gather_rows(t["exp_avg_sq"])}}
         for j, (n, p) in enumerate(named):
             state[j + 1] = nets["state"][slot[id(p)]]
         groups = [dict(nets["param_groups"][0], params=list(range(len(named) + 1)))]

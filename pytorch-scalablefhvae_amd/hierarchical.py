@@ -6,6 +6,8 @@ over only those K rows.  A step's cost and memory depend on K, not on the corpus
   plan_epoch            host: the epoch's blocks (numpy Generator seeded from (seed, epoch)), every block K distinct sequences
   HierarchicalTrainer   device: per block select (fhvae_hs_select) -> estimate (encode_z2 + fhvae_mu2_accumulate_sorted)
                         -> load (fhvae_mu2_load_table into the FusedAdam arena) -> one shuffled pass of training steps
+  DistributedHierarchicalTrainer  the same blocks on W ranks over the row-sharded K-row table (dist_shard): each rank estimates
+                        a range of the block, the partials are all-gathered and summed in rank order (fhvae_mu2_merge_load_shard)
   estimate_pool_mu2     every sequence's mu2 of a pool by the same deterministic path (dev evaluation in this mode)
 
 The model's table has K rows; row i holds the mu2 of the current block's i-th sequence, so a table row means nothing across blocks.
@@ -17,6 +19,8 @@ from typing import Callable, Optional
 
 import numpy as np
 import torch
+
+from dist_shard import rank_range, rank_slice
 
 
 def eligible_sequences(seq_counts) -> np.ndarray:
@@ -86,8 +90,8 @@ class HierarchicalTrainer:
         import hip_binding as hb
 
         if not isinstance(model.table_ops, LocalTableOps):
-            raise ValueError("hierarchical sampling needs the single-GPU mu2 table; a row-sharded table (dist_shard) is not "
-                             "supported")
+            raise ValueError("HierarchicalTrainer needs the single-GPU mu2 table; a row-sharded table (dist_shard) is trained "
+                             "by DistributedHierarchicalTrainer")
         table = model.mu2_table
         if table is None or table.shape[0] != K:
             raise ValueError("hierarchical sampling with K=%d needs a model built with num_seqs=K" % K)
@@ -201,6 +205,114 @@ class HierarchicalTrainer:
                     return total, nb, nseg, rc
         self._read_words()  # the last block's estimate status
         return total, nb, nseg, None
+
+
+class DistributedHierarchicalTrainer(HierarchicalTrainer):
+    """The blocks of hierarchical sampling on W ranks: the K-row table is row-sharded by `runner` (dist_shard.DistributedFHVAE,
+    rank r owns rows [row0, row1)), the nets are replicated.
+
+    select     every rank selects the whole block (the plan and fhvae_hs_select are deterministic: identical on every rank)
+    estimate   rank r encodes the contiguous range rank_range(N, W, r) of the block's CSR list into its own (K, D) sums; a
+               sequence that crosses a range boundary is split over two ranks, which the merge makes whole
+    merge      fhvae_hs_pack_partials -> ONE all-gather of (K, D+1) -> fhvae_mu2_merge_load_shard: the W partials of the own
+               rows summed in rank order (independent of how the transport reduces: identical on every rank for a given W),
+               loaded into the shard, its Adam moment rows zeroed
+    train      the block's shuffled pass as on one GPU (the same seeded generator on every rank); each global batch of B is cut
+               to a multiple of W (rank_slice) and rank r steps on its slice: step_fn(local_idx, x, nsegs)
+    The status word is all-reduced (MAX) where it is read, so every rank raises together.
+    """
+
+    def __init__(self, runner, pool, K: int, batch_size: int, step_fn: Callable, seed: int = 0, chunk: int = 4096,
+                 log: Optional[Callable] = print):
+        import hip_binding as hb
+
+        model, sh = runner.model, runner.sh
+        if sh.S != K:
+            raise ValueError("hierarchical sampling with K=%d needs a model built with num_seqs=K (the runner's table has %d rows)"
+                             % (K, sh.S))
+        self.hb, self.runner, self.sh, self.model, self.opt, self.pool = hb, runner, sh, model, None, pool
+        self.K, self.D, self.B = int(K), int(runner.shard.shape[1]), int(batch_size)
+        if self.B % sh.world:
+            raise ValueError("the batch size %d is not a multiple of the %d ranks" % (self.B, sh.world))
+        self.step_fn, self.chunk, self.log = step_fn, int(chunk), log
+        self.seed = int(seed)
+        self.dev = runner.shard.device
+        self.eligible = eligible_sequences(pool.seq_counts)
+        if self.K > len(self.eligible):
+            raise ValueError("K=%d exceeds the %d sequences that have segments" % (self.K, len(self.eligible)))
+        n = runner.shard.numel()  # the shard is the only parameter of opt_table: its moments are the arena's first n
+        self.m_rows, self.v_rows = runner.opt_table.m[:n], runner.opt_table.v[:n]
+        cap = int(np.sort(np.asarray(pool.seq_counts, dtype=np.int64))[::-1][:self.K].sum())
+        self.seg_ids = torch.zeros(cap, dtype=torch.int64, device=self.dev)
+        self.local_idx = torch.zeros(cap, dtype=torch.int64, device=self.dev)
+        self.words = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        self.n_out, self.status = self.words[0:1], self.words[1:2].view(torch.int32)[0:1]
+        self.est = hb.SortedMu2Estimator(self.K, self.D, self.dev, status=self.status)
+        self.packed = torch.zeros(self.K, self.D + 1, device=self.dev, dtype=torch.float32)
+        self.ratio = mu2_ratio(model)
+        self.gen = torch.Generator(device=self.dev)
+        self.gen.manual_seed(self.seed)
+        self.times = {}
+        self.skipped = 0  # segments of ragged last batches nobody trained (at most W - 1 per block)
+
+    def _read_words(self):
+        # words[0] (the block's segment count) is the same on every rank; MAX over the status half raises on every rank at once
+        self.sh.all_reduce_(self.words, op=torch.distributed.ReduceOp.MAX)
+        return super()._read_words()
+
+    @torch.no_grad()
+    def estimate(self, N: int):
+        a, b = rank_range(N, self.sh.world, self.sh.rank)
+        for c0 in range(a, b, self.chunk):
+            c1 = min(b, c0 + self.chunk)
+            z2 = self.model.encode_z2(self.pool.features(self.seg_ids[c0:c1]))
+            self.est.add(z2, self.local_idx[c0:c1])
+
+    def load(self):
+        """The merge: pack -> all-gather -> rank-order sum + load of the own rows (two launches, one collective)."""
+        self.hb.hs_pack_partials(self.est.zsum, self.est.count, self.packed)
+        parts = self.sh.all_gather(self.packed).view(self.sh.world, self.K, self.D + 1)
+        self.hb.mu2_merge_load_shard(parts, self.sh.row0, self.sh.row1, self.runner.shard.data, self.m_rows, self.v_rows,
+                                     self.ratio)
+
+    def train_pass(self, N: int):
+        perm = torch.randperm(N, device=self.dev, generator=self.gen)
+        total = torch.zeros((), device=self.dev)
+        nb = 0
+        for s in range(0, N, self.B):
+            sel = perm[s:s + self.B]
+            a, b, skip = rank_slice(sel.shape[0], self.sh.world, self.sh.rank)
+            self.skipped += skip
+            if b == a:
+                continue
+            sel = sel[a:b]
+            ids, li = self.seg_ids[sel], self.local_idx[sel]
+            _, x, nsegs = self.pool.batch(ids)
+            loss, _ = self.step_fn(li, x, nsegs)
+            total += loss
+            nb += 1
+        return total, nb
+
+    def run_block(self, block_seqs, j: int = 0, n_blocks: int = 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        skipped0 = self.skipped
+        ev[0].record()
+        N = self.select(block_seqs)
+        ev[1].record()
+        self.estimate(N)
+        ev[2].record()
+        self.load()
+        ev[3].record()
+        total, nb = self.train_pass(N)
+        ev[3].synchronize()
+        self.times = {"select_ms": ev[0].elapsed_time(ev[1]), "estimate_ms": ev[1].elapsed_time(ev[2]),
+                      "merge_ms": ev[2].elapsed_time(ev[3])}
+        if self.log is not None:
+            skip = self.skipped - skipped0
+            self.log("hs block %d/%d: %d seqs, %d segments, estimate %.2f ms, merge %.2f ms%s" % (
+                j + 1, n_blocks, self.K, N, self.times["estimate_ms"], self.times["merge_ms"],
+                (", %d segments of the last batch skipped (not a multiple of %d ranks)" % (skip, self.sh.world)) if skip else ""))
+        return total, nb, N - (self.skipped - skipped0)
 
 
 def hs_clamp(K: int, seq_counts, log: Optional[Callable] = print) -> int:

@@ -133,6 +133,8 @@ SIGNATURES = {
     "fhvae_hs_select": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "fhvae_mu2_accumulate_sorted": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "fhvae_mu2_load_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
+    "fhvae_hs_pack_partials": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "fhvae_mu2_merge_load_shard": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1402,6 +1404,38 @@ def mu2_load_table(zsum, count, table, m_rows, v_rows, ratio):
     with _Timed("fhvae_mu2_load_table"):
         _check(lib.fhvae_mu2_load_table(_p(zsum), _p(count), _p(table), _p(m_rows), _p(v_rows), K, D, float(ratio), _stream()),
                "fhvae_mu2_load_table")
+
+
+def hs_pack_partials(zsum, count, out):
+    """out (K, D+1) = [zsum | count], then zsum = count = 0: one launch (the buffer one all-gather moves across ranks)."""
+    _need_gpu(zsum, count, out)
+    K, D = zsum.shape
+    for t, shape in ((zsum, (K, D)), (count, (K,)), (out, (K, D + 1))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError("hs_pack_partials: zsum (K, D), count (K,) and out (K, D+1) must be contiguous f32")
+    lib = load_library()
+    with _Timed("fhvae_hs_pack_partials"):
+        _check(lib.fhvae_hs_pack_partials(_p(zsum), _p(count), _p(out), K, D, _stream()), "fhvae_hs_pack_partials")
+
+
+def mu2_merge_load_shard(parts, row0, row1, shard, m_rows, v_rows, ratio):
+    """parts (W, K, D+1): the ranks' packed partials in rank order.  For rows [row0, row1): the partials summed in rank order,
+    shard = sum / (count + ratio) (0 where count is 0), m_rows = v_rows = 0.  One launch; none for an empty shard."""
+    _need_gpu(parts)
+    W, K, D1 = parts.shape
+    D, n = D1 - 1, row1 - row0
+    if parts.dtype != torch.float32 or not parts.is_contiguous() or not 0 <= row0 <= row1 <= K:
+        raise RuntimeError("mu2_merge_load_shard: parts must be contiguous f32 (W, K, D+1) and 0 <= row0 <= row1 <= K")
+    for t in (shard, m_rows, v_rows):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n * D:
+            raise RuntimeError("mu2_merge_load_shard: shard / m_rows / v_rows must be contiguous f32 of %d x %d" % (n, D))
+    if n == 0:
+        return
+    _need_gpu(shard, m_rows, v_rows)
+    lib = load_library()
+    with _Timed("fhvae_mu2_merge_load_shard"):
+        _check(lib.fhvae_mu2_merge_load_shard(_p(parts), W, K, row0, row1, _p(shard), _p(m_rows), _p(v_rows), D, float(ratio),
+                                              _stream()), "fhvae_mu2_merge_load_shard")
 
 
 class SortedMu2Estimator:

@@ -12,6 +12,7 @@ feature scp files are SURVEY 8f "next" #1.
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 import time
 from typing import Optional
@@ -98,6 +99,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--paper-objective", action="store_true", help="(accepted for compatibility: this is the default now)")
     p.add_argument("--continue-from", default=None,                 # train_model.py:192-197
                    help="checkpoint file (utils.save_checkpoint layout) to resume from: model, mu2 table, Adam moments and step")
+    p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
+                   help="process-group backend of the distributed mode (on when torchrun sets WORLD_SIZE > 1): nccl = RCCL, "
+                        "the product transport; gloo stages device tensors through the host (tests: several ranks on one GPU)")
     p.add_argument("--check-interval", type=int, default=100,
                    help="batches between reads of the device-side divergence / recurrence-status words (each read is a host "
                         "sync; they are always read at the end of an epoch and before a checkpoint)")
@@ -112,12 +116,52 @@ def synthetic_split(n, T, F, S, seed):
     return x, idx, nsegs
 
 
+def dist_arg_error(args, world: int) -> Optional[str]:
+    """Why the arguments cannot run on `world` ranks (None: they can)."""
+    if args.training_batch_size % world:
+        return ("--training-batch-size %d is not a multiple of the %d ranks: every global batch is cut into %d equal slices "
+                "(the runner's 1/W gradient scale and its all-gather need equal local batches)" % (args.training_batch_size, world, world))
+    if args.hip_graph and args.dist_backend != "nccl":
+        return ("--hip-graph in distributed mode needs --dist-backend nccl: the captured step holds the runner's collectives, "
+                "and gloo's (staged through the host) cannot be captured")
+    return None
+
+
+def _quiet(*_a, **_k):
+    pass
+
+
 def main(argv=None) -> int:
+    """One process per GPU under torchrun when WORLD_SIZE > 1 (the distributed mode: dist_shard.DistributedFHVAE, the row-sharded
+    table, rank 0 prints and writes); otherwise the single-GPU loop on cuda:0."""
     args = build_parser().parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        err = dist_arg_error(args, world)
+        if err is not None:
+            print(err, file=sys.stderr)
+            return 1
     if args.device != "gpu" or not torch.cuda.is_available():
         print("this training path runs on a MI355X only (no CPU fallback)", file=sys.stderr)
         return 1
-    device = torch.device("cuda:0")
+    if world <= 1:
+        return _train(args, torch.device("cuda:0"), 1, 0)
+    import torch.distributed as dist
+
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    own = not dist.is_initialized()
+    if own:
+        dist.init_process_group(args.dist_backend, **({"device_id": device} if args.dist_backend == "nccl" else {}))
+    try:
+        return _train(args, device, dist.get_world_size(), dist.get_rank())
+    finally:
+        if own:
+            dist.destroy_process_group()
+
+
+def _train(args, device, world: int, rank: int) -> int:
+    say = print if rank == 0 else _quiet  # rank 0 prints (and writes) for all ranks
     from fhvae import FHVAE
     from simple_fhvae import SimpleFHVAE
 
@@ -153,12 +197,12 @@ def main(argv=None) -> int:
         else:
             syn_tr = synthetic_split(args.train_segments, T, F, S, args.seed + 1)
             counts = np.bincount(syn_tr[1].numpy(), minlength=S)
-        hs_K = hs_clamp(args.num_hierarchical_sequences, counts)
+        hs_K = hs_clamp(args.num_hierarchical_sequences, counts, log=say)
     S_model = hs_K if hs_K is not None else S  # the table's rows: forward()'s num_seqs
     kw = dict(num_seqs=S_model, reference_compat=bool(args.reference_objective))
     if args.reference_objective:
-        print("WARNING: --reference-objective trains the reference's literal loss (+CE, detached decoder); "
-              "throughput/ELBO figures of this build use the default objective", file=sys.stderr)
+        say("WARNING: --reference-objective trains the reference's literal loss (+CE, detached decoder); "
+            "throughput/ELBO figures of this build use the default objective", file=sys.stderr)
     if args.model_type == "fhvae":
         model = FHVAE(input_size, args.z1_hus, args.z2_hus, args.z1_dim, args.z2_dim, args.x_hus, seg_len=T,
                       compute_dtype=args.compute_dtype, **kw)
@@ -167,12 +211,32 @@ def main(argv=None) -> int:
     model.to(device)
     from hip_optim import FusedAdam
 
-    optimizer = FusedAdam(model.parameters(), lr=args.learning_rate, betas=(args.beta_one, args.beta_two))
+    runner = optimizer = None
+    if world > 1:
+        # data parallel over the batch, the table's rows sharded over the ranks; opt_nets / opt_table replace the one FusedAdam
+        from dist_shard import DistributedFHVAE
+
+        runner = DistributedFHVAE(model, lr=args.learning_rate, betas=(args.beta_one, args.beta_two))
+    else:
+        optimizer = FusedAdam(model.parameters(), lr=args.learning_rate, betas=(args.beta_one, args.beta_two))
     import hip_binding as hb
 
     start_epoch = 0
     best_epoch, best_val_lb = 0, -np.inf
-    if args.continue_from:
+    if args.continue_from and runner is not None:
+        # a checkpoint of this build (one GPU or distributed: the same layout) -> every rank keeps its own rows
+        ck = torch.load(args.continue_from, map_location="cpu", weights_only=False)
+        ck_table = ck["state_dict"].get("mu2_table")
+        if ck_table is None or ck_table.shape[0] != S_model:
+            raise ValueError("--continue-from in distributed mode needs a checkpoint of this build with a %d-row mu2 table; it has %s"
+                             % (S_model, tuple(ck_table.shape) if ck_table is not None else "none"))
+        runner.load_state_dict(ck)
+        start_epoch = int(ck["epoch"]) + 1
+        if ck.get("best_val_lb") is not None:
+            best_val_lb = float(ck["best_val_lb"])
+        best_epoch = int(ck.get("best_epoch", start_epoch - 1))
+        say(f"resumed from {args.continue_from}: starting at epoch {start_epoch}")
+    elif args.continue_from:
         # resume (train_model.py:303-322 -> utils.load_checkpoint_file): weights + table into the live model, Adam moments and
         # step count into the arenas; the reference's own branch never rebuilds the optimizer (dead path)
         from utils import load_checkpoint_file
@@ -218,7 +282,7 @@ def main(argv=None) -> int:
             best_val_lb = float(ck_best)
         ck_raw = torch.load(args.continue_from, map_location="cpu", weights_only=False)
         best_epoch = int(ck_raw.get("best_epoch", start_epoch - 1))  # the patience window continues where it stood
-        print(f"resumed from {args.continue_from}: starting at epoch {start_epoch}")
+        say(f"resumed from {args.continue_from}: starting at epoch {start_epoch}")
 
     if real:
         def train_batches():
@@ -245,26 +309,54 @@ def main(argv=None) -> int:
 
         n_train = xtr.shape[0]
 
+    from dist_shard import rank_slice
+
+    dist_counts = {"skipped": 0, "trained": 0}  # per epoch: segments of ragged last batches nobody trained, segments trained
+    global_batches = train_batches
+    if world > 1:
+        # every rank draws the same permutation (a generator of its own, seeded with --seed) and steps on its slice of each
+        # global batch; only that slice's features are gathered
+        if real:
+            order_dev, take = device, tr_pool.batch
+        else:
+            order_dev, take = torch.device("cpu"), (lambda sel: (itr[sel], xtr[sel.to(device)], ntr[sel]))
+        perm_gen = torch.Generator(device=order_dev)
+        perm_gen.manual_seed(args.seed)
+
+        def train_batches():
+            order = torch.randperm(n_train, device=order_dev, generator=perm_gen)
+            for s0 in range(0, n_train, args.training_batch_size):
+                sel = order[s0:s0 + args.training_batch_size]
+                a, b, skip = rank_slice(sel.shape[0], world, rank)
+                dist_counts["skipped"] += skip
+                dist_counts["trained"] += (b - a) * world
+                if b > a:
+                    yield take(sel[a:b])
+
     if args.sample_hierarchical and hs_K is None:
         # closed-form mu2 from the current encoder (train_model.py:424-436); unlike the reference the result is USED:
         # it initialises the persistent table
         from utils import estimate_mu2_dict
 
-        mu2_dict = estimate_mu2_dict(model, train_batches(), S)
+        mu2_dict = estimate_mu2_dict(model, global_batches(), S)
         with torch.no_grad():
             for y, v in mu2_dict.items():
-                model.mu2_table[y] = v
-        print(f"hierarchical: mu2 re-estimated for {len(mu2_dict)} of {S} sequences")
+                if runner is None:
+                    model.mu2_table[y] = v
+                elif runner.sh.row0 <= y < runner.sh.row1:  # every rank has the whole estimate and keeps its own rows
+                    runner.shard[y - runner.sh.row0] = v
+        say(f"hierarchical: mu2 re-estimated for {len(mu2_dict)} of {S} sequences")
     if args.exp_dir:
-        import os
-
-        os.makedirs(args.exp_dir, exist_ok=True)
         from utils import save_args, save_checkpoint
 
-        save_args(args.exp_dir, args)  # train_model.py:422
+        if rank == 0:
+            os.makedirs(args.exp_dir, exist_ok=True)
+            save_args(args.exp_dir, args)  # train_model.py:422
 
     def train_step(idxs, features, nsegs):
         """One iteration of the reference loop body, train_model.py:446-454."""
+        if runner is not None:
+            return runner.train_step(features, idxs, nsegs, alpha=args.alpha_dis)
         optimizer.zero_grad()
         lower_bound, discrim_loss, log_px_z, neg_kld_z1, neg_kld_z2, log_pmu2 = model(features, idxs, S_model, nsegs)
         loss = loss_function(lower_bound, discrim_loss, args.alpha_dis)
@@ -276,7 +368,7 @@ def main(argv=None) -> int:
 
     def graph_step(idxs, features, nsegs):
         nonlocal graph
-        bsz = args.training_batch_size
+        bsz = args.training_batch_size // world  # (the local batch)
         idxs = torch.as_tensor(idxs).to(device=device, dtype=torch.int64)
         nsegs = torch.as_tensor(nsegs).to(device=device, dtype=torch.int64)
         if not args.hip_graph or features.shape[0] != bsz:
@@ -285,7 +377,9 @@ def main(argv=None) -> int:
             st_i, st_x, st_n = idxs.clone(), features.clone(), nsegs.clone()
             # the warm-up steps and the capture must not train: parameters, Adam moments and the step count are put back
             # afterwards, so this batch gets exactly one update (the first replay) like every other batch
-            keep = [t.clone() for t in (optimizer.p_arena.flat, optimizer.m, optimizer.v, optimizer.step_dev)]
+            arenas = [t for o in ([optimizer] if runner is None else [runner.opt_nets, runner.opt_table])
+                      for t in (o.p_arena.flat, o.m, o.v, o.step_dev)]
+            keep = [t.clone() for t in arenas]
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -297,7 +391,7 @@ def main(argv=None) -> int:
             with torch.cuda.graph(g):
                 outs = train_step(st_i, st_x, st_n)
             graph = (g, (st_i, st_x, st_n), outs)
-            for t, k in zip((optimizer.p_arena.flat, optimizer.m, optimizer.v, optimizer.step_dev), keep):
+            for t, k in zip(arenas, keep):
                 t.copy_(k)
             # capture only RECORDS the kernels: `outs` is uninitialised graph-pool memory until the first replay
             g.replay()
@@ -312,13 +406,22 @@ def main(argv=None) -> int:
     def healthy() -> Optional[int]:
         """One host sync: the sticky device words.  Divergence = NaN lower bound in ANY batch since the start
         (fhvae_loss_fwd's nan_flag; the reference tests every batch on the host, train_model.py:464-466).  Recurrence status
-        = a persistent bf16 LSTM launch gave up (all 256 CUs were not co-resident): everything computed since is invalid."""
+        = a persistent bf16 LSTM launch gave up (all 256 CUs were not co-resident): everything computed since is invalid.
+        Distributed: the worst code over the ranks, so that every rank stops together."""
+        if runner is not None:
+            code = runner.check_status()
+            if code == 2:
+                say("Training diverged")
+            elif code == 3:
+                say("a persistent LSTM recurrence launch gave up on some rank: results since are invalid; rerun with "
+                    "FHVAE_NO_CLUSTER=1 if the GPU is shared", file=sys.stderr)
+            return code or None
         if hb.diverged(device):
-            print("Training diverged")
+            say("Training diverged")
             return 2  # sys.exit(2), train_model.py:464-466
         st = hb.lstm_sync_status()
         if st != 0:
-            print("a persistent LSTM recurrence launch gave up (status %d): results since are invalid; rerun with "
+            say("a persistent LSTM recurrence launch gave up (status %d): results since are invalid; rerun with "
                   "FHVAE_NO_CLUSTER=1 if the GPU is shared" % st, file=sys.stderr)
             return 3
         return None
@@ -328,28 +431,56 @@ def main(argv=None) -> int:
         # every block: select its segments, estimate + load its K table rows, one shuffled pass (hierarchical.py); dev sequences
         # have no table rows: their mu2 is estimated the same way and injected (step 4 of the algorithm)
         from datasets import SyntheticSegmentPool
-        from hierarchical import HierarchicalTrainer, estimate_pool_mu2
+        from hierarchical import DistributedHierarchicalTrainer, HierarchicalTrainer, estimate_pool_mu2
 
         if real:
             hs_tr, hs_dv = tr_pool, dv_pool
         else:
             hs_tr = SyntheticSegmentPool(xtr, itr, ntr, S, device)
             hs_dv = SyntheticSegmentPool(xdv, idv, ndv, S, device)
-        trainer = HierarchicalTrainer(model, optimizer, hs_tr, hs_K, args.training_batch_size, graph_step, seed=args.seed)
+        if runner is None:
+            trainer = HierarchicalTrainer(model, optimizer, hs_tr, hs_K, args.training_batch_size, graph_step, seed=args.seed)
+        else:
+            trainer = DistributedHierarchicalTrainer(runner, hs_tr, hs_K, args.training_batch_size, graph_step, seed=args.seed,
+                                                     log=say)
 
         def dev_lower_bounds():
-            dev_mu2 = estimate_pool_mu2(model, hs_dv)
-            return [model(features, idxs, hs_dv.num_seqs, nsegs, mu2_table=dev_mu2)[0]
-                    for idxs, features, nsegs in hs_dv.epoch(args.dev_batch_size, shuffle=False)]
+            dev_mu2 = estimate_pool_mu2(model, hs_dv)  # (the same on every rank)
+            fwd = lambda idxs, features, nsegs: model(features, idxs, hs_dv.num_seqs, nsegs, mu2_table=dev_mu2)[0]  # noqa: E731
+            batches = lambda: hs_dv.epoch(args.dev_batch_size, shuffle=False)  # noqa: E731
+            if runner is not None:
+                return dist_dev_mean(batches, fwd)
+            return [fwd(idxs, features, nsegs) for idxs, features, nsegs in batches()]
     else:
         def dev_lower_bounds():
+            if runner is not None:
+                return dist_dev_mean(dev_batches, lambda idxs, features, nsegs: model(features, idxs, S, nsegs)[0])
             return [model(features, idxs, S, nsegs)[0] for idxs, features, nsegs in dev_batches()]
+
+    def dist_dev_mean(batches, fwd):
+        """The dev mean over W ranks, every segment counted once: each global dev batch is padded to a multiple of W (the
+        padding repeats its first segment; the sharded forward needs equal local sizes), rank r takes the r-th slice, the
+        padding is masked out of the sums, and the (sum, count) pair is all-reduced.  Returns [mean] (a (1,) tensor)."""
+        acc = torch.zeros(2, device=device, dtype=torch.float64)
+        for idxs, features, nsegs in batches():
+            n = features.shape[0]
+            per = -(-n // world)
+            pos = torch.arange(rank * per, (rank + 1) * per)
+            valid = pos < n
+            pos = torch.where(valid, pos, torch.zeros_like(pos))
+            pick = lambda t: t[pos.to(t.device)]  # noqa: E731
+            lb = fwd(pick(torch.as_tensor(idxs)), pick(features), pick(torch.as_tensor(nsegs)))
+            acc[0] += (lb.double() * valid.to(device)).sum()
+            acc[1] += int(valid.sum())
+        runner.sh.all_reduce_(acc)
+        return [(acc[0] / acc[1]).float().reshape(1)]
 
     for epoch in range(start_epoch, args.epochs):
         model.train()
         t0 = time.time()
         train_loss = torch.zeros((), device=device)
         nb = 0
+        dist_counts.update(skipped=0, trained=0)
         if trainer is not None:
             checked = [0]
 
@@ -375,22 +506,37 @@ def main(argv=None) -> int:
         if rc is not None:
             return rc
         dt = time.time() - t0
-        print(f"====> Train set average loss: {train_loss.item() / nb:.4f}  ({n_train / dt:.0f} segments/s)")
+        n_seg = n_train
+        if runner is not None:
+            runner.sh.all_reduce_(train_loss)  # the global loss: the mean of the ranks' (equal-sized) local losses
+            train_loss = train_loss / world
+            if trainer is None:
+                n_seg = dist_counts["trained"]
+                if dist_counts["skipped"]:
+                    say("dist: %d segments of the last ragged batch skipped (not a multiple of %d ranks)"
+                        % (dist_counts["skipped"], world))
+            elif trainer.skipped:
+                say("dist: %d segments of ragged last batches skipped this epoch (not a multiple of %d ranks)"
+                    % (trainer.skipped, world))
+                trainer.skipped = 0
+        say(f"====> Train set average loss: {train_loss.item() / nb:.4f}  ({n_seg / dt:.0f} segments/s)")
         model.eval()
         with torch.no_grad():
             val_lower_bound = torch.cat(dev_lower_bounds())
-        print(f"====> Validation set lower bound: {val_lower_bound.mean().item():.4f} "
+        say(f"====> Validation set lower bound: {val_lower_bound.mean().item():.4f} "
               f"({val_lower_bound.mean().item() / T:.4f} nats/frame)")
         if check_best(val_lower_bound, best_val_lb):
             best_epoch, best_val_lb = epoch, val_lower_bound.mean().item()
         if args.exp_dir:
-            save_checkpoint(model, optimizer, None, {"val_lower_bound": val_lower_bound.mean().item()}, "run", epoch, best_epoch,
-                            val_lower_bound.mean().item(), best_val_lb, args.exp_dir, input_size=input_size,
-                            hierarchical_sequences=hs_K)
+            full = runner.state_dict() if runner is not None else None  # (collective: every rank takes part, rank 0 writes)
+            if rank == 0:
+                save_checkpoint(model, optimizer, None, {"val_lower_bound": val_lower_bound.mean().item()}, "run", epoch,
+                                best_epoch, val_lower_bound.mean().item(), best_val_lb, args.exp_dir, input_size=input_size,
+                                hierarchical_sequences=hs_K, state=full)
         if check_terminate(epoch, best_epoch, args.patience, args.epochs):
-            print("Training terminated!")
+            say("Training terminated!")
             break
-    print("Training complete!")
+    say("Training complete!")
     return 0
 
 

@@ -53,12 +53,13 @@ def load_args(exp_dir):
 
 def save_checkpoint(model, optimizer, summary_list, values_dict, run_info: str, epoch: int, best_epoch: int,
                     val_lower_bound: float, best_val_lb: float, checkpoint_dir: str, input_size=None,
-                    hierarchical_sequences=None) -> None:
+                    hierarchical_sequences=None, state=None) -> None:
     """Same dict layout and file names as utils.py:116-152.  `model_params` additionally carries the input size as
     its first element (the reference stores 5 values but both constructors take 6, utils.py:75,135-141); the mu2
     table travels inside `state_dict` (key `mu2_table`).  `hierarchical_sequences` (K of a hierarchical-sampling run: the
     table then holds the last block's K sequences, not one row per corpus sequence) adds a top-level key of that name; without
-    it the layout is unchanged."""
+    it the layout is unchanged.  `state` (dist_shard.DistributedFHVAE.state_dict(): the gathered table and one Adam state in
+    the single-GPU layout) replaces the model's state_dict and the optimizer's; the file is the same as one GPU's."""
     if input_size is None:
         input_size = getattr(model, "seg_len", 1) * getattr(model, "n_feat", 0) or model.dec_gauss_layer.mulayer.out_features
     checkpoint = {
@@ -67,8 +68,8 @@ def save_checkpoint(model, optimizer, summary_list, values_dict, run_info: str, 
         "epoch": epoch,
         "model_type": model.model,
         "model_params": (input_size, model.z1_hus, model.z2_hus, model.z1_dim, model.z2_dim, model.x_hus),
-        "optimizer": optimizer.state_dict() if optimizer is not None else None,
-        "state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+        "optimizer": state["optimizer"] if state is not None else (optimizer.state_dict() if optimizer is not None else None),
+        "state_dict": {k: v.detach().cpu().clone() for k, v in (state["state_dict"] if state is not None else model.state_dict()).items()},
         "summary_vals": summary_list,
         "values": values_dict,
         # one key beyond the reference's layout: keyword-only constructor arguments of this build
