@@ -483,6 +483,36 @@ int fhvae_hs_pack_partials(float* zsum, float* count, float* out, int64_t K, int
 int fhvae_mu2_merge_load_shard(const float* parts, int64_t W, int64_t K, int64_t row0, int64_t row1, float* shard,
                                float* m_rows, float* v_rows, int64_t D, float ratio, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Features from audio (csrc/feats.hip): the reference's prepare_numpy_data.generate_feat (prepare_numpy_data.py:14-46) on
+ * AudioUtils.stft / rstft / to_melspec (utils.py:155-272, librosa 0.8.0), for a batch of U utterances in one launch.
+ *   wave (n_samples) f32: the utterances' samples, concatenated; wave_ptr (U+1) int64 their offsets.
+ *   frame_ptr (U+1) int64: output row offsets, frame_ptr[u+1] - frame_ptr[u] = 1 + (L + 2*(n_fft/2) - n_fft) / hop for an
+ *     utterance of L >= n_fft/2 + 1 samples; frame_ptr[0] = 0, frame_ptr[U] = n_frames.
+ *   Per frame: pre-emphasis y[t] - 0.97 y[t-1] (y[-1] = 0), centre padding of n_fft/2 by reflection (edge not repeated),
+ *   S = |DFT(window * frame)| over bins 0 .. n_fft/2; SPEC: out (n_frames, n_fft/2+1) = max(ln S, -50); FBANK: out
+ *   (n_frames, n_mels) = max(ln(S . mel^T), -20).
+ *   dft_basis (32*G, KP) f32, KP = n_fft rounded up to 16, G = ceil((n_fft/2+1) / 16): row 32g + i holds w[n] cos(2 pi n b / n_fft)
+ *     and row 32g + 16 + i holds -w[n] sin(2 pi n b / n_fft) for bin b = 16g + i, n < n_fft (zero for b > n_fft/2 and n >= n_fft).
+ *   mel_basis (16*ceil(n_mels/16), 16*G) f32 (FBANK only, NULL for SPEC): row j = mel filter j over the bins, zero-padded.
+ *   Both bases 16-byte aligned.  n_fft in [2, FHVAE_FEATS_MAX_NFFT]; FBANK also needs the tile to fit LDS (n_fft <=
+ *   FHVAE_FEATS_MAX_NFFT_FBANK) and n_mels in [1, FHVAE_FEATS_MAX_NMELS]; otherwise FHVAE_ERR_LIMIT before any launch.
+ *   Pointers that break the framing rule set FHVAE_FEATS_BAD_PTR in the int32 device word `status` (never cleared by the
+ *   library; read once per batch) and nothing is written.  Every row is a fixed-order f32 chain over its own samples: the
+ *   result of a frame does not depend on the rest of the batch (bitwise).
+ * tile_rows: frames per workgroup for (n_fft, ftype); 0 = not supported.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_FEATS_FBANK 0
+#define FHVAE_FEATS_SPEC 1
+#define FHVAE_FEATS_MAX_NFFT 2048
+#define FHVAE_FEATS_MAX_NFFT_FBANK 1664
+#define FHVAE_FEATS_MAX_NMELS 256
+#define FHVAE_FEATS_BAD_PTR 1
+int fhvae_feats_tile_rows(int64_t n_fft, int ftype);
+int fhvae_feats_fwd(const float* wave, int64_t n_samples, const int64_t* wave_ptr, const int64_t* frame_ptr, int64_t U,
+                    int64_t n_frames, const float* dft_basis, const float* mel_basis, int64_t n_fft, int64_t hop, int64_t n_mels,
+                    int ftype, float* out, int32_t* status, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -135,6 +135,8 @@ SIGNATURES = {
     "fhvae_mu2_load_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp]),
     "fhvae_hs_pack_partials": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "fhvae_mu2_merge_load_shard": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp]),
+    "fhvae_feats_tile_rows": (C.c_int, [_i64, C.c_int]),
+    "fhvae_feats_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1371,6 +1373,38 @@ def hs_select(seq_ptr, block_seqs, seg_ids, local_idx, n_out, status):
     with _Timed("fhvae_hs_select"):
         _check(lib.fhvae_hs_select(_p(seq_ptr), seq_ptr.shape[0] - 1, _p(block_seqs), block_seqs.shape[0], _p(seg_ids),
                                    _p(local_idx), _p(n_out), seg_ids.shape[0], _p(status), _stream()), "fhvae_hs_select")
+
+
+FEATS_TYPES = {"fbank": 0, "spec": 1}  # FHVAE_FEATS_FBANK / FHVAE_FEATS_SPEC
+FEATS_BAD_PTR = 1  # FHVAE_FEATS_BAD_PTR
+
+
+def feats_fwd(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, n_fft, hop, n_mels, ftype, out, status):
+    """Features of a batch of utterances in one launch (fhvae_feats_fwd): wave (n_samples,) f32 concatenated samples,
+    wave_ptr / frame_ptr (U+1,) int64, dft_basis / mel_basis in the header's padded layouts (mel_basis None for "spec"),
+    out (frame_ptr[U], n_out) f32, status (1,) int32 (FEATS_BAD_PTR when the pointers break the framing rule)."""
+    _need_gpu(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, out, status)
+    for t in (wave, dft_basis, out) + ((mel_basis,) if mel_basis is not None else ()):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("feats_fwd takes contiguous f32 samples, bases and output")
+    for t in (wave_ptr, frame_ptr):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise RuntimeError("feats_fwd takes contiguous int64 wave_ptr / frame_ptr")
+    if status.dtype != torch.int32 or wave_ptr.shape != frame_ptr.shape or out.dim() != 2:
+        raise RuntimeError("feats_fwd: status must be int32, wave_ptr / frame_ptr the same length and out 2-D")
+    n_out = n_mels if ftype == "fbank" else n_fft // 2 + 1
+    G = (n_fft // 2 + 16) // 16  # 16-bin groups
+    if tuple(dft_basis.shape) != (32 * G, (n_fft + 15) // 16 * 16):
+        raise RuntimeError("feats_fwd: dft_basis must be (%d, %d) for n_fft %d" % (32 * G, (n_fft + 15) // 16 * 16, n_fft))
+    if ftype == "fbank" and (mel_basis is None or tuple(mel_basis.shape) != ((n_mels + 15) // 16 * 16, 16 * G)):
+        raise RuntimeError("feats_fwd: mel_basis must be (%d, %d)" % ((n_mels + 15) // 16 * 16, 16 * G))
+    if out.shape[1] != n_out:
+        raise RuntimeError("feats_fwd: out has %d columns, %s needs %d" % (out.shape[1], ftype, n_out))
+    lib = load_library()
+    with _Timed("fhvae_feats_fwd"):
+        _check(lib.fhvae_feats_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
+                                   _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status),
+                                   _stream()), "fhvae_feats_fwd")
 
 
 def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):

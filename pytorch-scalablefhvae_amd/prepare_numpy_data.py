@@ -1,0 +1,132 @@
+"""prepare_numpy_data.py -- WAV files listed in wav.scp -> the numpy feature layout the loaders read (the reference's
+prepare_numpy_data.py:50-205, with the features computed on the MI355X by features.compute_features).
+
+    python pytorch-scalablefhvae_amd/prepare_numpy_data.py DATASET_DIR [--np_dir OUT] [--set_name train]
+        [--ftype {fbank,spec}] [--sr RATE] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80]
+
+For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<seq> <path>"
+lines) and writes, in wav.scp order, <OUT>/<set>/<seq>.npy (float32, (nframes, n_mels) or (nframes, n_fft // 2 + 1)) plus
+<OUT>/<set>/feats.scp ("<seq> <path.npy>") and <OUT>/<set>/len.scp ("<seq> <nframes>"); OUT is --np_dir or DATASET_DIR.
+
+Differences from the reference:
+  * wav.scp is read from DATASET_DIR even when --np_dir is given (the reference looks for it under the output directory,
+    prepare_numpy_data.py:81-92, which only works when both are the same).
+  * no resampling: every file of a set must have one sample rate, and a --sr that differs from a file's rate is an error
+    (the reference resampled with resampy through librosa.load).
+  * integer PCM WAV only (features.read_wav); sets run one after the other on the GPU instead of a pool of 3 processes.
+"""
+from __future__ import annotations
+
+import argparse
+import concurrent.futures as cf
+import os
+import sys
+import time
+from pathlib import Path
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+import numpy as np  # noqa: E402
+
+import features  # noqa: E402
+
+READ_THREADS = 8  # file reads overlapping the GPU work (of the 16 CPUs a job gets; not sized by os.cpu_count())
+CHUNK_FILES = 512  # files read ahead of the batch being computed
+
+
+def read_wav_scp(path):
+    with open(path) as fh:
+        return [tuple(line.rstrip().split(None, 1)) for line in fh if line.strip()]
+
+
+def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank", sample_rate=None, win_t=0.025, hop_t=0.010,
+                  n_mels=80, timings=None):
+    """prepare_numpy_data.py:50-129: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
+    Returns (count, (wav_path, feat_path, len_path)).  `timings` (optional dict) receives seconds spent in "read", "gpu"
+    and "write"."""
+    wav_path = Path(dataset_dir) / set_name / "wav.scp"
+    set_path = Path(output_dir if output_dir is not None else dataset_dir) / set_name
+    if not os.path.exists(wav_path):
+        raise ValueError(f"The wav.scp file at {wav_path} does not exist!")
+    os.makedirs(set_path, exist_ok=True)
+    feat_path, len_path = set_path / "feats.scp", set_path / "len.scp"
+    entries = read_wav_scp(wav_path)
+    t = {"read": 0.0, "gpu": 0.0, "write": 0.0} if timings is None else timings
+    for k in ("read", "gpu", "write"):
+        t.setdefault(k, 0.0)
+    start_time = time.time()
+    count = 0
+
+    def load(entry):
+        seq, path = entry
+        y, sr = features.read_wav(path)
+        return seq, path, y, sr
+
+    chunks = [entries[i:i + CHUNK_FILES] for i in range(0, len(entries), CHUNK_FILES)]
+    with cf.ThreadPoolExecutor(max_workers=READ_THREADS) as pool, open(feat_path, "w") as featfile, \
+            open(len_path, "w") as lenfile:
+        pending = [pool.submit(load, e) for e in chunks[0]] if chunks else []
+        for ci in range(len(chunks)):
+            t0 = time.time()
+            got = [f.result() for f in pending]
+            t["read"] += time.time() - t0
+            # the next chunk's files are read while this one is on the GPU and being written
+            pending = [pool.submit(load, e) for e in chunks[ci + 1]] if ci + 1 < len(chunks) else []
+            for seq, path, _, sr in got:
+                if sample_rate is None:
+                    sample_rate = sr
+                elif sr != sample_rate:
+                    raise ValueError(f"{path}: sample rate {sr} differs from {sample_rate} (no resampling: convert the file "
+                                     f"or pass the matching --sr)")
+            t0 = time.time()
+            feats = features.compute_features([g[2] for g in got], sample_rate, ftype, win_t, hop_t, n_mels,
+                                              names=["%s (%s)" % (g[0], g[1]) for g in got])
+            t["gpu"] += time.time() - t0
+            t0 = time.time()
+            for (seq, _, _, _), feat in zip(got, feats):
+                np_path = os.path.join(set_path, f"{seq}.npy")
+                with open(np_path, "wb") as numpyfile:
+                    np.save(numpyfile, feat)
+                featfile.write(f"{seq} {np_path}\n")  # prepare_numpy_data.py:118-119
+                lenfile.write(f"{seq} {len(feat)}\n")
+                count += 1
+                if count % 1000 == 0:
+                    print(f"{count} {set_name} files in {time.time() - start_time} seconds.")
+            t["write"] += time.time() - t0
+    print(f"Processed {count} files in {set_name} set over {time.time() - start_time} seconds.")
+    return count, (wav_path, feat_path, len_path)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("dataset_dir", type=str, help="Directory containing subdirectories with wav.scp files")
+    p.add_argument("--np_dir", type=str, default=None, help="Output directory for numpy matrices")
+    p.add_argument("--dataset", type=str, default="librispeech", choices=["librispeech", "timit"], help="Dataset name")
+    p.add_argument("--set_name", type=str, default=None, help="Set {train, dev, test} to operate on, Leave blank for all three")
+    p.add_argument("--ftype", type=str, default="fbank", choices=["fbank", "spec"], help="Feature type to compute")
+    p.add_argument("--sr", type=int, default=None,
+                   help="Sample rate every file must have (no resampling); default: the rate of the first file")
+    p.add_argument("--win_t", type=float, default=0.025, help="Window size in seconds")
+    p.add_argument("--hop_t", type=float, default=0.010, help="Frame spacing in seconds")
+    p.add_argument("--n_mels", type=int, default=80, help="Number of filter banks if choosing fbank")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    print(args)
+    sets = ["train", "dev", "test"] if args.set_name is None else [args.set_name]
+    t0 = time.time()
+    total = 0
+    for s in sets:
+        total += prepare_numpy(args.dataset, s, args.dataset_dir, args.np_dir, args.ftype, args.sr, args.win_t, args.hop_t,
+                               args.n_mels)[0]
+    if len(sets) > 1:
+        print(f"Processed {total} files in {time.time() - t0} seconds.")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,6 +1,7 @@
 """utils.py -- the parts of the reference's utils.py that touch the hot path's state (utils.py:14-152):
-checkpoint layout, args pickle, and the closed-form mu2 estimate (run naming, utils.py:20-42, is CLI plumbing: not built).  AudioUtils (librosa wrappers,
-utils.py:155-300) is offline feature extraction and out of scope.
+checkpoint layout, args pickle, and the closed-form mu2 estimate (run naming, utils.py:20-42, is CLI plumbing: not built).  AudioUtils's
+feature extraction (stft / rstft / to_melspec, utils.py:155-272) is features.py and the fhvae_feats_fwd kernel; energy_vad
+(utils.py:275-300) is not built.
 """
 from __future__ import annotations
 
