@@ -513,6 +513,45 @@ int fhvae_feats_fwd(const float* wave, int64_t n_samples, const int64_t* wave_pt
                     int64_t n_frames, const float* dft_basis, const float* mel_basis, int64_t n_fft, int64_t hop, int64_t n_mels,
                     int ftype, float* out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Waveforms from magnitude spectrograms (csrc/synth.hip): Griffin-Lim with librosa 0.8.0's griffinlim / istft semantics
+ * (window = periodic Hamming, win_length = n_fft, center = True), for a batch of U utterances per launch.  The framing is
+ * the one of fhvae_feats_fwd read backwards: an utterance of F >= 2 frames has hop * (F - 1) samples.
+ *   wave_ptr (U+1) int64 sample offsets, frame_ptr (U+1) int64 frame offsets; wave_ptr[0] = frame_ptr[0] = 0, wave_ptr[U] =
+ *     n_samples, frame_ptr[U] = n_frames, wave_ptr[u+1] - wave_ptr[u] = hop * (frame_ptr[u+1] - frame_ptr[u] - 1).
+ *   Complex arrays are (n_frames, n_fft/2+1, 2) f32 (re, im), 8-byte aligned.
+ * istft: wave_out = overlap-add of window * irfft(spec row) at f * hop, divided by the sum of the squared window over the
+ *   covering frames where that exceeds tiny(f32), the n_fft/2 centre padding trimmed.  Two launches: the inverse DFT of every
+ *   frame into frames_ws (n_frames, KP) f32 (KP = n_fft rounded up to 16; 16-byte aligned), then a gather that sums the
+ *   covering frames of every sample in increasing frame order (no atomics).
+ *   synth_basis (KP, K2P) f32, K2P = 2 * (n_fft/2+1) rounded up to 16: row n holds at column 2b
+ *     window[n] * c_b / n_fft * cos(2 pi b n / n_fft) and at 2b+1 -window[n] * c_b / n_fft * sin(2 pi b n / n_fft), c_b = 1
+ *     for bin 0 and (even n_fft) bin n_fft/2, else 2; zero for n >= n_fft and columns >= 2 * (n_fft/2+1).  16-byte aligned.
+ *   win_sq (n_fft) f32: the squared window.
+ * project: frames of `wave` (centre padding by reflection, numpy "reflect" for any length; frame f reads padded positions
+ *   f * hop .. f * hop + n_fft - 1; no pre-emphasis), rebuilt = their DFT (dft_basis as for fhvae_feats_fwd),
+ *   a = rebuilt - coef * tprev, next = mag * a / (|a| + 1e-16).  mag (n_frames, n_fft/2+1) f32; tprev NULL = zero; rebuilt
+ *   NULL = not stored.  For Griffin-Lim coef = momentum / (1 + momentum).
+ * deemph: out[t] = wave[t] + coef * out[t-1] within every utterance (the inverse of the features' pre-emphasis), |coef| < 1;
+ *   a blocked scan that restarts W samples before each 256-sample block of the utterance, |coef|^W < 2^-30 (W > 65536:
+ *   FHVAE_ERR_LIMIT).  coef = 0 copies.  Only wave_ptr is needed.
+ * n_fft in [2, FHVAE_FEATS_MAX_NFFT], 1 <= hop <= n_fft, otherwise FHVAE_ERR_SHAPE / FHVAE_ERR_LIMIT before any launch.
+ * Pointers that break the rule above set FHVAE_SYNTH_BAD_PTR in the int32 device word `status` (never cleared by the
+ * library) and nothing is written.  Every output is a fixed-order f32 chain over its own utterance: bitwise independent of
+ * the batch.
+ * tile_rows: frames per workgroup of the two MFMA kernels for n_fft; 0 = not supported.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_SYNTH_BAD_PTR 1
+int fhvae_synth_tile_rows(int64_t n_fft);
+int fhvae_synth_istft(const float* spec, int64_t n_frames, const int64_t* wave_ptr, const int64_t* frame_ptr, int64_t U,
+                      int64_t n_samples, const float* synth_basis, const float* win_sq, int64_t n_fft, int64_t hop,
+                      float* frames_ws, float* wave_out, int32_t* status, void* stream);
+int fhvae_synth_project(const float* wave, int64_t n_samples, const int64_t* wave_ptr, const int64_t* frame_ptr, int64_t U,
+                        int64_t n_frames, const float* dft_basis, const float* mag, const float* tprev, float coef, int64_t n_fft,
+                        int64_t hop, float* rebuilt, float* next, int32_t* status, void* stream);
+int fhvae_synth_deemph(const float* wave, const int64_t* wave_ptr, int64_t U, int64_t n_samples, float coef, float* out,
+                       int32_t* status, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -9,6 +9,12 @@ without the plotting: load a checkpoint, then write as .npy files under --out
   summary.json                the mean lower bound per frame over the data (forward() with zero noise: the ELBO at the
                               posterior means), segment / sequence counts
 
+With --wav-out DIR --wav-seqs N (needs --feat-scp data of "spec" features, n_fft // 2 + 1 columns for --sr / --win-t) the first N
+sequences are also made audible: every segment of a sequence is reconstructed (and, with --convert-to Y, decoded with Y's
+mu2), the decoder means are un-normalised, put back together (utils.overlap_mean) and turned into a waveform by Griffin-Lim
+(features.synthesize): DIR/<seq>_orig.wav (the input features through the same vocoder: the ceiling of what it can do),
+<seq>_recon.wav and <seq>_to_<Y>.wav, listed under "wavs" in summary.json.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -41,11 +47,65 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch-size", type=int, default=2048)
     p.add_argument("--convert-to", type=int, default=None, help="sequence index whose mu2 replaces z2 of the reconstructed segments")
     p.add_argument("--max-recon", type=int, default=16)
+    p.add_argument("--wav-out", default=None, help="directory for the synthesized WAV files (needs --feat-scp spec features)")
+    p.add_argument("--wav-seqs", type=int, default=0, help="synthesize the first N sequences of the data")
+    p.add_argument("--sr", type=int, default=16000, help="sample rate the features were taken at")
+    p.add_argument("--win-t", type=float, default=0.025)
+    p.add_argument("--hop-t", type=float, default=0.010)
+    p.add_argument("--gl-iters", type=int, default=32, help="Griffin-Lim rounds")
+    p.add_argument("--gl-seed", type=int, default=0, help="seed of the initial phases")
     return p
+
+
+def write_wavs(args, model, ds, mu2, dev):
+    """--wav-out: returns the list of files written (see the module docstring)."""
+    import features
+    import utils
+
+    T, shift = ds.seg_len, ds.seg_shift
+    os.makedirs(args.wav_out, exist_ok=True)
+    names, specs = [], []
+    with torch.no_grad():
+        for si in range(min(args.wav_seqs, len(ds))):
+            seq = ds.seq_keys[si]
+            feat = np.load(ds.seq_feats[si]).astype(np.float32)
+            nseg = (len(feat) - T) // shift + 1
+            if nseg < 1:
+                continue
+            x = np.stack([ds.apply_mvn(feat[k * shift:k * shift + T]) for k in range(nseg)]).astype(np.float32)
+            xd = torch.from_numpy(x).to(dev)
+            decoded = [("recon", model.reconstruct(xd)[0])]
+            if args.convert_to is not None:
+                decoded.append(("to_%d" % args.convert_to, model.convert(xd, mu2[args.convert_to])[0]))
+            covered = min(len(feat), (nseg - 1) * shift + T)
+            names.append("%s_orig" % seq), specs.append(feat[:covered])
+            for tag, mu in decoded:
+                full, n = utils.overlap_mean(torch.from_numpy(np.asarray(ds.undo_mvn(mu.float().cpu().numpy()), dtype=np.float32)),
+                                             T, shift, len(feat))
+                assert n == covered
+                names.append("%s_%s" % (seq, tag)), specs.append(full.numpy())
+    waves = features.synthesize(specs, args.sr, args.win_t, args.hop_t, n_iter=args.gl_iters, seed=args.gl_seed, device=dev,
+                                names=names)
+    files = []
+    for name, y in zip(names, waves):
+        features.write_wav(os.path.join(args.wav_out, name + ".wav"), y, args.sr)
+        files.append(name + ".wav")
+    return files
 
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    if args.wav_out is not None:
+        import features
+
+        if args.feat_scp is None:
+            print("--wav-out needs --feat-scp data (\"spec\" features)", file=sys.stderr)
+            return 1
+        try:
+            n_fft, _ = features.check_synth_params(args.sr, args.win_t, args.hop_t, args.gl_iters, 0.99, 0.97)
+        except ValueError as e:
+            print("--wav-out: %s" % e, file=sys.stderr)
+            return 1
     if not torch.cuda.is_available():
         print("evaluation runs on a MI355X only (no CPU fallback)", file=sys.stderr)
         return 1
@@ -62,6 +122,12 @@ def main(argv=None) -> int:
 
         ds = NumpyDataset(args.feat_scp, args.len_scp, args.min_len if args.min_len is not None else T, args.mvn_path, T,
                           args.seg_shift, False)
+        if args.wav_out is not None:
+            cols = np.load(ds.seq_feats[0], mmap_mode="r").shape[1] if len(ds) else -1
+            if cols != n_fft // 2 + 1:
+                print("--wav-out: the features have %d columns, but --sr %d / --win-t %g need \"spec\" features of n_fft // 2 + 1 = %d "
+                      "columns (mel \"fbank\" features cannot be inverted)" % (cols, args.sr, args.win_t, n_fft // 2 + 1), file=sys.stderr)
+                return 1
         pool = ResidentSegmentPool(ds, dev)
         S = len(ds)
         undo = ds.undo_mvn
@@ -119,11 +185,19 @@ def main(argv=None) -> int:
                     return 1
                 c_mu, c_lv = model.convert(xr, mu2[args.convert_to])
                 out("convert_mu.npy", undo(c_mu.cpu().numpy())), out("convert_logvar.npy", c_lv.cpu().numpy())
+    wavs = None
+    if args.wav_out is not None:
+        if args.convert_to is not None and args.convert_to not in mu2:
+            print("--convert-to %d: no segment of that sequence in the data" % args.convert_to, file=sys.stderr)
+            return 1
+        wavs = write_wavs(args, model, ds, mu2, dev)
     if hb.lstm_sync_status() != 0:
         print("a persistent recurrence launch gave up: the results are invalid", file=sys.stderr)
         return 3
     summary = {"checkpoint": os.path.basename(args.checkpoint), "segments": int(sum(z.shape[0] for z in z1s)),
                "sequences": len(mu2), "lower_bound_per_frame": sum(lbs) / max(frames, 1)}
+    if wavs is not None:
+        summary["wavs"] = wavs
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

@@ -137,6 +137,10 @@ SIGNATURES = {
     "fhvae_mu2_merge_load_shard": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp]),
     "fhvae_feats_tile_rows": (C.c_int, [_i64, C.c_int]),
     "fhvae_feats_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
+    "fhvae_synth_tile_rows": (C.c_int, [_i64]),
+    "fhvae_synth_istft": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "fhvae_synth_project": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.c_float, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "fhvae_synth_deemph": (C.c_int, [_vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1405,6 +1409,74 @@ def feats_fwd(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, n_fft, hop, n_mel
         _check(lib.fhvae_feats_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
                                    _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status),
                                    _stream()), "fhvae_feats_fwd")
+
+
+SYNTH_BAD_PTR = 1  # FHVAE_SYNTH_BAD_PTR
+
+
+def _synth_args(name, f32, ptrs, status):
+    for t in f32:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError("%s takes contiguous f32 tensors" % name)
+    for t in ptrs:
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.shape != ptrs[0].shape or t.shape[0] < 2:
+            raise RuntimeError("%s takes contiguous int64 wave_ptr / frame_ptr of one length (U + 1)" % name)
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise RuntimeError("%s: status must be one int32 word" % name)
+
+
+def synth_istft(spec, wave_ptr, frame_ptr, synth_basis, win_sq, n_fft, hop, frames_ws, wave_out, status):
+    """Inverse STFT of a batch (fhvae_synth_istft): spec (n_frames, n_fft // 2 + 1, 2) f32 complex, wave_ptr / frame_ptr
+    (U+1,) int64, synth_basis / win_sq as features.synth_basis / features.window_sq, frames_ws (n_frames, KP) f32 workspace,
+    wave_out (wave_ptr[U],) f32, status (1,) int32 (SYNTH_BAD_PTR when the pointers break hop * (frames - 1))."""
+    _need_gpu(spec, wave_ptr, frame_ptr, synth_basis, win_sq, frames_ws, wave_out, status)
+    _synth_args("synth_istft", (spec, synth_basis, win_sq, frames_ws, wave_out), (wave_ptr, frame_ptr), status)
+    n_bins, KP = n_fft // 2 + 1, (n_fft + 15) // 16 * 16
+    if spec.dim() != 3 or tuple(spec.shape[1:]) != (n_bins, 2):
+        raise RuntimeError("synth_istft: spec must be (n_frames, %d, 2) for n_fft %d" % (n_bins, n_fft))
+    if tuple(synth_basis.shape) != (KP, (2 * n_bins + 15) // 16 * 16) or tuple(win_sq.shape) != (n_fft,):
+        raise RuntimeError("synth_istft: synth_basis must be (%d, %d) and win_sq (%d,)" % (KP, (2 * n_bins + 15) // 16 * 16, n_fft))
+    if tuple(frames_ws.shape) != (spec.shape[0], KP) or wave_out.dim() != 1:
+        raise RuntimeError("synth_istft: frames_ws must be (%d, %d) and wave_out 1-D" % (spec.shape[0], KP))
+    lib = load_library()
+    with _Timed("fhvae_synth_istft"):
+        _check(lib.fhvae_synth_istft(_p(spec), spec.shape[0], _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, wave_out.numel(),
+                                     _p(synth_basis), _p(win_sq), n_fft, hop, _p(frames_ws), _p(wave_out), _p(status), _stream()),
+               "fhvae_synth_istft")
+
+
+def synth_project(wave, wave_ptr, frame_ptr, dft_basis, mag, tprev, coef, n_fft, hop, rebuilt, nxt, status):
+    """One Griffin-Lim projection (fhvae_synth_project): rebuilt = STFT(wave), a = rebuilt - coef * tprev,
+    nxt = mag * a / (|a| + 1e-16).  mag (n_frames, n_bins) f32; tprev / rebuilt / nxt (n_frames, n_bins, 2) f32 (tprev None =
+    zero, rebuilt None = not stored)."""
+    _need_gpu(wave, wave_ptr, frame_ptr, dft_basis, mag, tprev, rebuilt, nxt, status)
+    _synth_args("synth_project", (wave, dft_basis, mag, tprev, rebuilt, nxt), (wave_ptr, frame_ptr), status)
+    n_bins = n_fft // 2 + 1
+    G = (n_bins + 15) // 16
+    if tuple(dft_basis.shape) != (32 * G, (n_fft + 15) // 16 * 16):
+        raise RuntimeError("synth_project: dft_basis must be (%d, %d) for n_fft %d" % (32 * G, (n_fft + 15) // 16 * 16, n_fft))
+    if mag.dim() != 2 or mag.shape[1] != n_bins or wave.dim() != 1:
+        raise RuntimeError("synth_project: mag must be (n_frames, %d) and wave 1-D" % n_bins)
+    for t in (tprev, rebuilt, nxt):
+        if t is not None and tuple(t.shape) != (mag.shape[0], n_bins, 2):
+            raise RuntimeError("synth_project: complex arrays must be (%d, %d, 2)" % (mag.shape[0], n_bins))
+    lib = load_library()
+    with _Timed("fhvae_synth_project"):
+        _check(lib.fhvae_synth_project(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, mag.shape[0],
+                                       _p(dft_basis), _p(mag), _p(tprev), float(coef), n_fft, hop, _p(rebuilt), _p(nxt), _p(status),
+                                       _stream()), "fhvae_synth_project")
+
+
+def synth_deemph(wave, wave_ptr, coef, out, status):
+    """out[t] = wave[t] + coef * out[t-1] within every utterance (fhvae_synth_deemph); coef 0 copies."""
+    _need_gpu(wave, wave_ptr, out, status)
+    _synth_args("synth_deemph", (wave, out), (wave_ptr,), status)
+    if wave.dim() != 1 or out.shape != wave.shape:
+        raise RuntimeError("synth_deemph: wave and out must be 1-D of one length")
+    lib = load_library()
+    with _Timed("fhvae_synth_deemph"):
+        _check(lib.fhvae_synth_deemph(_p(wave), _p(wave_ptr), wave_ptr.shape[0] - 1, wave.numel(), float(coef), _p(out), _p(status),
+                                      _stream()), "fhvae_synth_deemph")
 
 
 def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):

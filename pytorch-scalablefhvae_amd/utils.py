@@ -42,6 +42,33 @@ def estimate_mu2_dict(model, loader, num_seqs):
     return {y: mu2[y] for y in seen}
 
 
+def overlap_mean(segments, seg_len, seg_shift, nframes):
+    """Put the consecutive segments of one utterance (datasets.make_segs: segment k starts at frame k * seg_shift) back
+    together: segments (nseg, seg_len, F) -> ((covered, F), covered), every frame the mean of the segments covering it.
+    A gather: each frame adds its <= ceil(seg_len / seg_shift) segments in increasing segment order and divides by their
+    number (no index_add_, no atomics), so the result is bitwise reproducible on any device.  Frames past the last segment
+    are dropped: covered = min(nframes, (nseg - 1) * seg_shift + seg_len)."""
+    segments = torch.as_tensor(segments)
+    if segments.dim() != 3 or segments.shape[1] != seg_len:
+        raise ValueError("overlap_mean: segments must be (nseg, %d, F), got %s" % (seg_len, tuple(segments.shape)))
+    if seg_shift < 1 or seg_shift > seg_len:
+        raise ValueError("overlap_mean: seg_shift = %d must be in [1, seg_len = %d] (no frame may be left uncovered)" % (seg_shift, seg_len))
+    nseg = segments.shape[0]
+    if nseg == 0:
+        return segments.new_zeros((0, segments.shape[2])), 0
+    covered = min(int(nframes), (nseg - 1) * seg_shift + seg_len)
+    t = torch.arange(covered, device=segments.device)
+    first = torch.clamp((t - seg_len + seg_shift) // seg_shift, min=0)  # ceil((t - seg_len + 1) / seg_shift)
+    last = torch.clamp(t // seg_shift, max=nseg - 1)
+    acc = torch.zeros((covered, segments.shape[2]), dtype=segments.dtype, device=segments.device)
+    for j in range(-(-seg_len // seg_shift)):
+        k = first + j
+        ok = k <= last
+        k = torch.where(ok, k, last)
+        acc = acc + torch.where(ok.unsqueeze(1), segments[k, t - k * seg_shift], torch.zeros_like(acc))
+    return acc / (last - first + 1).to(acc.dtype).unsqueeze(1), covered
+
+
 def save_args(exp_dir, args):
     with open(f"{exp_dir}/args.pkl", "wb") as f:
         pickle.dump(args, f)
