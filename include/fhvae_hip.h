@@ -552,6 +552,42 @@ int fhvae_synth_project(const float* wave, int64_t n_samples, const int64_t* wav
 int fhvae_synth_deemph(const float* wave, const int64_t* wave_ptr, int64_t U, int64_t n_samples, float coef, float* out,
                        int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sample-rate conversion (csrc/resample.hip): librosa.load's resampling (librosa 0.8.0 resample(fix=True, scale=False) on
+ * resampy 0.2.2's kaiser_best; the reference's prepare_numpy_data.py:108) for a batch of U utterances per call, as a
+ * polyphase FIR whose weights the host computes in float64 (features.ResampleBank) for the reduced ratio L / M = sr_out /
+ * sr_in.  An output row is P periods: outputs row * P * L + c, c < P * L, from the window x[row * P * M - WL + k], k < KP
+ * (samples outside the utterance count as zero).
+ *   wave_in (n_in) f32: the utterances' samples, concatenated; in_ptr (U+1) int64 their offsets (an utterance may be empty).
+ *   out_ptr (U+1) int64: output offsets, out_ptr[u+1] - out_ptr[u] = ceil(n * ratio) in double precision for an utterance
+ *     of n samples; out_ptr[0] = 0, out_ptr[U] = n_out.  Of those the first (int64)(n * ratio) are computed, the rest are 0
+ *     (resampy's length, padded by librosa).
+ *   row_ptr (U+1) int64: row offsets, row_ptr[u+1] - row_ptr[u] = ceil(outputs / (P * L)); row_ptr[0] = 0, row_ptr[U] = n_rows.
+ *   bank (NCP, KP) f32, NCP = P * L rounded up to 16, KP a multiple of 16, 16-byte aligned: row c = weights of output c of a
+ *     row over the window; zero rows past P * L.  chunks (NCP / 16, 2) int32: the range [c0, c1) of 16-sample chunks of the
+ *     window in which the 16 columns of a group have weights (only those are multiplied).
+ *   exc (n_exc) uint8, alt (alt_taps) f32, alt_wl: output p * L of an utterance with exc[p] != 0 (p < n_exc) is
+ *     sum_k alt[k] * x[p * M - 1 - alt_wl + k] instead (resampy's time register, advanced by repeated addition, fell just
+ *     below the integer time p * M; computed after the rows by a second launch).  n_exc = 0: none (exc / alt may be NULL).
+ *   Limits, otherwise FHVAE_ERR_LIMIT before any launch: L <= FHVAE_RESAMPLE_MAX_L phases; NCP * KP <=
+ *   FHVAE_RESAMPLE_MAX_BANK weights (64 MiB); 16 windows of KP + 4 floats within FHVAE_RESAMPLE_LDS_FLOATS (the
+ *   160 KiB of a CU's LDS less the 3.25 KiB of per-row bookkeeping), i.e. KP <= 2496.
+ *   Pointers that break the rules above set FHVAE_RESAMPLE_BAD_PTR in the int32 device word `status` (never cleared by the
+ *   library) and nothing is written.  Every output is a fixed-order f32 chain over its own window: bitwise independent of
+ *   the batch and of the utterance's place in it.
+ * tile_rows: rows per workgroup for a window of KP samples; 0 = not supported.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_RESAMPLE_MAX_L 4096
+#define FHVAE_RESAMPLE_MAX_BANK (1 << 24)
+#define FHVAE_RESAMPLE_LDS_FLOATS 40128
+#define FHVAE_RESAMPLE_BAD_PTR 1
+int fhvae_resample_tile_rows(int64_t KP);
+int fhvae_resample_fwd(const float* wave_in, int64_t n_in, const int64_t* in_ptr, const int64_t* out_ptr,
+                       const int64_t* row_ptr, int64_t U, int64_t n_rows, const float* bank, const int32_t* chunks, int64_t L,
+                       int64_t M, int64_t P, int64_t KP, int64_t WL, double ratio, const uint8_t* exc, int64_t n_exc,
+                       const float* alt, int64_t alt_taps, int64_t alt_wl, float* wave_out, int64_t n_out, int32_t* status,
+                       void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

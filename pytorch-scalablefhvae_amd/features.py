@@ -5,12 +5,16 @@ AudioUtils.stft / rstft / to_melspec, utils.py:155-272).  Here the arithmetic ru
 (fhvae_feats_fwd, csrc/feats.hip); this module holds the host side:
 
   read_wav            RIFF WAV, integer PCM (8-bit unsigned, 16, 24, 32-bit) -> float32 mono, scaled like soundfile
-                      (int16 / 2**15, int24 / 2**23, int32 / 2**31, (u8 - 128) / 128); channels averaged.  No resampling.
+                      (int16 / 2**15, int24 / 2**23, int32 / 2**31, (u8 - 128) / 128); channels averaged.  No resampling here.
   frame_sizes         n_fft = win_length = int(sr * win_t), hop = int(sr * hop_t) (the reference's truncation)
   dft_basis           windowed cos / -sin columns (periodic Hamming), built in float64, rounded to f32, padded for the kernel
   mel_filters         librosa.filters.mel(sr, n_fft', n_mels, fmin=0, fmax=sr/2, htk=False, norm='slaney') in float64, with
                       n_fft' = 2 * (n_bins - 1): melspectrogram(S=...) recovers n_fft from S's row count (odd n_fft differs)
   compute_features    a list of waveforms -> a list of (nframes, n_out) float32 arrays, batched into bounded launches
+  resample_filter / resample_bank / resampled_length / resample
+                      librosa.load's sample-rate conversion (resampy kaiser_best): the filter and the polyphase bank of a
+                      pair of rates on the host in float64, the conversion itself on the device (csrc/resample.hip);
+                      compute_features(..., rates=...) converts on the way to the features
 
 and the way back for "spec" features (csrc/synth.hip: fhvae_synth_istft / _project / _deemph):
 
@@ -137,6 +141,188 @@ def mel_basis(sr, n_fft, n_mels):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- resampling
+# librosa.load(path, sr) resamples with resampy 0.2.2's kaiser_best filter (librosa 0.8.0: resample(..., fix=True,
+# scale=False)).  The filter is rebuilt from its published parameters; for a rational ratio L / M = sr_out / sr_in there
+# are L distinct phases, so every weight is computed once here in float64 and the device runs a polyphase FIR
+# (csrc/resample.hip).
+RS_NUM_ZEROS = 64
+RS_NUM_TABLE = 512  # precision 9: table entries per zero crossing
+RS_ROLLOFF = 0.9475937167399596
+RS_BETA = 14.769656459379492
+RS_MAX_L = 4096  # FHVAE_RESAMPLE_MAX_L
+RS_MAX_BANK = 1 << 24  # FHVAE_RESAMPLE_MAX_BANK (f32 elements: 64 MiB)
+RS_LDS_FLOATS = 40128  # FHVAE_RESAMPLE_LDS_FLOATS: 16 window rows of KP + 4 floats must fit (a CU's 160 KiB less the row bookkeeping)
+RS_BAD_PTR = 1
+
+_RS_CACHE = {}
+
+
+def resample_filter():
+    """resampy's kaiser_best half filter, 32769 float64 entries: kaiser(2n + 1, beta)[n:] * rolloff * sinc(rolloff * x),
+    x = linspace(0, 64, n + 1), n = 512 * 64.  The Kaiser window is i0(beta * sqrt(1 - (k / n)^2)) / i0(beta)."""
+    if "filter" not in _RS_CACHE:
+        n = RS_NUM_TABLE * RS_NUM_ZEROS
+        k = np.arange(n + 1, dtype=np.float64)
+        taper = np.i0(RS_BETA * np.sqrt(np.maximum(0.0, 1.0 - (k / n) ** 2))) / np.i0(RS_BETA)
+        _RS_CACHE["filter"] = taper * RS_ROLLOFF * np.sinc(RS_ROLLOFF * np.linspace(0.0, RS_NUM_ZEROS, n + 1))
+    return _RS_CACHE["filter"]
+
+
+def resampled_length(n, sr_in, sr_out):
+    """Samples librosa returns for n input samples: ceil(n * ratio) in float64 (resampy computes int(n * ratio) of them,
+    the rest is zero padding).  Works on arrays."""
+    ratio = float(sr_out) / sr_in
+    return np.ceil(np.asarray(n, dtype=np.float64) * ratio).astype(np.int64) if np.ndim(n) else int(np.ceil(n * ratio))
+
+
+def _computed_length(n, sr_in, sr_out):
+    ratio = float(sr_out) / sr_in
+    return (np.asarray(n, dtype=np.float64) * ratio).astype(np.int64)
+
+
+class ResampleBank:
+    """The polyphase form of one (sr_in, sr_out) pair.  An output row is P periods: P * L outputs computed from the window
+    x[row * P * M - WL + k], k < KP.  bank (NCP, KP) float64 (f32 for the device in bank32): row c = p * L + r holds
+    the weights of output c of a row over that window (zero outside its taps, zero rows past P * L).  chunks (NCP / 16, 2)
+    int32: the 16-sample chunks [c0, c1) of the window that the 16 columns of a group use; the kernel multiplies only
+    those.  alt (alt_taps,) / alt_wl: the weights of an output whose time register fell just below its integer time
+    (see resample_exceptions), over x[p * M - 1 - alt_wl + k]."""
+
+    def __init__(self, sr_in, sr_out):
+        import math
+
+        g = math.gcd(int(sr_in), int(sr_out))
+        L, M = int(sr_out) // g, int(sr_in) // g
+        self.sr_in, self.sr_out, self.L, self.M = int(sr_in), int(sr_out), L, M
+        self.ratio = float(sr_out) / sr_in
+        scale = min(1.0, self.ratio)
+        self.scale = scale
+        step = int(scale * RS_NUM_TABLE)
+        if L > RS_MAX_L or step < 1:
+            raise ValueError("resampling %d -> %d Hz is not supported: the reduced ratio %d / %d has more than %d phases"
+                             % (sr_in, sr_out, L, M, RS_MAX_L))
+        self.index_step = step
+        table = resample_filter() * (scale if self.ratio < 1 else 1.0)
+        delta = np.zeros_like(table)
+        delta[:-1] = np.diff(table)
+        nwin = len(table)
+        wing = nwin // step  # the most taps a wing can have (offset 0)
+        taps = 2 * wing
+        P0 = max(-(-taps // M), -(-16 // L))
+        P = min(range(P0, 2 * P0 + 1), key=lambda p: (-(-p * L // 16) * 16 / (p * L), p))
+        WL = wing - 1
+        KP = (WL + P * M + wing + 15) // 16 * 16
+        NCP = (P * L + 15) // 16 * 16
+        if 16 * (KP + 4) > RS_LDS_FLOATS or NCP * KP > RS_MAX_BANK:
+            raise ValueError("resampling %d -> %d Hz is not supported: a window of %d samples (limit %d) or a bank of %d "
+                             "weights (limit %d) is too large" % (sr_in, sr_out, KP, RS_LDS_FLOATS // 16 - 4, NCP * KP,
+                                                                  RS_MAX_BANK))
+        self.P, self.WL, self.KP, self.NCP, self.wing = P, WL, KP, NCP, wing
+        bank = np.zeros((NCP, KP), dtype=np.float64)
+        for c in range(P * L):
+            n, k = divmod(c * M, L)
+            self._wings(bank[c], n + WL, scale * (k / L), table, delta)
+        self.bank = bank
+        self.bank32 = bank.astype(np.float32)
+        nz = (self.bank32.reshape(NCP // 16, 16, KP // 16, 16) != 0).any(axis=(1, 3))
+        ch = np.zeros((NCP // 16, 2), dtype=np.int32)
+        for gi in range(NCP // 16):
+            w = np.flatnonzero(nz[gi])
+            if len(w):
+                ch[gi] = (w[0], w[-1] + 1)
+        self.chunks = ch
+        # the phase just below an integer time: n = p * M - 1, frac -> scale from below
+        alt = np.zeros(2 * wing + 1, dtype=np.float64)
+        self._wings(alt, wing - 1, scale * (1.0 - 2.0 ** -40), table, delta)
+        w = np.flatnonzero(alt)
+        self.alt_wl = (wing - 1) - int(w[0])
+        self.alt = alt[w[0]:w[-1] + 1].copy()
+        self.alt32 = self.alt.astype(np.float32)
+        # whether an integer time is a discontinuity of resampy's filter: only when index_step was truncated
+        self.discontinuous = step != scale * RS_NUM_TABLE
+        self._exc = np.zeros(0, dtype=np.uint8)
+        self._exc_time = 0.0
+
+    def _wings(self, row, centre, frac, table, delta):
+        """Adds resampy's weights for an output at input sample `centre` (index into row) + frac / scale."""
+        step, nwin = self.index_step, len(table)
+        f = frac * RS_NUM_TABLE
+        off = int(f)
+        eta = f - off
+        i = np.arange((nwin - off) // step)
+        row[centre - i] = table[off + i * step] + eta * delta[off + i * step]
+        f = (self.scale - frac) * RS_NUM_TABLE
+        off = int(f)
+        eta = f - off
+        k = np.arange((nwin - off) // step)
+        row[centre + 1 + k] = table[off + k * step] + eta * delta[off + k * step]
+
+    def terms(self, n_out):
+        """Products the kernel accumulates for output samples 0 .. n_out - 1 of an utterance (zero padding included)."""
+        per_col = np.repeat(16 * (self.chunks[:, 1] - self.chunks[:, 0]), 16)[:self.P * self.L]
+        t = per_col[np.arange(n_out) % (self.P * self.L)].astype(np.int64)
+        e = self.exceptions(-(-n_out // self.L))
+        idx = np.flatnonzero(e) * self.L
+        t[idx[idx < n_out]] = 64 * -(-len(self.alt) // 64)
+        return t
+
+    def exceptions(self, n_periods):
+        """uint8 (n_periods,): 1 where resampy's time register, advanced by repeated float64 addition of 1 / ratio, sits
+        just below the integer time p * M of output sample p * L, so that resampy takes n = p * M - 1 and the phase at
+        the end of the interval.  Where the filter is continuous there (index_step not truncated, every upsampling) the
+        two readings agree and no exception is reported."""
+        if not self.discontinuous:
+            return np.zeros(n_periods, dtype=np.uint8)
+        have = len(self._exc)
+        if have < n_periods:
+            inc = 1.0 / self.ratio
+            new = np.zeros(n_periods - have, dtype=np.uint8)
+            blk = max(1, (1 << 22) // self.L)  # periods per block of the running sum
+            t = self._exc_time
+            for a in range(0, len(new), blk):
+                b = min(a + blk, len(new))
+                acc = np.empty((b - a) * self.L + 1)
+                acc[0] = t
+                acc[1:] = inc
+                acc = np.cumsum(acc)  # sequential float64 additions, as the time register
+                at = acc[:-1:self.L]
+                new[a:b] = at.astype(np.int64) < (np.arange(have + a, have + b, dtype=np.int64) * self.M)
+                t = acc[-1]
+            self._exc = np.concatenate([self._exc, new])
+            self._exc_time = t
+        return self._exc[:n_periods]
+
+
+def resample_bank(sr_in, sr_out):
+    """The cached ResampleBank of a pair of rates; ValueError naming both rates and the limit for a ratio whose reduced
+    L / M has too many phases or too wide a window."""
+    key = (int(sr_in), int(sr_out))
+    if key[0] < 1 or key[1] < 1:
+        raise ValueError("sample rates must be positive, got %r -> %r" % (sr_in, sr_out))
+    if key not in _RS_CACHE:
+        _RS_CACHE[key] = ResampleBank(*key)
+    return _RS_CACHE[key]
+
+
+def resample_host(y, sr_in, sr_out):
+    """Float64 numpy model of the device computation (the bank applied row by row); for tests and small inputs."""
+    b = resample_bank(sr_in, sr_out)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n_ret, n_calc = resampled_length(len(y), sr_in, sr_out), int(_computed_length(len(y), sr_in, sr_out))
+    PL, PM = b.P * b.L, b.P * b.M
+    rows = -(-n_ret // PL)
+    x = np.concatenate([np.zeros(b.WL), y, np.zeros(rows * PM + b.KP)])
+    out = np.concatenate([b.bank[:PL] @ x[r * PM:r * PM + b.KP] for r in range(rows)]) if rows else np.zeros(0)
+    out = out[:n_ret].copy()
+    xa = np.concatenate([np.zeros(b.alt_wl + 1), y, np.zeros(len(b.alt))])
+    for p in np.flatnonzero(b.exceptions(-(-n_ret // b.L))):
+        if p * b.L < n_calc:
+            out[p * b.L] = b.alt @ xa[p * b.M:p * b.M + len(b.alt)]
+    out[n_calc:] = 0.0
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------- the launch
 def check_params(sr, ftype, win_t, hop_t, n_mels):
     if ftype not in FTYPES:
@@ -199,11 +385,141 @@ def batches(lengths, max_samples=BATCH_SAMPLES):
     return out
 
 
+class _ResampleDev:
+    """Device copies of one ResampleBank."""
+
+    def __init__(self, bank, device):
+        import torch
+
+        self.b = bank
+        self.bank = torch.from_numpy(bank.bank32).to(device)
+        self.chunks = torch.from_numpy(bank.chunks).to(device)
+        self.alt = torch.from_numpy(bank.alt32).to(device) if bank.discontinuous else None
+
+
+def _resample_batch(hb, waves, rd, device):
+    """One launch: the waveforms (float32, one source rate) -> (device tensor of the concatenated results, their lengths)."""
+    import torch
+
+    b = rd.b
+    lens = np.array([len(w) for w in waves], dtype=np.int64)
+    olens = resampled_length(lens, b.sr_in, b.sr_out)
+    PL = b.P * b.L
+    rows = -(-olens // PL)
+    ptrs = np.stack([np.concatenate([[0], np.cumsum(v)]).astype(np.int64) for v in (lens, olens, rows)])
+    n_in, n_out, n_rows = int(ptrs[0, -1]), int(ptrs[1, -1]), int(ptrs[2, -1])
+    out = torch.zeros(n_out, dtype=torch.float32, device=device)
+    if n_out == 0:
+        return out, olens, torch.zeros(1, dtype=torch.int32, device=device)
+    host = torch.empty(n_in, dtype=torch.float32, pin_memory=True)
+    np.concatenate(waves, out=host.numpy())
+    wave_d = host.to(device, non_blocking=True)
+    ptrs_d = torch.from_numpy(ptrs).pin_memory().to(device, non_blocking=True)
+    exc = None
+    if rd.alt is not None:
+        exc = torch.from_numpy(b.exceptions(int(-(-olens.max() // b.L))).copy()).to(device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    hb.resample_fwd(wave_d, ptrs_d[0], ptrs_d[1], ptrs_d[2], n_rows, rd.bank, rd.chunks, b.L, b.M, b.P, b.WL, b.ratio, exc,
+                    rd.alt if exc is not None else None, b.alt_wl, out, status)
+    return out, olens, status
+
+
+def resample(waves, sr_in, sr_out, device="cuda", max_samples=BATCH_SAMPLES):
+    """Every waveform (float32 1-D arrays at rate sr_in) converted to sr_out as librosa.load does (resampy kaiser_best,
+    ceil(n * sr_out / sr_in) samples) -> list of float32 arrays, in input order; batched into launches of at most
+    `max_samples` input samples.  sr_in == sr_out returns the input unchanged."""
+    if sr_in == sr_out:
+        return list(waves)
+    bank = resample_bank(sr_in, sr_out)
+    waves = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in waves]
+    if not waves:
+        return []
+    import torch
+
+    import hip_binding as hb
+
+    rd = _ResampleDev(bank, device)
+    out = []
+    for a, b in batches([len(w) for w in waves], max_samples):
+        r = _resample_batch(hb, waves[a:b], rd, device)
+        y, olens = r[0], r[1]
+        res = torch.empty(y.shape, dtype=torch.float32, pin_memory=True)
+        res.copy_(y, non_blocking=True)
+        st = int(r[2].cpu().item())  # (synchronises: the copy above is done too)
+        if st != 0:
+            raise RuntimeError("fhvae_resample_fwd: status %d (inconsistent in_ptr / out_ptr / row_ptr)" % st)
+        ptr = np.concatenate([[0], np.cumsum(olens)])
+        rn = res.numpy()
+        out.extend(rn[ptr[j]:ptr[j + 1]].copy() for j in range(b - a))
+    return out
+
+
+def _features_resampled(hb, waves, rd, n_fft, hop, n_mels, ftype, bases, device, names):
+    """One batch at a source rate: resampled on the device and handed to fhvae_feats_fwd there (no host round trip)."""
+    import torch
+
+    r = _resample_batch(hb, waves, rd, device)
+    y, olens = r[0], r[1]
+    for j, n in enumerate(olens):
+        if n < n_fft // 2 + 1:
+            raise ValueError("%s: %d samples after resampling; at least n_fft // 2 + 1 = %d are needed" % (names[j], n, n_fft // 2 + 1))
+    frames = num_frames(olens, n_fft, hop)
+    wave_ptr = np.concatenate([[0], np.cumsum(olens)]).astype(np.int64)
+    frame_ptr = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    n_out = n_mels if ftype == "fbank" else n_fft // 2 + 1
+    ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).pin_memory().to(device, non_blocking=True)
+    out = torch.empty((int(frame_ptr[-1]), n_out), dtype=torch.float32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    hb.feats_fwd(y, ptrs_d[0], ptrs_d[1], bases.dft, bases.mel, n_fft, hop, n_mels, ftype, out, status)
+    res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
+    res.copy_(out, non_blocking=True)
+    st = (int(r[2].cpu().item()), int(status.cpu().item()))  # (synchronises: the copy above is done too)
+    if st != (0, 0):
+        raise RuntimeError("fhvae_resample_fwd / fhvae_feats_fwd: status %s (inconsistent pointers)" % (st,))
+    rn = res.numpy()
+    return [rn[frame_ptr[j]:frame_ptr[j + 1]].copy() for j in range(len(waves))]
+
+
+def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples):
+    import hip_binding as hb
+
+    n_fft, hop = check_params(sr, ftype, win_t, hop_t, n_mels)
+    if len(rates) != len(waves):
+        raise ValueError("rates has %d entries for %d waveforms" % (len(rates), len(waves)))
+    names = list(names) if names is not None else ["utterance %d" % j for j in range(len(waves))]
+    groups = {}
+    for j, r in enumerate(rates):
+        groups.setdefault(int(r), []).append(j)
+    banks = {r: resample_bank(r, sr) for r in groups if r != sr}  # (an unsupported ratio fails before any work)
+    out = [None] * len(waves)
+    bases = None
+    for r, idx in groups.items():
+        if r == sr:
+            got = compute_features([waves[j] for j in idx], sr, ftype, win_t, hop_t, n_mels, [names[j] for j in idx], device,
+                                   max_samples)
+        else:
+            ws = [np.ascontiguousarray(waves[j], dtype=np.float32).reshape(-1) for j in idx]
+            if bases is None:
+                bases = _Bases(sr, n_fft, n_mels, ftype, device)
+            rd = _ResampleDev(banks[r], device)
+            got = []
+            for a, b in batches([len(w) for w in ws], max_samples):
+                got.extend(_features_resampled(hb, ws[a:b], rd, n_fft, hop, n_mels, ftype, bases, device,
+                                               [names[j] for j in idx[a:b]]))
+        for j, g in zip(idx, got):
+            out[j] = g
+    return out
+
+
 def compute_features(waves, sr, ftype="fbank", win_t=0.025, hop_t=0.010, n_mels=80, names=None, device="cuda",
-                     max_samples=BATCH_SAMPLES):
+                     max_samples=BATCH_SAMPLES, rates=None):
     """Features of every waveform (float32 1-D arrays at rate `sr`) -> list of float32 (nframes, n_mels) for "fbank" or
     (nframes, n_fft // 2 + 1) for "spec", in input order.  Batched into launches of at most `max_samples` samples.
-    `names` (optional) label the utterances in error messages."""
+    `names` (optional) label the utterances in error messages.  `rates` (optional, one source rate per waveform): the
+    waveforms whose rate is not `sr` are grouped by rate, resampled to `sr` on the device (see resample) and their features
+    computed from the device copy; the others take the same path as without `rates`."""
+    if rates is not None:
+        return _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples)
     import hip_binding as hb
 
     n_fft, hop = check_params(sr, ftype, win_t, hop_t, n_mels)

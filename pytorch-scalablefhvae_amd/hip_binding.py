@@ -141,6 +141,9 @@ SIGNATURES = {
     "fhvae_synth_istft": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_synth_project": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.c_float, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_synth_deemph": (C.c_int, [_vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _vp]),
+    "fhvae_resample_tile_rows": (C.c_int, [_i64]),
+    "fhvae_resample_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp,
+                                     _i64, _i64, _vp, _i64, _vp, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1409,6 +1412,38 @@ def feats_fwd(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, n_fft, hop, n_mel
         _check(lib.fhvae_feats_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
                                    _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status),
                                    _stream()), "fhvae_feats_fwd")
+
+
+RESAMPLE_BAD_PTR = 1  # FHVAE_RESAMPLE_BAD_PTR
+
+
+def resample_fwd(wave_in, in_ptr, out_ptr, row_ptr, n_rows, bank, chunks, L, M, P, WL, ratio, exc, alt, alt_wl, wave_out, status):
+    """Sample-rate conversion of a batch of utterances (fhvae_resample_fwd): wave_in (n_in,) f32 concatenated samples,
+    in_ptr / out_ptr / row_ptr (U+1,) int64 (n_rows = row_ptr[U]), bank (NCP, KP) f32 and chunks (NCP / 16, 2) int32 as features.ResampleBank
+    builds them, exc (n_exc,) uint8 with alt (alt_taps,) f32 or both None, wave_out (out_ptr[U],) f32, status (1,) int32
+    (RESAMPLE_BAD_PTR when the pointers break the length rule)."""
+    _need_gpu(wave_in, in_ptr, out_ptr, row_ptr, bank, chunks, exc, alt, wave_out, status)
+    for t in (wave_in, bank, wave_out) + ((alt,) if alt is not None else ()):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("resample_fwd takes contiguous f32 samples, bank and output")
+    for t in (in_ptr, out_ptr, row_ptr):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.shape != in_ptr.shape or t.shape[0] < 2:
+            raise RuntimeError("resample_fwd takes contiguous int64 in_ptr / out_ptr / row_ptr of one length (U + 1)")
+    if status.dtype != torch.int32 or status.numel() != 1 or wave_in.dim() != 1 or wave_out.dim() != 1:
+        raise RuntimeError("resample_fwd: status must be one int32 word, wave_in and wave_out 1-D")
+    NCP = (P * L + 15) // 16 * 16
+    if bank.dim() != 2 or bank.shape[0] != NCP or bank.shape[1] % 16 != 0:
+        raise RuntimeError("resample_fwd: bank must be (%d, KP) with KP a multiple of 16" % NCP)
+    if chunks.dtype != torch.int32 or not chunks.is_contiguous() or tuple(chunks.shape) != (NCP // 16, 2):
+        raise RuntimeError("resample_fwd: chunks must be contiguous int32 (%d, 2)" % (NCP // 16))
+    if (exc is None) != (alt is None) or (exc is not None and (exc.dtype != torch.uint8 or not exc.is_contiguous() or exc.dim() != 1)):
+        raise RuntimeError("resample_fwd: exc (uint8, 1-D) and alt come together")
+    lib = load_library()
+    with _Timed("fhvae_resample_fwd"):
+        _check(lib.fhvae_resample_fwd(_p(wave_in), wave_in.numel(), _p(in_ptr), _p(out_ptr), _p(row_ptr), in_ptr.shape[0] - 1,
+                                      n_rows, _p(bank), _p(chunks), L, M, P, bank.shape[1], WL, float(ratio), _p(exc),
+                                      0 if exc is None else exc.numel(), _p(alt), 0 if alt is None else alt.numel(), alt_wl,
+                                      _p(wave_out), wave_out.numel(), _p(status), _stream()), "fhvae_resample_fwd")
 
 
 SYNTH_BAD_PTR = 1  # FHVAE_SYNTH_BAD_PTR

@@ -2,7 +2,7 @@
 prepare_numpy_data.py:50-205, with the features computed on the MI355X by features.compute_features).
 
     python pytorch-scalablefhvae_amd/prepare_numpy_data.py DATASET_DIR [--np_dir OUT] [--set_name train]
-        [--ftype {fbank,spec}] [--sr RATE] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80]
+        [--ftype {fbank,spec}] [--sr RATE] [--resample] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<seq> <path>"
 lines) and writes, in wav.scp order, <OUT>/<set>/<seq>.npy (float32, (nframes, n_mels) or (nframes, n_fft // 2 + 1)) plus
@@ -11,8 +11,10 @@ lines) and writes, in wav.scp order, <OUT>/<set>/<seq>.npy (float32, (nframes, n
 Differences from the reference:
   * wav.scp is read from DATASET_DIR even when --np_dir is given (the reference looks for it under the output directory,
     prepare_numpy_data.py:81-92, which only works when both are the same).
-  * no resampling: every file of a set must have one sample rate, and a --sr that differs from a file's rate is an error
-    (the reference resampled with resampy through librosa.load).
+  * resampling is opt-in: by default every file of a set must have one sample rate, and a --sr that differs from a
+    file's rate is an error.  With --resample (which needs --sr, the target rate) files at other rates are converted to
+    --sr on the GPU as the reference's librosa.load does (resampy kaiser_best; features.resample); files already at --sr
+    go through unchanged.  The reference always resampled.
   * integer PCM WAV only (features.read_wav); sets run one after the other on the GPU instead of a pool of 3 processes.
 """
 from __future__ import annotations
@@ -42,10 +44,12 @@ def read_wav_scp(path):
 
 
 def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank", sample_rate=None, win_t=0.025, hop_t=0.010,
-                  n_mels=80, timings=None):
+                  n_mels=80, timings=None, resample=False):
     """prepare_numpy_data.py:50-129: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (wav_path, feat_path, len_path)).  `timings` (optional dict) receives seconds spent in "read", "gpu"
-    and "write"."""
+    and "write".  `resample`: files whose rate differs from `sample_rate` (required then) are converted to it on the GPU."""
+    if resample and sample_rate is None:
+        raise ValueError("--resample needs --sr, the target sample rate")
     wav_path = Path(dataset_dir) / set_name / "wav.scp"
     set_path = Path(output_dir if output_dir is not None else dataset_dir) / set_name
     if not os.path.exists(wav_path):
@@ -75,6 +79,8 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
             # the next chunk's files are read while this one is on the GPU and being written
             pending = [pool.submit(load, e) for e in chunks[ci + 1]] if ci + 1 < len(chunks) else []
             for seq, path, _, sr in got:
+                if resample:
+                    continue
                 if sample_rate is None:
                     sample_rate = sr
                 elif sr != sample_rate:
@@ -82,7 +88,8 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
                                      f"or pass the matching --sr)")
             t0 = time.time()
             feats = features.compute_features([g[2] for g in got], sample_rate, ftype, win_t, hop_t, n_mels,
-                                              names=["%s (%s)" % (g[0], g[1]) for g in got])
+                                              names=["%s (%s)" % (g[0], g[1]) for g in got],
+                                              rates=[g[3] for g in got] if resample else None)
             t["gpu"] += time.time() - t0
             t0 = time.time()
             for (seq, _, _, _), feat in zip(got, feats):
@@ -108,6 +115,8 @@ def build_parser():
     p.add_argument("--ftype", type=str, default="fbank", choices=["fbank", "spec"], help="Feature type to compute")
     p.add_argument("--sr", type=int, default=None,
                    help="Sample rate every file must have (no resampling); default: the rate of the first file")
+    p.add_argument("--resample", action="store_true",
+                   help="Convert files whose rate differs from --sr (required then) to --sr on the GPU, as librosa.load does")
     p.add_argument("--win_t", type=float, default=0.025, help="Window size in seconds")
     p.add_argument("--hop_t", type=float, default=0.010, help="Frame spacing in seconds")
     p.add_argument("--n_mels", type=int, default=80, help="Number of filter banks if choosing fbank")
@@ -115,14 +124,17 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.resample and args.sr is None:
+        parser.error("--resample needs --sr, the target sample rate")
     print(args)
     sets = ["train", "dev", "test"] if args.set_name is None else [args.set_name]
     t0 = time.time()
     total = 0
     for s in sets:
         total += prepare_numpy(args.dataset, s, args.dataset_dir, args.np_dir, args.ftype, args.sr, args.win_t, args.hop_t,
-                               args.n_mels)[0]
+                               args.n_mels, resample=args.resample)[0]
     if len(sets) > 1:
         print(f"Processed {total} files in {time.time() - t0} seconds.")
     return 0
