@@ -588,6 +588,34 @@ int fhvae_resample_fwd(const float* wave_in, int64_t n_in, const int64_t* in_ptr
                        const float* alt, int64_t alt_taps, int64_t alt_wl, float* wave_out, int64_t n_out, int32_t* status,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear magnitudes from mel magnitudes (csrc/melinv.hip): per frame, minimise ||A x - m||^2 over x >= 0 for the mel bank A
+ * (n_mels, n_bins) by n_iter accelerated projected-gradient (FISTA) steps from zero, all in one launch:
+ *   x = y = 0;  n_iter times { g = A^T (A y - m);  x+ = max(y - inv_l g, 0);  y = x+ + beta[k] (x+ - x);  x = x+ }
+ *   mel (n_frames, n_mels) f32: mel magnitudes m, or with FHVAE_MELINV_IN_LOG their natural logarithms (exp on the device).
+ *   out (n_frames, n_bins) f32: x, or with FHVAE_MELINV_OUT_LOG max(ln x, -50) as FHVAE_FEATS_SPEC features look.
+ *   The bank in band form (a bin lies in at most two adjacent filters, a filter is one contiguous run of bins):
+ *     bin_filt (n_bins) int32 in [0, n_mels): the lower filter f of bin b; bin_w (n_bins, 2) f32 = A[f, b], A[f + 1, b] (zero
+ *       where there is none).
+ *     filt_first (n_mels) int32, filt_off (n_mels + 1) int32, filt_w (nnz) f32: filter j holds A[j, filt_first[j] + k] =
+ *       filt_w[filt_off[j] + k] for k < filt_off[j + 1] - filt_off[j]; filt_off[0] = 0, filt_off[n_mels] = nnz <= 2 n_bins.  A
+ *       filter without bins is legal.
+ *   inv_l f32 = 1 / lambda_max(A A^T), not above it; beta (n_iter) f32 = (t_k - 1) / t_{k+1}, t_0 = 1,
+ *     t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2: both computed by the host in double precision.
+ *   n_mels in [1, FHVAE_FEATS_MAX_NMELS], n_bins in [2, FHVAE_FEATS_MAX_NFFT / 2 + 1], n_iter >= 1, otherwise
+ *   FHVAE_ERR_SHAPE / FHVAE_ERR_LIMIT before any launch.  A band that points outside its arrays sets FHVAE_MELINV_BAD_BAND
+ *   in the int32 device word `status` (never cleared by the library) and nothing is written.  Every output is a fixed-order
+ *   f32 chain over its own frame: bitwise independent of the batch and of the frame's place in it.
+ * tile_rows: frames per workgroup for (n_mels, n_bins); 0 = not supported.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_MELINV_IN_LOG 1
+#define FHVAE_MELINV_OUT_LOG 2
+#define FHVAE_MELINV_BAD_BAND 1
+int fhvae_mel_invert_tile_rows(int64_t n_mels, int64_t n_bins);
+int fhvae_mel_invert(const float* mel, int64_t n_frames, int64_t n_mels, int64_t n_bins, const int32_t* bin_filt,
+                     const float* bin_w, const int32_t* filt_first, const int32_t* filt_off, const float* filt_w, int64_t nnz,
+                     float inv_l, const float* beta, int64_t n_iter, int flags, float* out, int32_t* status, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -13,7 +13,9 @@ With --wav-out DIR --wav-seqs N (needs --feat-scp data of "spec" features, n_fft
 sequences are also made audible: every segment of a sequence is reconstructed (and, with --convert-to Y, decoded with Y's
 mu2), the decoder means are un-normalised, put back together (utils.overlap_mean) and turned into a waveform by Griffin-Lim
 (features.synthesize): DIR/<seq>_orig.wav (the input features through the same vocoder: the ceiling of what it can do),
-<seq>_recon.wav and <seq>_to_<Y>.wav, listed under "wavs" in summary.json.
+<seq>_recon.wav and <seq>_to_<Y>.wav, listed under "wavs" in summary.json.  With --wav-ftype fbank the data are mel features
+(as many columns as the checkpoint's feature width) and the three go through features.synthesize_mel instead: linear
+magnitudes fitted to the mel magnitudes (non-negative least squares, --nnls-iters steps), then the same Griffin-Lim.
 
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
@@ -54,7 +56,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hop-t", type=float, default=0.010)
     p.add_argument("--gl-iters", type=int, default=32, help="Griffin-Lim rounds")
     p.add_argument("--gl-seed", type=int, default=0, help="seed of the initial phases")
+    p.add_argument("--wav-ftype", default="spec", choices=["spec", "fbank"],
+                   help="feature type of the --feat-scp data for --wav-out; fbank: mel inversion in front of Griffin-Lim")
+    p.add_argument("--nnls-iters", type=int, default=200, help="steps of the mel inversion (--wav-ftype fbank)")
     return p
+
+
+def feature_width(model, seg_len):
+    """Features per frame the checkpoint was trained on."""
+    if hasattr(model, "n_feat"):
+        return int(model.n_feat)
+    return int(model.dec_gauss_layer.mulayer.out_features) // int(seg_len)  # (SimpleFHVAE works on flattened segments)
 
 
 def write_wavs(args, model, ds, mu2, dev):
@@ -84,8 +96,12 @@ def write_wavs(args, model, ds, mu2, dev):
                                              T, shift, len(feat))
                 assert n == covered
                 names.append("%s_%s" % (seq, tag)), specs.append(full.numpy())
-    waves = features.synthesize(specs, args.sr, args.win_t, args.hop_t, n_iter=args.gl_iters, seed=args.gl_seed, device=dev,
-                                names=names)
+    if args.wav_ftype == "fbank":
+        waves = features.synthesize_mel(specs, args.sr, args.win_t, args.hop_t, nnls_iters=args.nnls_iters, n_iter=args.gl_iters,
+                                        seed=args.gl_seed, device=dev, names=names)
+    else:
+        waves = features.synthesize(specs, args.sr, args.win_t, args.hop_t, n_iter=args.gl_iters, seed=args.gl_seed, device=dev,
+                                    names=names)
     files = []
     for name, y in zip(names, waves):
         features.write_wav(os.path.join(args.wav_out, name + ".wav"), y, args.sr)
@@ -103,6 +119,8 @@ def main(argv=None) -> int:
             return 1
         try:
             n_fft, _ = features.check_synth_params(args.sr, args.win_t, args.hop_t, args.gl_iters, 0.99, 0.97)
+            if args.wav_ftype == "fbank" and args.nnls_iters < 1:
+                raise ValueError("--nnls-iters %d must be at least 1" % args.nnls_iters)
         except ValueError as e:
             print("--wav-out: %s" % e, file=sys.stderr)
             return 1
@@ -124,7 +142,16 @@ def main(argv=None) -> int:
                           args.seg_shift, False)
         if args.wav_out is not None:
             cols = np.load(ds.seq_feats[0], mmap_mode="r").shape[1] if len(ds) else -1
-            if cols != n_fft // 2 + 1:
+            if args.wav_ftype == "fbank":
+                width = feature_width(model, T)
+                try:
+                    if cols != width:
+                        raise ValueError("the features have %d columns, but the checkpoint was trained on %d" % (cols, width))
+                    features.check_melinv_params(args.sr, args.win_t, args.hop_t, cols, args.nnls_iters)
+                except ValueError as e:
+                    print("--wav-out --wav-ftype fbank: %s" % e, file=sys.stderr)
+                    return 1
+            elif cols != n_fft // 2 + 1:
                 print("--wav-out: the features have %d columns, but --sr %d / --win-t %g need \"spec\" features of n_fft // 2 + 1 = %d "
                       "columns (mel \"fbank\" features cannot be inverted)" % (cols, args.sr, args.win_t, n_fft // 2 + 1), file=sys.stderr)
                 return 1

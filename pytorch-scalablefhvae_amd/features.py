@@ -24,6 +24,14 @@ and the way back for "spec" features (csrc/synth.hip: fhvae_synth_istft / _proje
                       Griffin-Lim (librosa 0.8.0 griffinlim semantics) and de-emphasis, batched into bounded launches
   write_wav           float32 mono -> 16-bit PCM WAV (the inverse of read_wav)
 
+and for "fbank" features the step in front of it (csrc/melinv.hip: fhvae_mel_invert):
+
+  MelBand             the mel bank in band form (a bin in at most two adjacent filters, a filter one run of bins)
+  nnls_constants      1 / L and the momentum table of FISTA on ||A x - m||^2, in float64
+  mel_to_spec         a list of (nframes, n_mels) log-mel features -> a list of (nframes, n_fft // 2 + 1) log-magnitude
+                      spectrograms: non-negative least squares against mel_filters, a fixed number of FISTA steps from zero
+  synthesize_mel      mel_to_spec, then synthesize on the device buffer
+
 Utterances shorter than n_fft // 2 + 1 samples are an error (one reflection of the centre padding must suffice; numpy's
 repeated reflection for shorter inputs is not reproduced).
 """
@@ -607,7 +615,8 @@ def check_specs(specs, sr, n_fft, names=None):
         if S.shape[1] != n_bins:
             hint = ""
             if S.shape[1] == 80:
-                hint = " (80 columns look like ftype=\"fbank\" features: mel inversion is out of scope, only \"spec\" features can be synthesized)"
+                hint = (" (80 columns look like ftype=\"fbank\" features: mel inversion is out of scope, only \"spec\" features can be "
+                        "synthesized here; synthesize_mel inverts mel features)")
             raise ValueError("%s: %d columns, but sr %d and the window give n_fft // 2 + 1 = %d%s" % (name, S.shape[1], sr, n_bins, hint))
         if S.shape[0] < 2:
             raise ValueError("%s: %d frame(s); at least 2 are needed" % (name, S.shape[0]))
@@ -629,8 +638,10 @@ class _SynthBases:
         self.wsq = torch.from_numpy(window_sq(n_fft)).to(device)
 
 
-def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, log, bases, device):
-    """Griffin-Lim of one batch; every round is two library calls on the stream, nothing is read back before the end."""
+def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, log, bases, device, spec_dev=None):
+    """Griffin-Lim of one batch; every round is two library calls on the stream, nothing is read back before the end.
+    `spec_dev`: the concatenated spectrograms already on the device (synthesize_mel); `specs` then only gives the frame
+    counts."""
     import torch
 
     frames = np.array([len(S) for S in specs], dtype=np.int64)
@@ -639,7 +650,7 @@ def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, l
     frame_ptr = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
     n_frames, n_samples, n_bins = int(frame_ptr[-1]), int(wave_ptr[-1]), n_fft // 2 + 1
     ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).to(device)
-    mag = torch.from_numpy(np.concatenate(specs)).to(device)
+    mag = spec_dev if spec_dev is not None else torch.from_numpy(np.concatenate(specs)).to(device)
     if log:
         mag = torch.exp(mag)
     ph = np.concatenate(phases)
@@ -670,6 +681,18 @@ def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, l
     return [r[wave_ptr[j]:wave_ptr[j + 1]].copy() for j in range(len(specs))]
 
 
+def _check_init_phase(init_phase, shapes):
+    if init_phase is None:
+        return None
+    if len(init_phase) != len(shapes):
+        raise ValueError("init_phase has %d arrays for %d spectrograms" % (len(init_phase), len(shapes)))
+    init_phase = [np.asarray(p, dtype=np.complex128) for p in init_phase]
+    for j, (p, shape) in enumerate(zip(init_phase, shapes)):
+        if p.shape != tuple(shape):
+            raise ValueError("init_phase[%d] has shape %s, the spectrogram %s" % (j, p.shape, tuple(shape)))
+    return init_phase
+
+
 def synthesize(specs, sr, win_t=0.025, hop_t=0.010, n_iter=32, momentum=0.99, preemphasis=0.97, seed=0, init_phase=None,
                log=True, device="cuda", max_frames=BATCH_FRAMES, names=None):
     """Waveforms (float32, hop * (nframes - 1) samples each) of (nframes, n_fft // 2 + 1) spectrograms as
@@ -677,16 +700,10 @@ def synthesize(specs, sr, win_t=0.025, hop_t=0.010, n_iter=32, momentum=0.99, pr
     Griffin-Lim with librosa 0.8.0's semantics and the inverse of the features' pre-emphasis (`preemphasis=0`: none).
     Initial phases are exp(2 pi i u), u drawn from numpy.random.RandomState(seed) utterance by utterance in input order,
     unless `init_phase` gives them: a list of complex (nframes, n_fft // 2 + 1) arrays of unit modulus.  Only "spec"
-    features can be inverted; mel ("fbank") inversion is out of scope."""
+    features are taken here; mel ("fbank") features go through synthesize_mel."""
     n_fft, hop = check_synth_params(sr, win_t, hop_t, n_iter, momentum, preemphasis)
     specs = check_specs(specs, sr, n_fft, names)
-    if init_phase is not None:
-        if len(init_phase) != len(specs):
-            raise ValueError("init_phase has %d arrays for %d spectrograms" % (len(init_phase), len(specs)))
-        init_phase = [np.asarray(p, dtype=np.complex128) for p in init_phase]
-        for j, (p, S) in enumerate(zip(init_phase, specs)):
-            if p.shape != S.shape:
-                raise ValueError("init_phase[%d] has shape %s, the spectrogram %s" % (j, p.shape, S.shape))
+    init_phase = _check_init_phase(init_phase, [S.shape for S in specs])
     rng = np.random.RandomState(seed)
     if not specs:
         return []
@@ -697,4 +714,213 @@ def synthesize(specs, sr, win_t=0.025, hop_t=0.010, n_iter=32, momentum=0.99, pr
     for a, b in frame_batches([len(S) for S in specs], max_frames):
         phases = init_phase[a:b] if init_phase is not None else [np.exp(2j * np.pi * rng.rand(*S.shape)) for S in specs[a:b]]
         out.extend(_synth_batch(hb, specs[a:b], phases, n_fft, hop, n_iter, momentum, preemphasis, log, bases, device))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------- mel inversion
+# "fbank" features are mel_filters . |STFT| (utils.py:257-268), so the way back to linear magnitudes is, per frame,
+# min ||A x - m||^2 over x >= 0 (librosa 0.8.0 feature.inverse.mel_to_stft, power = 1).  The minimiser is not unique (A is
+# n_mels x n_bins, and rank deficient at 16 kHz / 80 mels), so the algorithm is fixed instead: nnls_iters steps of FISTA
+# from zero (csrc/melinv.hip), its constants computed here in float64.
+NNLS_ITERS = 200
+
+
+class MelBand:
+    """A mel bank (n_mels, n_bins) float64 in the band form csrc/melinv.hip works on.  Slaney triangles overlap by half: a
+    bin lies in at most two adjacent filters and a filter is one contiguous run of bins; a matrix of any other shape is
+    refused (ValueError).  bin_filt (n_bins,) int32 / bin_w (n_bins, 2): the lower filter f of a bin and A[f, b], A[f + 1, b];
+    filt_first (n_mels,) / filt_off (n_mels + 1,) int32 / filt_w (nnz,): the run of every filter and its weights."""
+
+    def __init__(self, A):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 2 or not np.all(np.isfinite(A)):
+            raise ValueError("a mel bank must be a finite (n_mels, n_bins) matrix, got shape %s" % (A.shape,))
+        n_mels, n_bins = A.shape
+        nz = A != 0.0
+        self.n_mels, self.n_bins = n_mels, n_bins
+        self.filt_first = np.zeros(n_mels, dtype=np.int32)
+        self.filt_off = np.zeros(n_mels + 1, dtype=np.int32)
+        w = []
+        for j in range(n_mels):
+            k = np.flatnonzero(nz[j])
+            if len(k):
+                if k[-1] - k[0] + 1 != len(k):
+                    raise ValueError("the mel bank is not banded: filter %d is not one contiguous run of bins" % j)
+                self.filt_first[j] = k[0]
+                w.append(A[j, k[0]:k[-1] + 1])
+            self.filt_off[j + 1] = self.filt_off[j] + len(k)
+        self.filt_w = np.concatenate(w) if w else np.zeros(0)
+        self.bin_filt = np.zeros(n_bins, dtype=np.int32)
+        self.bin_w = np.zeros((n_bins, 2), dtype=np.float64)
+        for b in range(n_bins):
+            f = np.flatnonzero(nz[:, b])
+            if len(f) > 2 or (len(f) == 2 and f[1] != f[0] + 1):
+                raise ValueError("the mel bank is not banded: bin %d lies in filters %s, not in at most two adjacent ones"
+                                 % (b, f.tolist()))
+            if len(f):
+                self.bin_filt[b] = f[0]
+                self.bin_w[b, 0] = A[f[0], b]
+                if len(f) == 2:
+                    self.bin_w[b, 1] = A[f[1], b]
+
+    def dense(self):
+        """The (n_mels, n_bins) matrix again, from the filter side."""
+        A = np.zeros((self.n_mels, self.n_bins))
+        for j in range(self.n_mels):
+            o0, o1 = self.filt_off[j], self.filt_off[j + 1]
+            A[j, self.filt_first[j]:self.filt_first[j] + o1 - o0] = self.filt_w[o0:o1]
+        return A
+
+    def dense_from_bins(self):
+        """The same matrix from the bin side (the two must agree: the kernel uses one per product)."""
+        A = np.zeros((self.n_mels, self.n_bins))
+        for b in range(self.n_bins):
+            f = self.bin_filt[b]
+            A[f, b] = self.bin_w[b, 0]
+            if self.bin_w[b, 1] != 0.0:
+                A[f + 1, b] = self.bin_w[b, 1]
+        return A
+
+
+def inversion_bank(sr, n_fft, n_mels):
+    """The bank the "fbank" features of (sr, n_fft, n_mels) were taken with: (n_mels, n_fft // 2 + 1) float64."""
+    return mel_filters(sr, 2 * (n_fft // 2), n_mels)
+
+
+def nnls_constants(A, n_iter):
+    """-> (inv_l float32, beta float32 (n_iter,)) of FISTA on ||A x - m||^2: L = lambda_max(A A^T) (numpy.linalg.eigvalsh,
+    float64) nudged up by one part in 2**20 before 1 / L is rounded to f32, so that the f32 step is never above 1 / L;
+    beta[k] = (t_k - 1) / t_{k+1}, t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2, tabulated in float64."""
+    A = np.asarray(A, dtype=np.float64)
+    L = float(np.linalg.eigvalsh(A @ A.T)[-1])
+    if not L > 0.0:
+        raise ValueError("the mel bank is zero: nothing to invert")
+    inv_l = np.float32(1.0 / (L * (1.0 + 2.0 ** -20)))
+    beta = np.empty(int(n_iter), dtype=np.float64)
+    t = 1.0
+    for k in range(int(n_iter)):
+        tn = (1.0 + np.sqrt(1.0 + 4.0 * t * t)) / 2.0
+        beta[k] = (t - 1.0) / tn
+        t = tn
+    return inv_l, beta.astype(np.float32)
+
+
+def check_melinv_params(sr, win_t, hop_t, n_mels, nnls_iters):
+    n_fft, hop = check_params(sr, "fbank", win_t, hop_t, n_mels)
+    if nnls_iters < 1:
+        raise ValueError("nnls_iters = %d must be at least 1" % nnls_iters)
+    return n_fft, hop
+
+
+def check_mels(mels, n_mels, names=None):
+    """-> the mel features as contiguous float32 arrays; ValueError for anything mel_to_spec cannot invert.  n_mels None:
+    the column count of the first array."""
+    out = []
+    for j, S in enumerate(mels):
+        name = names[j] if names is not None else "mel features %d" % j
+        S = np.asarray(S)
+        if S.ndim != 2:
+            raise ValueError("%s: expected a (nframes, n_mels) array, got shape %s" % (name, S.shape))
+        if n_mels is None:
+            n_mels = S.shape[1]
+        if S.shape[1] != n_mels:
+            raise ValueError("%s: %d columns, but n_mels = %d" % (name, S.shape[1], n_mels))
+        if S.shape[0] < 2:
+            raise ValueError("%s: %d frame(s); at least 2 are needed" % (name, S.shape[0]))
+        out.append(np.ascontiguousarray(S, dtype=np.float32))
+    return out, n_mels
+
+
+class _MelInvDev:
+    """Device copies of the band and the FISTA constants for one (sr, n_fft, n_mels, nnls_iters)."""
+
+    def __init__(self, sr, n_fft, n_mels, nnls_iters, device):
+        import torch
+
+        A = inversion_bank(sr, n_fft, n_mels)
+        band = MelBand(A)  # (refuses a bank that is not banded before anything is launched)
+        self.inv_l, beta = nnls_constants(A, nnls_iters)
+        self.n_bins = band.n_bins
+        self.bin_filt = torch.from_numpy(band.bin_filt).to(device)
+        self.bin_w = torch.from_numpy(band.bin_w.astype(np.float32)).to(device)
+        self.filt_first = torch.from_numpy(band.filt_first).to(device)
+        self.filt_off = torch.from_numpy(band.filt_off).to(device)
+        self.filt_w = torch.from_numpy(band.filt_w.astype(np.float32)).to(device)
+        self.beta = torch.from_numpy(beta).to(device)
+
+
+def _melinv_batch(hb, mels, md, log, device):
+    """One launch: the mel features of a batch -> ((n_frames, n_bins) device tensor, status word)."""
+    import torch
+
+    n = sum(len(S) for S in mels)
+    host = torch.empty((n, mels[0].shape[1]), dtype=torch.float32, pin_memory=True)
+    np.concatenate(mels, out=host.numpy())
+    mel_d = host.to(device, non_blocking=True)
+    out = torch.empty((n, md.n_bins), dtype=torch.float32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    hb.mel_invert(mel_d, md.bin_filt, md.bin_w, md.filt_first, md.filt_off, md.filt_w, md.inv_l, md.beta, out, status, in_log=log,
+                  out_log=log)
+    return out, status
+
+
+def mel_to_spec(mels, sr, win_t=0.025, hop_t=0.010, n_mels=None, nnls_iters=NNLS_ITERS, log=True, device="cuda",
+                max_frames=BATCH_FRAMES, names=None):
+    """(nframes, n_fft // 2 + 1) float32 spectrograms of (nframes, n_mels) mel features as compute_features(..., "fbank")
+    writes them (`log=True`: log-mels in, max(log magnitude, -50) out, as "spec" features look; False: magnitudes in and
+    out), in input order: per frame the non-negative least-squares fit against mel_filters by `nnls_iters` steps of FISTA
+    from zero (fhvae_mel_invert), batched into launches of at most `max_frames` frames.  `n_mels` defaults to the column
+    count.  A frame's result depends on that frame alone."""
+    mels, n_mels = check_mels(mels, n_mels, names)
+    if n_mels is None:
+        n_mels = 80  # (no features: only the parameters are checked)
+    n_fft, _ = check_melinv_params(sr, win_t, hop_t, n_mels, nnls_iters)
+    if not mels:
+        return []
+    import torch
+
+    import hip_binding as hb
+
+    md = _MelInvDev(sr, n_fft, n_mels, nnls_iters, device)
+    out = []
+    for a, b in frame_batches([len(S) for S in mels], max_frames):
+        spec, status = _melinv_batch(hb, mels[a:b], md, log, device)
+        res = torch.empty(spec.shape, dtype=torch.float32, pin_memory=True)
+        res.copy_(spec, non_blocking=True)
+        st = int(status.cpu().item())  # (synchronises: the copy above is done too)
+        if st != 0:
+            raise RuntimeError("fhvae_mel_invert: status %d (the band points outside its arrays)" % st)
+        ptr = np.concatenate([[0], np.cumsum([len(S) for S in mels[a:b]])])
+        r = res.numpy()
+        out.extend(r[ptr[j]:ptr[j + 1]].copy() for j in range(b - a))
+    return out
+
+
+def synthesize_mel(mels, sr, win_t=0.025, hop_t=0.010, n_mels=None, nnls_iters=NNLS_ITERS, n_iter=32, momentum=0.99,
+                   preemphasis=0.97, seed=0, init_phase=None, log=True, device="cuda", max_frames=BATCH_FRAMES, names=None):
+    """Waveforms (float32, hop * (nframes - 1) samples each) of (nframes, n_mels) mel features: mel_to_spec, then Griffin-Lim
+    as synthesize runs it, on the device buffer the inversion left (no host round trip).  Bitwise equal to
+    synthesize(mel_to_spec(mels, ...), ...) with the same arguments: the phases are drawn exactly as synthesize draws them."""
+    n_fft, hop = check_synth_params(sr, win_t, hop_t, n_iter, momentum, preemphasis)
+    mels, n_mels = check_mels(mels, n_mels, names)
+    if n_mels is None:
+        n_mels = 80
+    check_melinv_params(sr, win_t, hop_t, n_mels, nnls_iters)
+    n_bins = n_fft // 2 + 1
+    init_phase = _check_init_phase(init_phase, [(len(S), n_bins) for S in mels])
+    rng = np.random.RandomState(seed)
+    if not mels:
+        return []
+    import hip_binding as hb
+
+    md = _MelInvDev(sr, n_fft, n_mels, nnls_iters, device)
+    bases = _SynthBases(n_fft, device)
+    out = []
+    for a, b in frame_batches([len(S) for S in mels], max_frames):
+        phases = init_phase[a:b] if init_phase is not None else [np.exp(2j * np.pi * rng.rand(len(S), n_bins)) for S in mels[a:b]]
+        spec, status = _melinv_batch(hb, mels[a:b], md, log, device)
+        out.extend(_synth_batch(hb, mels[a:b], phases, n_fft, hop, n_iter, momentum, preemphasis, log, bases, device, spec_dev=spec))
+        st = int(status.cpu().item())
+        if st != 0:
+            raise RuntimeError("fhvae_mel_invert: status %d (the band points outside its arrays)" % st)
     return out

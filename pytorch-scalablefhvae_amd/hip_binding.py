@@ -144,6 +144,8 @@ SIGNATURES = {
     "fhvae_resample_tile_rows": (C.c_int, [_i64]),
     "fhvae_resample_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp,
                                      _i64, _i64, _vp, _i64, _vp, _vp]),
+    "fhvae_mel_invert_tile_rows": (C.c_int, [_i64, _i64]),
+    "fhvae_mel_invert": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1512,6 +1514,42 @@ def synth_deemph(wave, wave_ptr, coef, out, status):
     with _Timed("fhvae_synth_deemph"):
         _check(lib.fhvae_synth_deemph(_p(wave), _p(wave_ptr), wave_ptr.shape[0] - 1, wave.numel(), float(coef), _p(out), _p(status),
                                       _stream()), "fhvae_synth_deemph")
+
+
+MELINV_BAD_BAND = 1  # FHVAE_MELINV_BAD_BAND
+MELINV_IN_LOG, MELINV_OUT_LOG = 1, 2  # FHVAE_MELINV_IN_LOG / FHVAE_MELINV_OUT_LOG
+
+
+def mel_invert(mel, bin_filt, bin_w, filt_first, filt_off, filt_w, inv_l, beta, out, status, in_log=True, out_log=True):
+    """Non-negative least squares of every frame against the mel bank in one launch (fhvae_mel_invert): mel (n_frames, n_mels)
+    f32 mel magnitudes (`in_log`: their logarithms), the band as features.MelBand holds it (bin_filt (n_bins,) int32, bin_w
+    (n_bins, 2) f32, filt_first (n_mels,) int32, filt_off (n_mels + 1,) int32, filt_w (nnz,) f32), inv_l = 1 / L, beta (n_iter,)
+    f32 momentum factors, out (n_frames, n_bins) f32 magnitudes (`out_log`: max(log, -50)), status (1,) int32
+    (MELINV_BAD_BAND when the band points outside its arrays)."""
+    _need_gpu(mel, bin_filt, bin_w, filt_first, filt_off, filt_w, beta, out, status)
+    for t in (mel, bin_w, filt_w, beta, out):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("mel_invert takes contiguous f32 mel, bin_w, filt_w, beta and out")
+    for t in (bin_filt, filt_first, filt_off):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+            raise RuntimeError("mel_invert takes contiguous 1-D int32 bin_filt / filt_first / filt_off")
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise RuntimeError("mel_invert: status must be one int32 word")
+    if mel.dim() != 2 or out.dim() != 2 or out.shape[0] != mel.shape[0]:
+        raise RuntimeError("mel_invert: mel must be (n_frames, n_mels) and out (n_frames, n_bins)")
+    n_mels, n_bins = mel.shape[1], out.shape[1]
+    if bin_filt.shape[0] != n_bins or tuple(bin_w.shape) != (n_bins, 2):
+        raise RuntimeError("mel_invert: bin_filt must be (%d,) and bin_w (%d, 2)" % (n_bins, n_bins))
+    if filt_first.shape[0] != n_mels or filt_off.shape[0] != n_mels + 1 or filt_w.dim() != 1:
+        raise RuntimeError("mel_invert: filt_first must be (%d,), filt_off (%d,) and filt_w 1-D" % (n_mels, n_mels + 1))
+    if beta.dim() != 1 or beta.shape[0] < 1:
+        raise RuntimeError("mel_invert: beta must hold one factor per iteration")
+    lib = load_library()
+    flags = (MELINV_IN_LOG if in_log else 0) | (MELINV_OUT_LOG if out_log else 0)
+    with _Timed("fhvae_mel_invert"):
+        _check(lib.fhvae_mel_invert(_p(mel), mel.shape[0], n_mels, n_bins, _p(bin_filt), _p(bin_w), _p(filt_first), _p(filt_off),
+                                    _p(filt_w), filt_w.numel(), float(inv_l), _p(beta), beta.shape[0], flags, _p(out), _p(status),
+                                    _stream()), "fhvae_mel_invert")
 
 
 def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):
