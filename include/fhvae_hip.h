@@ -616,6 +616,49 @@ int fhvae_mel_invert(const float* mel, int64_t n_frames, int64_t n_mels, int64_t
                      const float* bin_w, const int32_t* filt_first, const int32_t* filt_off, const float* filt_w, int64_t nnz,
                      float inv_l, const float* beta, int64_t n_iter, int flags, float* out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Kaldi filterbank features (csrc/kaldi_fbank.hip): compute-fbank-feats with snip-edges framing, for a batch of U
+ * utterances in one launch.  N = frame_len, S = frame_shift, P = padded_len = the smallest power of two >= N.
+ *   wave (n_samples) f32: the utterances' samples on the int16 scale, concatenated; wave_ptr (U+1) int64 their offsets.
+ *   frame_ptr (U+1) int64: output row offsets, frame_ptr[u+1] - frame_ptr[u] = 1 + (L - N) / S for an utterance of L >= N
+ *     samples; frame_ptr[0] = 0, frame_ptr[U] = n_frames.  Frame f of an utterance is its samples f*S .. f*S + N - 1.
+ *   Per frame, in this order: x[i] += dither * g(f, i); x -= mean(x) (FHVAE_KALDI_REMOVE_DC); x[i] -= preemph * x[i-1] for
+ *   i = N-1 .. 1, then x[0] -= preemph * x[0]; window and P-point DFT, power re^2 + im^2 of bins 0 .. P/2 - 1 (its square
+ *   root without FHVAE_KALDI_USE_POWER); out (n_frames, n_mels) = power . mel^T, with FHVAE_KALDI_USE_LOG
+ *   ln(max(., FLT_EPSILON)), the floor being the f32 nearest to ln 2^-23.
+ *   dft_basis (32*G, KP) f32, KP = N rounded up to 16, G = ceil((P/2) / 16): row 32g + i holds w[n] cos(2 pi n b / P) and row
+ *     32g + 16 + i holds -w[n] sin(2 pi n b / P) for bin b = 16g + i, n < N (zero for b >= P/2 and n >= N); w the window.
+ *   mel_basis (16*ceil(n_mels/16), 16*G) f32: row j = mel filter j over bins 0 .. P/2 - 1, zero-padded.  Both 16-byte aligned.
+ *   Dither noise g(f, i), only evaluated when dither != 0 (stream_ids may be NULL otherwise): Philox4x32-10 with
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (f, i / 4, stream_ids[u] & 0xffffffff, stream_ids[u] >> 32)      f = frame index within utterance u
+ *     round   : (c0, c1, c2, c3) <- (hi(0xCD9E8D57 * c2) ^ c1 ^ k0, lo(0xCD9E8D57 * c2), hi(0xD2511F53 * c0) ^ c3 ^ k1,
+ *               lo(0xD2511F53 * c0)), ten times, the key advancing by (0x9E3779B9, 0xBB67AE85) after each round
+ *     uniform : u(r) = (2 * (r >> 9) + 1) * 2^-24, in (0, 1), exact in f32
+ *     normals : the output words (r0, r1, r2, r3) give samples 4*(i/4) + 0 .. 3 as
+ *               sqrt(-2 ln u(r0)) * cos(2 pi u(r1)), sqrt(-2 ln u(r0)) * sin(2 pi u(r1)),
+ *               sqrt(-2 ln u(r2)) * cos(2 pi u(r3)), sqrt(-2 ln u(r2)) * sin(2 pi u(r3))     (f32 on the device)
+ *   so the noise of a sample depends on (seed, stream id, f, i) alone: overlapping frames do not share noise, and a
+ *   frame's features do not depend on the batch it is computed in.
+ *   1 <= S <= N, N >= 2 and P the smallest power of two >= N, otherwise FHVAE_ERR_SHAPE; P <= FHVAE_KALDI_MAX_P,
+ *   N <= FHVAE_KALDI_MAX_N (above it a 16-frame tile and its spectrum do not fit the LDS) and n_mels in
+ *   [1, FHVAE_FEATS_MAX_NMELS], otherwise FHVAE_ERR_LIMIT; all before any launch.  Pointers that break the framing rule
+ *   set FHVAE_KALDI_BAD_PTR in the int32 device word `status` (never cleared by the library) and nothing is written.
+ *   Every row is a fixed-order f32 chain over its own samples (bitwise independent of the batch).
+ * tile_rows: frames per workgroup for (N, P, n_mels); 0 = not supported.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_KALDI_REMOVE_DC 1
+#define FHVAE_KALDI_USE_LOG 2
+#define FHVAE_KALDI_USE_POWER 4
+#define FHVAE_KALDI_MAX_P 2048
+#define FHVAE_KALDI_MAX_N 1504
+#define FHVAE_KALDI_BAD_PTR 1
+int fhvae_kaldi_fbank_tile_rows(int64_t frame_len, int64_t padded_len, int64_t n_mels);
+int fhvae_kaldi_fbank_fwd(const float* wave, int64_t n_samples, const int64_t* wave_ptr, const int64_t* frame_ptr,
+                          const uint64_t* stream_ids, int64_t U, int64_t n_frames, const float* dft_basis,
+                          const float* mel_basis, int64_t frame_len, int64_t frame_shift, int64_t padded_len, int64_t n_mels,
+                          float preemph, float dither, uint64_t seed, int flags, float* out, int32_t* status, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

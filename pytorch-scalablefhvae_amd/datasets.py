@@ -7,8 +7,10 @@ Kept from the reference (same names, constructor arguments and return values):
   (`nseg = (len - seg_len) // seg_shift + 1`, :155-185), MVN statistics over the kept sequences (:225-235) and
   `apply_mvn` / `undo_mvn` (:100-105, :131-136).  `len(dataset)` is the number of SEQUENCES, as in the reference
   (:138-139) -- the train loop passes it to the model as `num_seqs` (train_model.py:448); `num_segments` is new.
-Not reproduced: `json.dump` of ndarrays in `_mvn_prep` (:111-112 raises TypeError; lists are written instead);
-KaldiDataset (needs the external kaldiio package: out of scope).
+  KaldiDataset (:238-274): the same constructor and `__getitem__` over a Kaldi feats.scp ("<key> <ark>:<offset>"); the
+  matrices are read by kaldi_io_lite.load_mat instead of the external kaldiio package.  Both classes load a sequence's
+  matrix through `load_seq(i)`, the only place where they differ.
+Not reproduced: `json.dump` of ndarrays in `_mvn_prep` (:111-112 raises TypeError; lists are written instead).
 
 New: `ResidentSegmentPool` loads every kept utterance once, concatenates them into one (frames, F) f32 tensor in HBM
 (288 GB hold ~900 M frames of 80-bin features) and cuts minibatches with the `fhvae_segment_gather` kernel
@@ -91,8 +93,8 @@ class NumpyDataset(torch.utils.data.Dataset):
         """Per-feature mean and standard deviation over all frames of the kept utterances: first and second moments are
         summed utterance by utterance in the arrays' own dtype, then std = sqrt(E[x^2] - mean^2) (datasets.py:225-235)."""
         frames, s1, s2 = 0.0, 0.0, 0.0
-        for path in self.feats.values():
-            a = np.load(path)
+        for i in range(len(self.seq_feats)):
+            a = self.load_seq(i)
             s1 = s1 + a.sum(axis=0, keepdims=True)
             s2 = s2 + np.square(a).sum(axis=0, keepdims=True)
             frames += a.shape[0]
@@ -119,6 +121,10 @@ class NumpyDataset(torch.utils.data.Dataset):
         p = self.mvn_params
         return feats if p is None else feats * p["std"] + p["mean"]
 
+    def load_seq(self, i):
+        """The whole (nframes, F) matrix of sequence `i`, as stored."""
+        return np.load(self.seq_feats[i])
+
     def __len__(self):
         return len(self.seqlist)  # number of sequences (datasets.py:138-139): the loop's num_seqs
 
@@ -130,10 +136,19 @@ class NumpyDataset(torch.utils.data.Dataset):
         """Returns sequence index, feature (seg_len, F) and the sequence's number of segments (datasets.py:214-223)."""
         seg = self.segs[index]
         idx = self.seq2idx[seg.seq]
-        with open(self.seq_feats[idx], "rb") as f:
-            feat = np.load(f)[seg.start:seg.end]
+        feat = self.load_seq(idx)[seg.start:seg.end]
         feat = self.apply_mvn(feat)
         return idx, feat, self.seq_nsegs[idx]
+
+
+class KaldiDataset(NumpyDataset):
+    """NumpyDataset over a Kaldi script file: feat_scp lines are "<key> <ark path>:<offset>" (binary archives of float
+    matrices, kaldi_io_lite); len_scp is feat-to-len's "<key> <nframes>" table (datasets.py:238-274 of the reference)."""
+
+    def load_seq(self, i):
+        from kaldi_io_lite import load_mat
+
+        return load_mat(self.seq_feats[i])
 
 
 def seq_csr(seq_nsegs, seg_seq):
@@ -148,14 +163,14 @@ def seq_csr(seq_nsegs, seg_seq):
 
 
 class ResidentSegmentPool:
-    """All utterances of a NumpyDataset resident in HBM + device-side minibatch cutting (fhvae_segment_gather)."""
+    """All utterances of a NumpyDataset (or KaldiDataset) resident in HBM + device-side minibatch cutting (fhvae_segment_gather)."""
 
     def __init__(self, dataset: NumpyDataset, device="cuda"):
         import hip_binding as hb
 
         self.hb = hb
         self.T = dataset.seg_len
-        feats = [np.load(p).astype(np.float32) for p in dataset.seq_feats]
+        feats = [dataset.load_seq(i).astype(np.float32) for i in range(len(dataset.seq_feats))]
         offs = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
         self.pool = torch.from_numpy(np.concatenate(feats, axis=0)).to(device)  # (frames, F), one H2D copy per split
         self.num_seqs = len(dataset)

@@ -35,6 +35,8 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Evaluate a trained (Simple)FHVAE checkpoint: latents, mu2, reconstructions, conversion")
     p.add_argument("--checkpoint", required=True)
     p.add_argument("--out", required=True, help="output directory (created)")
+    p.add_argument("--data-format", default="numpy", choices=["numpy", "kaldi"],
+                   help="what --feat-scp points at: .npy files or Kaldi archives (as train_model.py)")
     p.add_argument("--feat-scp", default=None)
     p.add_argument("--len-scp", default=None)
     p.add_argument("--min-len", type=int, default=None)
@@ -117,6 +119,10 @@ def main(argv=None) -> int:
         if args.feat_scp is None:
             print("--wav-out needs --feat-scp data (\"spec\" features)", file=sys.stderr)
             return 1
+        if args.data_format == "kaldi":
+            print("--wav-out: Kaldi fbank features are not the features the synthesis inverts (use --data-format numpy data)",
+                  file=sys.stderr)
+            return 1
         try:
             n_fft, _ = features.check_synth_params(args.sr, args.win_t, args.hop_t, args.gl_iters, 0.99, 0.97)
             if args.wav_ftype == "fbank" and args.nnls_iters < 1:
@@ -136,10 +142,11 @@ def main(argv=None) -> int:
     T = getattr(model, "seg_len", args.seg_len)
     undo = lambda a: a  # noqa: E731
     if args.feat_scp is not None:
-        from datasets import NumpyDataset, ResidentSegmentPool
+        from datasets import KaldiDataset, NumpyDataset, ResidentSegmentPool
 
-        ds = NumpyDataset(args.feat_scp, args.len_scp, args.min_len if args.min_len is not None else T, args.mvn_path, T,
-                          args.seg_shift, False)
+        Dataset = NumpyDataset if args.data_format == "numpy" else KaldiDataset
+        ds = Dataset(args.feat_scp, args.len_scp, args.min_len if args.min_len is not None else T, args.mvn_path, T,
+                     args.seg_shift, False)
         if args.wav_out is not None:
             cols = np.load(ds.seq_feats[0], mmap_mode="r").shape[1] if len(ds) else -1
             if args.wav_ftype == "fbank":

@@ -32,6 +32,15 @@ and for "fbank" features the step in front of it (csrc/melinv.hip: fhvae_mel_inv
                       spectrograms: non-negative least squares against mel_filters, a fixed number of FISTA steps from zero
   synthesize_mel      mel_to_spec, then synthesize on the device buffer
 
+and Kaldi's filterbank features (csrc/kaldi_fbank.hip: fhvae_kaldi_fbank_fwd), numerically a different feature from "fbank":
+
+  kaldi_fbank_options a Kaldi config file ("--name=value" lines) or a dict -> the full option set, Kaldi's defaults filled in
+  kaldi_frame_sizes / kaldi_num_frames
+                      N = int(sr * 0.001 * frame-length), S likewise, P = the power of two >= N; snip-edges frame count
+  kaldi_window / kaldi_mel_filters / kaldi_dft_basis / kaldi_mel_basis
+                      the symmetric window, the HTK mel triangles over bins 0 .. P/2 - 1 and the kernel's padded bases
+  compute_kaldi_fbank a list of waveforms -> a list of (nframes, num-mel-bins) float32 arrays (dither by Philox, reproducible)
+
 Utterances shorter than n_fft // 2 + 1 samples are an error (one reflection of the centre padding must suffice; numpy's
 repeated reflection for shorter inputs is not reproduced).
 """
@@ -50,8 +59,9 @@ BATCH_FRAMES = 1 << 17  # frames per synthesis batch (about 22 minutes at a 10 m
 
 
 # ---------------------------------------------------------------------------------------------------------- audio input
-def read_wav(path):
-    """-> (samples float32 (n,), sample rate).  Integer PCM only; anything else raises ValueError naming the file."""
+def read_wav(path, channel=None):
+    """-> (samples float32 (n,), sample rate).  Integer PCM only; anything else raises ValueError naming the file.
+    `channel`: take that channel of a multi-channel file instead of the channel mean (Kaldi reads channel 0)."""
     try:
         with _wave.open(str(path), "rb") as w:
             nch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
@@ -74,7 +84,9 @@ def read_wav(path):
     else:
         x = b.view("<i4").astype(np.float32) / float(1 << 31)
     x = x.reshape(n, nch)
-    y = x[:, 0] if nch == 1 else x.mean(axis=1, dtype=np.float32)
+    if channel is not None and not 0 <= channel < nch:
+        raise ValueError("%s: no channel %d in a file of %d channel(s)" % (path, channel, nch))
+    y = x[:, channel or 0] if nch == 1 or channel is not None else x.mean(axis=1, dtype=np.float32)
     return np.ascontiguousarray(y, dtype=np.float32), sr
 
 
@@ -923,4 +935,263 @@ def synthesize_mel(mels, sr, win_t=0.025, hop_t=0.010, n_mels=None, nnls_iters=N
         st = int(status.cpu().item())
         if st != 0:
             raise RuntimeError("fhvae_mel_invert: status %d (the band points outside its arrays)" % st)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------- Kaldi fbank
+# compute-fbank-feats (FbankOptions, FrameExtractionOptions, MelBanksOptions) with Kaldi's defaults.  Nothing here runs a
+# Kaldi binary: the arithmetic is restated in include/fhvae_hip.h and runs in csrc/kaldi_fbank.hip.
+KALDI_DEFAULTS = {
+    "sample-frequency": 16000.0, "frame-length": 25.0, "frame-shift": 10.0, "preemphasis-coefficient": 0.97,
+    "remove-dc-offset": True, "dither": 1.0, "window-type": "povey", "blackman-coeff": 0.42, "num-mel-bins": 23,
+    "low-freq": 20.0, "high-freq": 0.0, "use-log-fbank": True, "use-power": True, "htk-compat": False, "snip-edges": True,
+    "round-to-power-of-two": True, "use-energy": False, "energy-floor": 0.0, "raw-energy": True,
+}
+KALDI_WINDOWS = ("hamming", "hanning", "povey", "rectangular", "blackman")
+KALDI_FIXED = {"snip-edges": True, "round-to-power-of-two": True, "use-energy": False}  # the only values implemented
+KALDI_MAX_P = 2048  # FHVAE_KALDI_MAX_P
+KALDI_MAX_N = 1504  # FHVAE_KALDI_MAX_N
+KALDI_SYNTAX = "one option per line as --name=value (for example --num-mel-bins=80); blank lines and # comments are skipped"
+
+
+def _kaldi_bool(text):
+    t = str(text).strip().lower()
+    if t in ("true", "t", "1", ""):
+        return True
+    if t in ("false", "f", "0"):
+        return False
+    raise ValueError("not a boolean: %r" % (text,))
+
+
+def kaldi_fbank_options(source=None):
+    """The option set of Kaldi's compute-fbank-feats from a config file (path) or a dict of option names (dashes, as Kaldi
+    spells them) -> dict with every supported option, Kaldi's defaults filled in.  An unknown option, or a value that is not
+    implemented (use-energy=true, snip-edges=false, round-to-power-of-two=false, any vtln-* option), raises ValueError naming
+    the option and the file, as Kaldi dies on unknown options."""
+    where = "options"
+    given = {}
+    if source is None:
+        pass
+    elif isinstance(source, dict):
+        given = {str(k).lstrip("-").replace("_", "-"): v for k, v in source.items()}
+    else:
+        where = str(source)
+        try:
+            fh = open(where)
+        except OSError as e:
+            raise ValueError("%s: cannot read the Kaldi fbank configuration (%s); expected a text file with %s"
+                             % (where, e.strerror or e, KALDI_SYNTAX)) from None
+        with fh:
+            for ln, raw in enumerate(fh, 1):
+                line = raw.split("#", 1)[0].strip()
+                if not line:
+                    continue
+                if not line.startswith("--"):
+                    raise ValueError("%s:%d: %r is not an option; expected %s" % (where, ln, line, KALDI_SYNTAX))
+                name, _, value = line[2:].partition("=")
+                given[name.strip()] = value.strip()
+    opts = dict(KALDI_DEFAULTS)
+    for name, value in given.items():
+        if name.startswith("vtln-"):
+            raise ValueError("%s: option --%s is not supported (no VTLN warping)" % (where, name))
+        if name not in KALDI_DEFAULTS:
+            raise ValueError("%s: unknown option --%s (supported: %s)" % (where, name, ", ".join(sorted(KALDI_DEFAULTS))))
+        kind = type(KALDI_DEFAULTS[name])
+        try:
+            opts[name] = _kaldi_bool(value) if kind is bool and not isinstance(value, bool) else kind(value)
+        except ValueError:
+            raise ValueError("%s: option --%s has the value %r, not a %s" % (where, name, value, kind.__name__)) from None
+    for name, only in KALDI_FIXED.items():
+        if opts[name] != only:
+            raise ValueError("%s: option --%s=%s is not supported (only %s is implemented)"
+                             % (where, name, str(opts[name]).lower(), str(only).lower()))
+    if opts["window-type"] not in KALDI_WINDOWS:
+        raise ValueError("%s: option --window-type=%s is not one of %s" % (where, opts["window-type"], ", ".join(KALDI_WINDOWS)))
+    return opts
+
+
+def kaldi_frame_sizes(opts):
+    """(N, S, P): samples per frame and per shift by Kaldi's truncation int(sr * 0.001 * ms), and the FFT size, the smallest
+    power of two >= N."""
+    sr = opts["sample-frequency"]
+    N, S = int(sr * 0.001 * opts["frame-length"]), int(sr * 0.001 * opts["frame-shift"])
+    P = 1
+    while P < N:
+        P *= 2
+    return N, S, P
+
+
+def kaldi_num_frames(n, N, S):
+    """Frames of n samples with snip-edges=true: 0 if n < N, else 1 + (n - N) // S.  Works on arrays."""
+    n = np.asarray(n, dtype=np.int64)
+    out = np.where(n < N, 0, 1 + (n - N) // S)
+    return out if out.ndim else int(out)
+
+
+def kaldi_window(N, window="povey", blackman_coeff=0.42):
+    """Kaldi's FeatureWindowFunction, float64 (N,): symmetric (i / (N - 1)), unlike the periodic window of dft_basis."""
+    a = 2.0 * np.pi * np.arange(N) / (N - 1)
+    if window == "hamming":
+        return 0.54 - 0.46 * np.cos(a)
+    if window == "hanning":
+        return 0.5 - 0.5 * np.cos(a)
+    if window == "povey":
+        return (0.5 - 0.5 * np.cos(a)) ** 0.85
+    if window == "rectangular":
+        return np.ones(N)
+    if window == "blackman":
+        return blackman_coeff - 0.5 * np.cos(a) + (0.5 - blackman_coeff) * np.cos(2.0 * a)
+    raise ValueError("window type %r is not one of %s" % (window, ", ".join(KALDI_WINDOWS)))
+
+
+def kaldi_mel_filters(sr, P, n_mels, low=20.0, high=0.0):
+    """(n_mels, P // 2) float64: Kaldi's MelBanks without VTLN.  mel(f) = 1127 ln(1 + f / 700); n_mels + 2 points equally spaced
+    in mel from `low` to `high` (<= 0: added to the Nyquist frequency); filter b rises over (point b, point b+1] and falls
+    over (point b+1, point b+2) in the mel of the bin frequency i * sr / P; no area normalisation."""
+    nyquist = 0.5 * sr
+    hi = high if high > 0.0 else nyquist + high
+    if not (0.0 <= low < nyquist and 0.0 < hi <= nyquist and low < hi):
+        raise ValueError("low-freq %g / high-freq %g do not fit a Nyquist frequency of %g" % (low, high, nyquist))
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)  # noqa: E731
+    pts = mel(low) + (mel(hi) - mel(low)) / (n_mels + 1) * np.arange(n_mels + 2)
+    m = mel(np.arange(P // 2) * (float(sr) / P))[None, :]
+    left, centre, right = pts[:-2, None], pts[1:-1, None], pts[2:, None]
+    up, down = (m - left) / (centre - left), (right - m) / (right - centre)
+    return np.where((m > left) & (m <= centre), up, np.where((m > centre) & (m < right), down, 0.0))
+
+
+def _kaldi_padded(N, P):
+    return (N + 15) // 16 * 16, P // 2, (P // 2 + 15) // 16
+
+
+def kaldi_dft_basis(N, P, window="povey", blackman_coeff=0.42):
+    """The kernel's (32 * G, KP) f32 basis: row 32g + i = w[n] cos(2 pi n b / P), row 32g + 16 + i = -w[n] sin(...), for bin
+    b = 16g + i < P / 2 and n < N (zero elsewhere); w = kaldi_window.  Built in float64 with the phase reduced exactly."""
+    KP, n_bins, G = _kaldi_padded(N, P)
+    n = np.arange(N)
+    w = kaldi_window(N, window, blackman_coeff)
+    ph = 2.0 * np.pi * ((np.arange(n_bins)[:, None] * n[None, :]) % P) / P
+    c = np.zeros((16 * G, N))
+    s = np.zeros((16 * G, N))
+    c[:n_bins] = w * np.cos(ph)
+    s[:n_bins] = -w * np.sin(ph)
+    out = np.zeros((G, 2, 16, KP), dtype=np.float64)
+    out[:, 0, :, :N] = c.reshape(G, 16, N)
+    out[:, 1, :, :N] = s.reshape(G, 16, N)
+    return out.reshape(32 * G, KP).astype(np.float32)
+
+
+def kaldi_mel_basis(sr, P, n_mels, low=20.0, high=0.0):
+    """The kernel's (16 * ceil(n_mels / 16), 16 * G) f32 mel basis (kaldi_mel_filters, zero-padded)."""
+    _, n_bins, G = _kaldi_padded(1, P)
+    out = np.zeros(((n_mels + 15) // 16 * 16, 16 * G), dtype=np.float32)
+    out[:n_mels, :n_bins] = kaldi_mel_filters(sr, P, n_mels, low, high)
+    return out
+
+
+def check_kaldi_options(opts):
+    """-> (N, S, P) or ValueError for sizes the kernel does not take."""
+    N, S, P = kaldi_frame_sizes(opts)
+    if N < 2 or N > KALDI_MAX_N:
+        raise ValueError("frame-length gives %d samples per frame, outside [2, %d]" % (N, KALDI_MAX_N))
+    if not 1 <= S <= N:
+        raise ValueError("frame-shift gives %d samples, outside [1, %d] (the frame length)" % (S, N))
+    if not 1 <= opts["num-mel-bins"] <= MAX_NMELS:
+        raise ValueError("num-mel-bins = %d is outside [1, %d]" % (opts["num-mel-bins"], MAX_NMELS))
+    return N, S, P
+
+
+def kaldi_stream_id(key):
+    """The dither stream of an utterance key: zlib.crc32 of its UTF-8 bytes, so that a file's noise does not depend on its
+    place in a list."""
+    import zlib
+
+    return zlib.crc32(str(key).encode("utf-8"))
+
+
+class _KaldiBases:
+    """Device copies of the bases for one option set, built once per compute_kaldi_fbank call."""
+
+    def __init__(self, opts, N, P, device):
+        import torch
+
+        sr = opts["sample-frequency"]
+        self.dft = torch.from_numpy(kaldi_dft_basis(N, P, opts["window-type"], opts["blackman-coeff"])).to(device)
+        self.mel = torch.from_numpy(kaldi_mel_basis(sr, P, opts["num-mel-bins"], opts["low-freq"], opts["high-freq"])).to(device)
+
+
+def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device):
+    import torch
+
+    N, S, P = sizes
+    n_mels = opts["num-mel-bins"]
+    lens = np.array([len(w) for w in waves], dtype=np.int64)
+    wave_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    frame_ptr = np.concatenate([[0], np.cumsum(kaldi_num_frames(lens, N, S))]).astype(np.int64)
+    host = torch.empty(int(wave_ptr[-1]), dtype=torch.float32, pin_memory=True)
+    np.concatenate(waves, out=host.numpy())
+    host.mul_(32768.0)  # Kaldi's int16 scale (exact: a power of two)
+    wave_d = host.to(device, non_blocking=True)
+    ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).pin_memory().to(device, non_blocking=True)
+    dither = float(opts["dither"])
+    ids_d = torch.from_numpy(np.asarray(ids, dtype=np.uint64).view(np.int64).copy()).to(device) if dither != 0.0 else None
+    out = torch.empty((int(frame_ptr[-1]), n_mels), dtype=torch.float32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    flags = ((hb.KALDI_REMOVE_DC if opts["remove-dc-offset"] else 0) | (hb.KALDI_USE_LOG if opts["use-log-fbank"] else 0)
+             | (hb.KALDI_USE_POWER if opts["use-power"] else 0))
+    hb.kaldi_fbank_fwd(wave_d, ptrs_d[0], ptrs_d[1], ids_d, bases.dft, bases.mel, N, S, P, n_mels,
+                       opts["preemphasis-coefficient"], dither, seed, flags, out, status)
+    res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
+    res.copy_(out, non_blocking=True)
+    st = status.cpu()  # (synchronises: the copy above is done too)
+    if int(st.item()) != 0:
+        raise RuntimeError("fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)" % int(st.item()))
+    r = res.numpy()
+    return [r[frame_ptr[j]:frame_ptr[j + 1]].copy() for j in range(len(waves))]
+
+
+def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, device="cuda", max_samples=BATCH_SAMPLES,
+                        rates=None):
+    """Kaldi filterbank features of every waveform -> list of float32 (nframes, num-mel-bins), in input order.  `waves` are
+    float32 1-D arrays as read_wav returns them (full scale 1.0; they are put on Kaldi's int16 scale here) at the rate
+    sample-frequency of `opts` (what kaldi_fbank_options takes: a config file, a dict, or None for Kaldi's defaults).  `seed` and `stream_ids` (one 64-bit
+    integer per waveform, default its index) select the dither noise, which depends on nothing else: the same
+    (seed, stream id) gives the same features in any batch.  `rates` (optional, one source rate per waveform): waveforms at
+    another rate are first converted with `resample`; without it every waveform is taken to be at sample-frequency, as
+    Kaldi refuses other rates.  An utterance shorter than one frame is an error that names it (`names`)."""
+    opts = kaldi_fbank_options(opts)
+    sizes = check_kaldi_options(opts)
+    sr = opts["sample-frequency"]
+    if sr != int(sr):
+        raise ValueError("sample-frequency %r is not a whole number of Hz" % (sr,))
+    kaldi_mel_filters(sr, sizes[2], opts["num-mel-bins"], opts["low-freq"], opts["high-freq"])  # (bad band edges fail here)
+    waves = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in waves]
+    names = list(names) if names is not None else ["utterance %d" % j for j in range(len(waves))]
+    ids = list(range(len(waves))) if stream_ids is None else [int(v) & 0xFFFFFFFFFFFFFFFF for v in stream_ids]
+    if len(ids) != len(waves) or len(names) != len(waves):
+        raise ValueError("stream_ids / names must have one entry per waveform (%d)" % len(waves))
+    if rates is not None:
+        if len(rates) != len(waves):
+            raise ValueError("rates has %d entries for %d waveforms" % (len(rates), len(waves)))
+        groups = {}
+        for j, r in enumerate(rates):
+            if int(r) != int(sr):
+                groups.setdefault(int(r), []).append(j)
+        for r in groups:
+            resample_bank(r, int(sr))  # (an unsupported ratio fails before any work)
+        for r, idx in groups.items():
+            for j, y in zip(idx, resample([waves[j] for j in idx], r, int(sr), device, max_samples)):
+                waves[j] = y
+    for j, w in enumerate(waves):
+        if len(w) < sizes[0]:
+            raise ValueError("%s: %d samples%s; one frame needs %d (Kaldi would skip the utterance)"
+                             % (names[j], len(w), " after resampling" if rates is not None else "", sizes[0]))
+    if not waves:
+        return []
+    import hip_binding as hb
+
+    bases = _KaldiBases(opts, sizes[0], sizes[2], device)
+    out = []
+    for a, b in batches([len(w) for w in waves], max_samples):
+        out.extend(_kaldi_batch(hb, waves[a:b], ids[a:b], opts, sizes, int(seed), bases, device))
     return out

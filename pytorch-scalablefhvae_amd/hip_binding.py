@@ -137,6 +137,9 @@ SIGNATURES = {
     "fhvae_mu2_merge_load_shard": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp]),
     "fhvae_feats_tile_rows": (C.c_int, [_i64, C.c_int]),
     "fhvae_feats_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
+    "fhvae_kaldi_fbank_tile_rows": (C.c_int, [_i64, _i64, _i64]),
+    "fhvae_kaldi_fbank_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, C.c_float, C.c_float,
+                                        C.c_uint64, C.c_int, _vp, _vp, _vp]),
     "fhvae_synth_tile_rows": (C.c_int, [_i64]),
     "fhvae_synth_istft": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_synth_project": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.c_float, _i64, _i64, _vp, _vp, _vp, _vp]),
@@ -1414,6 +1417,44 @@ def feats_fwd(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, n_fft, hop, n_mel
         _check(lib.fhvae_feats_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
                                    _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status),
                                    _stream()), "fhvae_feats_fwd")
+
+
+KALDI_REMOVE_DC, KALDI_USE_LOG, KALDI_USE_POWER = 1, 2, 4  # FHVAE_KALDI_*
+KALDI_BAD_PTR = 1  # FHVAE_KALDI_BAD_PTR
+
+
+def kaldi_fbank_fwd(wave, wave_ptr, frame_ptr, stream_ids, dft_basis, mel_basis, frame_len, frame_shift, padded_len, n_mels,
+                    preemph, dither, seed, flags, out, status):
+    """Kaldi fbank features of a batch of utterances in one launch (fhvae_kaldi_fbank_fwd): wave (n_samples,) f32 samples on
+    the int16 scale, wave_ptr / frame_ptr (U+1,) int64, stream_ids (U,) int64 holding the 64-bit stream ids (None when
+    dither is 0), dft_basis / mel_basis in the header's padded layouts, out (frame_ptr[U], n_mels) f32, status (1,) int32
+    (KALDI_BAD_PTR when the pointers break the snip-edges framing rule)."""
+    _need_gpu(wave, wave_ptr, frame_ptr, stream_ids, dft_basis, mel_basis, out, status)
+    for t in (wave, dft_basis, mel_basis, out):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("kaldi_fbank_fwd takes contiguous f32 samples, bases and output")
+    for t in (wave_ptr, frame_ptr) + ((stream_ids,) if stream_ids is not None else ()):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise RuntimeError("kaldi_fbank_fwd takes contiguous int64 wave_ptr / frame_ptr / stream_ids")
+    if status.dtype != torch.int32 or status.numel() != 1 or wave_ptr.shape != frame_ptr.shape or out.dim() != 2:
+        raise RuntimeError("kaldi_fbank_fwd: status must be one int32 word, wave_ptr / frame_ptr the same length and out 2-D")
+    U = wave_ptr.shape[0] - 1
+    if dither != 0 and (stream_ids is None or stream_ids.shape[0] != U):
+        raise RuntimeError("kaldi_fbank_fwd: dither needs one stream id per utterance")
+    G = (padded_len // 2 + 15) // 16  # 16-bin groups
+    if tuple(dft_basis.shape) != (32 * G, (frame_len + 15) // 16 * 16):
+        raise RuntimeError("kaldi_fbank_fwd: dft_basis must be (%d, %d) for a frame of %d samples padded to %d"
+                           % (32 * G, (frame_len + 15) // 16 * 16, frame_len, padded_len))
+    if tuple(mel_basis.shape) != ((n_mels + 15) // 16 * 16, 16 * G):
+        raise RuntimeError("kaldi_fbank_fwd: mel_basis must be (%d, %d)" % ((n_mels + 15) // 16 * 16, 16 * G))
+    if out.shape[1] != n_mels:
+        raise RuntimeError("kaldi_fbank_fwd: out has %d columns for %d mel bins" % (out.shape[1], n_mels))
+    lib = load_library()
+    with _Timed("fhvae_kaldi_fbank_fwd"):
+        _check(lib.fhvae_kaldi_fbank_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), _p(stream_ids), U, out.shape[0],
+                                         _p(dft_basis), _p(mel_basis), frame_len, frame_shift, padded_len, n_mels, float(preemph),
+                                         float(dither), int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), _p(out), _p(status), _stream()),
+               "fhvae_kaldi_fbank_fwd")
 
 
 RESAMPLE_BAD_PTR = 1  # FHVAE_RESAMPLE_BAD_PTR

@@ -1,0 +1,156 @@
+"""prepare_kaldi_data.py -- WAV files listed in wav.scp -> Kaldi filterbank features in the Kaldi layout the loaders read
+(the reference's prepare_kaldi_data.py:10-136, with compute-fbank-feats and feat-to-len replaced by
+features.compute_kaldi_fbank on the MI355X and kaldi_io_lite; no Kaldi binary is run).
+
+    python pytorch-scalablefhvae_amd/prepare_kaldi_data.py DATASET_DIR [--fbank_conf ./misc/fbank.conf] [--set_name train]
+        [--seed 0] [--resample]
+
+For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<key> <path>"
+lines) and writes, in wav.scp order, <DATASET_DIR>/<set>/feats.ark (binary archive of float32 matrices), feats.scp
+("<key> <feats.ark>:<offset>") and len.scp ("<key> <nframes>").  --fbank_conf is a Kaldi config file the user supplies,
+one option per line, for example
+
+    --window-type=hamming
+    --sample-frequency=16000
+    --dither=1
+    --num-mel-bins=80
+
+(features.kaldi_fbank_options lists what is supported).
+
+Differences from the reference:
+  * --kaldi_root is accepted and ignored.
+  * dither noise comes from a counter-based generator keyed by --seed and zlib.crc32 of the utterance key, so a file's
+    features are reproducible and do not depend on its place in wav.scp (Kaldi's rand() stream is neither).
+  * only plain "<key> <path>" entries: a line ending in "|" (a Kaldi pipe) is refused.  Integer PCM WAV only.
+  * a multi-channel file contributes channel 0, as Kaldi reads it (prepare_numpy_data.py averages the channels).
+  * a file whose rate differs from sample-frequency is an error, as in Kaldi, unless --resample converts it on the GPU
+    (features.resample); a file shorter than one frame is an error that names it (Kaldi skips it with a warning).
+"""
+from __future__ import annotations
+
+import argparse
+import concurrent.futures as cf
+import os
+import sys
+import time
+from pathlib import Path
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)
+
+import features  # noqa: E402
+import kaldi_io_lite  # noqa: E402
+
+READ_THREADS = 8  # file reads overlapping the GPU work (of the 16 CPUs a job gets; not sized by os.cpu_count())
+CHUNK_FILES = 512  # files read ahead of the batch being computed
+
+
+def read_wav_scp(path):
+    entries = []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            if not line.strip():
+                continue
+            parts = line.rstrip().split(None, 1)
+            if len(parts) != 2:
+                raise ValueError("%s:%d: expected \"<key> <path>\"" % (path, ln))
+            if parts[1].endswith("|"):
+                raise ValueError("%s:%d: %s is a piped entry (\"... |\"); only plain WAV paths are supported: run the command "
+                                 "and list its output file" % (path, ln, parts[0]))
+            entries.append((parts[0], parts[1]))
+    return entries
+
+
+def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None):
+    """prepare_kaldi_data.py:10-82: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
+    Returns (count, (dataset_dir, feats.ark, feats.scp, len.scp)).  `timings` (optional dict) receives seconds spent in
+    "read", "gpu" and "write"."""
+    opts = features.kaldi_fbank_options(fbank_conf)
+    sr = int(opts["sample-frequency"])
+    set_dir = Path(dataset_dir) / set_name
+    wav_path = set_dir / "wav.scp"
+    if not os.path.exists(wav_path):
+        raise ValueError(f"The wav.scp file at {wav_path} does not exist!")
+    feat_ark, feat_scp, len_scp = set_dir / "feats.ark", set_dir / "feats.scp", set_dir / "len.scp"
+    entries = read_wav_scp(wav_path)
+    t = {} if timings is None else timings
+    for k in ("read", "gpu", "write"):
+        t.setdefault(k, 0.0)
+    start_time = time.time()
+    lens = []
+
+    def load(entry):
+        key, path = entry
+        y, rate = features.read_wav(path, channel=0)
+        return key, path, y, rate
+
+    def items():
+        chunks = [entries[i:i + CHUNK_FILES] for i in range(0, len(entries), CHUNK_FILES)]
+        with cf.ThreadPoolExecutor(max_workers=READ_THREADS) as pool:
+            pending = [pool.submit(load, e) for e in chunks[0]] if chunks else []
+            for ci in range(len(chunks)):
+                t0 = time.time()
+                got = [f.result() for f in pending]
+                t["read"] += time.time() - t0
+                # the next chunk's files are read while this one is on the GPU and being written
+                pending = [pool.submit(load, e) for e in chunks[ci + 1]] if ci + 1 < len(chunks) else []
+                if not resample:
+                    for key, path, _, rate in got:
+                        if rate != sr:
+                            raise ValueError(f"{key} ({path}): sample rate {rate} differs from sample-frequency {sr} of "
+                                             f"{fbank_conf} (convert the file or pass --resample)")
+                t0 = time.time()
+                feats = features.compute_kaldi_fbank([g[2] for g in got], opts, seed=seed,
+                                                     stream_ids=[features.kaldi_stream_id(g[0]) for g in got],
+                                                     names=["%s (%s)" % (g[0], g[1]) for g in got],
+                                                     rates=[g[3] for g in got] if resample else None)
+                dt = time.time() - t0
+                t["gpu"] += dt
+                t0 = time.time()
+                for g, feat in zip(got, feats):
+                    lens.append((g[0], len(feat)))
+                    yield g[0], feat
+                    if len(lens) % 1000 == 0:
+                        print(f"{len(lens)} {set_name} files in {time.time() - start_time} seconds.")
+                t["write"] += time.time() - t0
+
+    count = kaldi_io_lite.write_ark_scp(str(feat_ark), str(feat_scp), items())
+    kaldi_io_lite.write_len_scp(len_scp, lens)
+    print(f"Processed {count} files in {set_name} set over {time.time() - start_time} seconds.")
+    return count, (Path(dataset_dir), feat_ark, feat_scp, len_scp)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("dataset_dir", type=str, help="Directory containing subdirectories with wav.scp files")
+    p.add_argument("--fbank_conf", type=str, default="./misc/fbank.conf", help="Kaldi fbank configuration")
+    p.add_argument("--kaldi_root", type=str, default=None, help="Kaldi root directory (ignored: no Kaldi binary is run)")
+    p.add_argument("--set_name", type=str, default=None, help="Set {train, dev, test} to operate on. Leave blank for all three")
+    p.add_argument("--seed", type=int, default=0, help="Seed of the dither noise")
+    p.add_argument("--resample", action="store_true",
+                   help="Convert files whose rate differs from the configuration's sample-frequency on the GPU")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    print(args)
+    if args.kaldi_root is not None:
+        print("--kaldi_root is ignored: the features are computed on the GPU, no Kaldi binary is run")
+    sets = ["train", "dev", "test"] if args.set_name is None else [args.set_name]
+    t0 = time.time()
+    total = 0
+    try:
+        for s in sets:
+            total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample)[0]
+    except ValueError as e:
+        print("prepare_kaldi_data: %s" % e, file=sys.stderr)
+        return 1
+    if len(sets) > 1:
+        print(f"Processed {total} files in {time.time() - t0} seconds.")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

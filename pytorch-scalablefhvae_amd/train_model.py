@@ -72,6 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dev-segments", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     # real features in the reference's on-disk format (feats.scp / len.scp of .npy files, prepare_numpy_data.py:115-119)
+    p.add_argument("--data-format", default="numpy", choices=["numpy", "kaldi"],              # train_model.py:38-43
+                   help="what the feat-scp files point at: .npy files (prepare_numpy_data.py) or Kaldi archives "
+                        "(prepare_kaldi_data.py, or any Kaldi recipe's uncompressed feats.scp)")
     p.add_argument("--train-feat-scp", default=None)
     p.add_argument("--train-len-scp", default=None)
     p.add_argument("--dev-feat-scp", default=None)
@@ -175,12 +178,13 @@ def _train(args, device, world: int, rank: int) -> int:
     T, F = args.seg_len, args.mels
     real = args.train_feat_scp is not None
     if real:
-        from datasets import NumpyDataset, ResidentSegmentPool
+        from datasets import KaldiDataset, NumpyDataset, ResidentSegmentPool
 
+        Dataset = NumpyDataset if args.data_format == "numpy" else KaldiDataset  # train_model.py:371-374
         min_len = args.min_len if args.min_len is not None else T  # train_model.py:267-268
-        tr_ds = NumpyDataset(args.train_feat_scp, args.train_len_scp, min_len, args.mvn_path, T, args.seg_shift, args.rand_seg)
-        dv_ds = NumpyDataset(args.dev_feat_scp or args.train_feat_scp, args.dev_len_scp or args.train_len_scp, min_len,
-                             args.mvn_path, T, args.seg_shift, False)
+        tr_ds = Dataset(args.train_feat_scp, args.train_len_scp, min_len, args.mvn_path, T, args.seg_shift, args.rand_seg)
+        dv_ds = Dataset(args.dev_feat_scp or args.train_feat_scp, args.dev_len_scp or args.train_len_scp, min_len,
+                        args.mvn_path, T, args.seg_shift, False)
         tr_pool, dv_pool = ResidentSegmentPool(tr_ds, device), ResidentSegmentPool(dv_ds, device)
         F = tr_pool.pool.shape[1]
         S = len(tr_ds)  # len(train_loader.dataset), train_model.py:448
