@@ -7,9 +7,8 @@
 // then log and the floor.  A workgroup takes BM = 16*TM consecutive output rows (frames); a tile may span utterances, each
 // row finds its utterance by binary search in frame_ptr.  Pre-emphasis and the reflection of the centre padding are applied
 // while the tile is gathered into LDS (one row per frame, KP = n_fft rounded up to 16, zero-filled).  Each wave owns whole
-// 16-bin groups (16 cos + 16 sin basis rows) for all BM rows: the basis fragment a lane loads is reused over the TM row
-// tiles in registers, and no two waves read the same basis rows, so the basis goes from L2 straight into registers (one
-// 16-k chunk ahead) instead of through LDS.  The magnitudes go to LDS for the mel product (same scheme, 16-mel groups).
+// 16-bin groups (16 cos + 16 sin basis rows) for all BM rows and multiplies them by the shared row-tile product
+// (audio_tile.h: tile_product).  The magnitudes go to LDS for the mel product (same product, 16-mel groups).
 //
 // Every output element is a fixed-order f32 chain over its own row's samples (chunk, then k-step, then lane group: the MFMA
 // order), so a frame's result does not depend on the other frames of its launch or its place in the tile: bitwise.
@@ -17,13 +16,13 @@
 // Pointer errors: a check kernel validates wave_ptr / frame_ptr against the framing rule and sets FHVAE_FEATS_BAD_PTR; the
 // main kernel then writes nothing.  It also re-checks the utterance of every row it gathers, so no input makes it read or
 // write out of bounds.
-#include "common.h"
+#include "audio_tile.h"
 
 namespace fh {
 
 constexpr int kFeatThreads = 256;  // 4 waves
 constexpr int kFeatMaxBM = 64;
-constexpr int kFeatLdsBytes = 163840;  // 160 KiB per CU on gfx950; one workgroup may use all of it
+using FeatTm = TmSet<4, 2, 1>;
 
 __host__ __device__ inline int64_t feats_frames(int64_t L, int64_t n_fft, int64_t hop) {
   const int64_t pad = n_fft / 2;
@@ -41,21 +40,6 @@ __global__ void feats_check_kernel(const int64_t* __restrict__ wave_ptr, const i
   if (u == 0) ok = ok && f0 == 0;
   if (u == U - 1) ok = ok && f1 == n_frames;
   if (!ok) atomicOr(status, FHVAE_FEATS_BAD_PTR);
-}
-
-// acc[t] += B-fragment . A-fragment over one 16-k chunk (SWAP order: lane (i, q) ends with rows 4q..4q+3 of the B side
-// (bins / mels) for column i (frame i of the row tile))
-template <int TM>
-__device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[TM], const uint4& b, const uint4 (&a)[TM]) {
-  const float bs[4] = {__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      const float as = s == 0 ? __uint_as_float(a[t].x) : s == 1 ? __uint_as_float(a[t].y) : s == 2 ? __uint_as_float(a[t].z) : __uint_as_float(a[t].w);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bs[s], as, acc[t], 0, 0, 0);
-    }
-  }
 }
 
 // FBANK: 1 = log-mel, 0 = log-magnitude spectrogram.  LDS: frames [BM][LDA] (LDA = KP + 4: row stride an odd multiple of
@@ -85,11 +69,7 @@ __global__ void __launch_bounds__(kFeatThreads) feats_kernel(const float* __rest
     int ok = 0;
     int64_t base = 0, start = 0, L = 0;
     if (f < n_frames) {
-      int64_t lo = 0, hi = U - 1;  // last u with frame_ptr[u] <= f
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (frame_ptr[mid] <= f) lo = mid; else hi = mid - 1;
-      }
+      const int64_t lo = last_le(frame_ptr, U, f);
       const int64_t w0 = wave_ptr[lo], w1 = wave_ptr[lo + 1], p0 = frame_ptr[lo], p1 = frame_ptr[lo + 1];
       L = w1 - w0;
       ok = w0 >= 0 && w1 <= n_samples && L >= pad + 1 && p0 <= f && f < p1 && p1 - p0 == feats_frames(L, n_fft, hop);
@@ -123,29 +103,11 @@ __global__ void __launch_bounds__(kFeatThreads) feats_kernel(const float* __rest
   const int NC = KP / 16;
   // ---- DFT: wave w takes bin groups w, w+4, ...
   for (int g = wave_id; g < G; g += 4) {
-    f32x4 ac[TM], as[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ac[t] = as[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2][TM] = {};
     const float* bc = dft + (int64_t)(32 * g + i) * KP + 4 * q;
-    const float* bsn = bc + (int64_t)16 * KP;
-    const float* ar = A + i * LDA + 4 * q;
-    uint4 nc = *(const uint4*)bc, ns = *(const uint4*)bsn, na[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA);
-    for (int c = 0; c < NC; ++c) {
-      const uint4 cc = nc, cs = ns;
-      uint4 ca[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) ca[t] = na[t];
-      if (c + 1 < NC) {  // next chunk's fragments before this chunk's products
-        nc = *(const uint4*)(bc + 16 * (c + 1));
-        ns = *(const uint4*)(bsn + 16 * (c + 1));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * (c + 1));
-      }
-      mfma_chunk<TM>(ac, cc, ca);
-      mfma_chunk<TM>(as, cs, ca);
-    }
+    const float* const bcs[2] = {bc, bc + (int64_t)16 * KP};
+    tile_product<TM, 2>(acc, bcs, A + i * LDA + 4 * q, LDA, 0, NC, 1);
+    const auto &ac = acc[0], &as = acc[1];
     // lane (i, q): bins 16g + 4q + v of tile row 16t + i
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -172,26 +134,10 @@ __global__ void __launch_bounds__(kFeatThreads) feats_kernel(const float* __rest
     // ---- mel: M[r][j] = sum over bins of mag[r][bin] * mel[j][bin]; wave w takes mel groups w, w+4, ...
     const int H = (n_out + 15) / 16, NCM = NBP / 16;
     for (int h = wave_id; h < H; h += 4) {
-      f32x4 acc[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* br = melb + (int64_t)(16 * h + i) * NBP + 4 * q;
-      const float* mr = Ms + i * LDM + 4 * q;
-      uint4 nb = *(const uint4*)br, na[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(mr + t * 16 * LDM);
-      for (int c = 0; c < NCM; ++c) {
-        const uint4 cb = nb;
-        uint4 ca[TM];
-#pragma unroll
-        for (int t = 0; t < TM; ++t) ca[t] = na[t];
-        if (c + 1 < NCM) {
-          nb = *(const uint4*)(br + 16 * (c + 1));
-#pragma unroll
-          for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(mr + t * 16 * LDM + 16 * (c + 1));
-        }
-        mfma_chunk<TM>(acc, cb, ca);
-      }
+      f32x4 accm[1][TM] = {};
+      const float* const br[1] = {melb + (int64_t)(16 * h + i) * NBP + 4 * q};
+      tile_product<TM, 1>(accm, br, Ms + i * LDM + 4 * q, LDM, 0, NCM, 1);
+      const auto& acc = accm[0];
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         const int r = 16 * t + i;
@@ -215,22 +161,7 @@ static inline int64_t feats_smem(int BM, int64_t n_fft, bool fbank) {
 constexpr int64_t kFeatStaticLds = kFeatMaxBM * (3 * 8 + 4);
 
 static inline int feats_tm(int64_t n_fft, bool fbank) {
-  for (int tm = 4; tm >= 1; tm >>= 1)
-    if (feats_smem(16 * tm, n_fft, fbank) + kFeatStaticLds <= kFeatLdsBytes) return tm;
-  return 0;
-}
-
-template <int TM, bool FBANK>
-static int feats_launch(const float* wave, const int64_t* wave_ptr, const int64_t* frame_ptr, int64_t U, int64_t n_samples,
-                        int64_t n_frames, const float* dft, const float* melb, int n_fft, int hop, int n_out, float* out,
-                        const int32_t* status, hipStream_t s) {
-  const int64_t smem = feats_smem(16 * TM, n_fft, FBANK);
-  auto fn = feats_kernel<TM, FBANK>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(n_frames, 16 * TM)), dim3(kFeatThreads), (size_t)smem, s, wave, wave_ptr,
-                     frame_ptr, U, n_samples, n_frames, dft, melb, n_fft, hop, n_out, out, status);
-  return fh_launch_status();
+  return FeatTm::largest(kCuLdsBytes, [&](int BM) { return feats_smem(BM, n_fft, fbank) + kFeatStaticLds; });
 }
 
 }  // namespace fh
@@ -272,13 +203,10 @@ extern "C" int fhvae_feats_fwd(const float* wave, int64_t n_samples, const int64
                      n_frames, n_fft, hop, status);
   int rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
-  const int nf = (int)n_fft, hp = (int)hop;
-  if (fbank) {
-    if (tm == 4) return feats_launch<4, true>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mel_basis, nf, hp, n_out, out, status, s);
-    if (tm == 2) return feats_launch<2, true>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mel_basis, nf, hp, n_out, out, status, s);
-    return feats_launch<1, true>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mel_basis, nf, hp, n_out, out, status, s);
-  }
-  if (tm == 4) return feats_launch<4, false>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, nullptr, nf, hp, n_out, out, status, s);
-  if (tm == 2) return feats_launch<2, false>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, nullptr, nf, hp, n_out, out, status, s);
-  return feats_launch<1, false>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, nullptr, nf, hp, n_out, out, status, s);
+  return FeatTm::dispatch(tm, [&](auto tmc) {
+    constexpr int TM = decltype(tmc)::value;
+    return launch_lds(fbank ? feats_kernel<TM, true> : feats_kernel<TM, false>, fh_cdiv(n_frames, 16 * TM), kFeatThreads,
+                      feats_smem(16 * TM, n_fft, fbank), s, wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis,
+                      fbank ? mel_basis : nullptr, (int)n_fft, (int)hop, n_out, out, status);
+  });
 }

@@ -2,9 +2,9 @@
 // per-frame DC removal, in-frame pre-emphasis, window, P-point power spectrum, HTK mel triangles, log (the features the
 // reference gets by shelling out to Kaldi, prepare_kaldi_data.py:38-73).
 //
-// Same structure as feats.hip: a workgroup takes BM = 16*TM consecutive output rows (frames; a tile may span utterances,
-// each row finds its utterance by binary search in frame_ptr), gathers them into LDS and runs two dense products on the
-// exact-f32 MFMA (v_mfma_f32_16x16x4_f32):
+// The scheme of audio_tile.h: a workgroup takes BM = 16*TM consecutive output rows (frames; a tile may span utterances,
+// each row finds its utterance by binary search in frame_ptr), gathers them into LDS and runs two dense products
+// (tile_product) on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32):
 //   DFT:  [c | s] = frame (1 x KP) . basis^T      basis rows = window * cos / -sin of the P-point DFT over the N non-zero
 //                                                 columns (host-built, f64 -> f32), bins 0 .. P/2 - 1
 //   mel:  M = (c^2 + s^2) (1 x NBP) . mel^T
@@ -12,9 +12,7 @@
 // samples: one Philox4x32-10 block gives their 4 normals), adds the dither noise, writes them to LDS and sums them (lane
 // partial sums in quad order, then the xor butterfly: a fixed order).  Pass 2 reads each lane's own quads back, subtracts
 // the mean, applies x[i] -= c x[i-1] with the left neighbour from the lane below (__shfl_up; the quad before lane 0's comes
-// from the previous 64-quad round) and x[0] -= c x[0], and writes the row in place.  Each wave owns whole 16-bin groups for
-// all BM rows: the basis goes from L2 straight to registers one 16-k chunk ahead, LDS rows have a stride of KP + 4 floats
-// (an odd multiple of 16 bytes).
+// from the previous 64-quad round) and x[0] -= c x[0], and writes the row in place.
 //
 // Every output element is a fixed-order f32 chain over its own frame, so a frame's result does not depend on the other
 // frames of its launch or its place in the tile: bitwise.  The noise is a function of (seed, stream id of the utterance,
@@ -25,13 +23,13 @@
 // write out of bounds.
 #include <float.h>
 
-#include "common.h"
+#include "audio_tile.h"
 
 namespace fh {
 
 constexpr int kKfThreads = 256;  // 4 waves
 constexpr int kKfMaxBM = 64;
-constexpr int kKfLdsBytes = 163840;  // 160 KiB per CU on gfx950; one workgroup may use all of it
+using KfTm = TmSet<4, 3, 2, 1>;
 
 __host__ __device__ inline int64_t kaldi_frames(int64_t L, int64_t N, int64_t S) { return L < N ? 0 : 1 + (L - N) / S; }
 
@@ -69,21 +67,6 @@ __device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& z0, 
   sincospif(2.0f * u2, &sn, &cs);
   z0 = rad * cs;
   z1 = rad * sn;
-}
-
-// acc[t] += B-fragment . A-fragment over one 16-k chunk (SWAP order: lane (i, q) ends with rows 4q..4q+3 of the B side
-// (bins / mels) for column i (frame i of the row tile))
-template <int TM>
-__device__ __forceinline__ void kf_mfma_chunk(f32x4 (&acc)[TM], const uint4& b, const uint4 (&a)[TM]) {
-  const float bs[4] = {__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      const float as = s == 0 ? __uint_as_float(a[t].x) : s == 1 ? __uint_as_float(a[t].y) : s == 2 ? __uint_as_float(a[t].z) : __uint_as_float(a[t].w);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bs[s], as, acc[t], 0, 0, 0);
-    }
-  }
 }
 
 struct KaldiFbankArgs {
@@ -124,11 +107,7 @@ __global__ void __launch_bounds__(kKfThreads) kaldi_fbank_kernel(const KaldiFban
     uint32_t fi = 0;
     uint64_t sid = 0;
     if (f < a.n_frames) {
-      int64_t lo = 0, hi = a.U - 1;  // last u with frame_ptr[u] <= f
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (a.frame_ptr[mid] <= f) lo = mid; else hi = mid - 1;
-      }
+      const int64_t lo = last_le(a.frame_ptr, a.U, f);
       const int64_t w0 = a.wave_ptr[lo], w1 = a.wave_ptr[lo + 1], p0 = a.frame_ptr[lo], p1 = a.frame_ptr[lo + 1];
       const int64_t L = w1 - w0;
       // p1 - p0 == frames(L) and f < p1 keep (f - p0) * S + N <= L: the frame lies inside its utterance
@@ -201,29 +180,11 @@ __global__ void __launch_bounds__(kKfThreads) kaldi_fbank_kernel(const KaldiFban
   const int NC = KP / 16;
   // ---- DFT: wave w takes bin groups w, w+4, ...
   for (int g = wave_id; g < G; g += 4) {
-    f32x4 ac[TM], as[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ac[t] = as[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2][TM] = {};
     const float* bc = a.dft + (int64_t)(32 * g + i) * KP + 4 * q;
-    const float* bsn = bc + (int64_t)16 * KP;
-    const float* ar = A + i * LDA + 4 * q;
-    uint4 nc = *(const uint4*)bc, ns = *(const uint4*)bsn, na[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA);
-    for (int ch = 0; ch < NC; ++ch) {
-      const uint4 cc = nc, cs = ns;
-      uint4 ca[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) ca[t] = na[t];
-      if (ch + 1 < NC) {  // next chunk's fragments before this chunk's products
-        nc = *(const uint4*)(bc + 16 * (ch + 1));
-        ns = *(const uint4*)(bsn + 16 * (ch + 1));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * (ch + 1));
-      }
-      kf_mfma_chunk<TM>(ac, cc, ca);
-      kf_mfma_chunk<TM>(as, cs, ca);
-    }
+    const float* const bcs[2] = {bc, bc + (int64_t)16 * KP};
+    tile_product<TM, 2>(acc, bcs, A + i * LDA + 4 * q, LDA, 0, NC, 1);
+    const auto &ac = acc[0], &as = acc[1];
     // lane (i, q): bins 16g + 4q + v of tile row 16t + i (padded bins: zero basis rows -> 0)
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -241,26 +202,10 @@ __global__ void __launch_bounds__(kKfThreads) kaldi_fbank_kernel(const KaldiFban
   // ---- mel: M[r][j] = sum over bins of spectrum[r][bin] * mel[j][bin]; wave w takes mel groups w, w+4, ...
   const int H = (a.n_out + 15) / 16, NCM = NBP / 16;
   for (int h = wave_id; h < H; h += 4) {
-    f32x4 acc[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* br = a.melb + (int64_t)(16 * h + i) * NBP + 4 * q;
-    const float* mr = Ms + i * LDM + 4 * q;
-    uint4 nb = *(const uint4*)br, na[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(mr + t * 16 * LDM);
-    for (int ch = 0; ch < NCM; ++ch) {
-      const uint4 cb = nb;
-      uint4 ca[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) ca[t] = na[t];
-      if (ch + 1 < NCM) {
-        nb = *(const uint4*)(br + 16 * (ch + 1));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(mr + t * 16 * LDM + 16 * (ch + 1));
-      }
-      kf_mfma_chunk<TM>(acc, cb, ca);
-    }
+    f32x4 accm[1][TM] = {};
+    const float* const br[1] = {a.melb + (int64_t)(16 * h + i) * NBP + 4 * q};
+    tile_product<TM, 1>(accm, br, Ms + i * LDM + 4 * q, LDM, 0, NCM, 1);
+    const auto& acc = accm[0];
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
       const int r = 16 * t + i;
@@ -290,27 +235,7 @@ static inline bool kf_sizes_ok(int64_t N, int64_t P) {
 }
 
 static inline int kf_tm(int64_t N, int64_t P) {
-  for (int tm = 4; tm >= 1; --tm)
-    if (kf_smem(16 * tm, N, P) + kKfStaticLds <= kKfLdsBytes) return tm;
-  return 0;
-}
-
-template <int TM, bool DITHER>
-static int kf_launch(const KaldiFbankArgs& a, hipStream_t s) {
-  const int64_t smem = kf_smem(16 * TM, a.N, a.P);
-  auto fn = kaldi_fbank_kernel<TM, DITHER>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(a.n_frames, 16 * TM)), dim3(kKfThreads), (size_t)smem, s, a);
-  return fh_launch_status();
-}
-
-template <bool DITHER>
-static int kf_dispatch(int tm, const KaldiFbankArgs& a, hipStream_t s) {
-  if (tm == 4) return kf_launch<4, DITHER>(a, s);
-  if (tm == 3) return kf_launch<3, DITHER>(a, s);
-  if (tm == 2) return kf_launch<2, DITHER>(a, s);
-  return kf_launch<1, DITHER>(a, s);
+  return KfTm::largest(kCuLdsBytes, [&](int BM) { return kf_smem(BM, N, P) + kKfStaticLds; });
 }
 
 }  // namespace fh
@@ -361,5 +286,9 @@ extern "C" int fhvae_kaldi_fbank_fwd(const float* wave, int64_t n_samples, const
   a.N = (int)frame_len; a.S = (int)frame_shift; a.P = (int)padded_len; a.n_out = (int)n_mels; a.flags = flags;
   a.preemph = preemph; a.dither = dither; a.seed = seed;
   a.out = out; a.status = status;
-  return dith ? kf_dispatch<true>(tm, a, s) : kf_dispatch<false>(tm, a, s);
+  return KfTm::dispatch(tm, [&](auto tmc) {
+    constexpr int TM = decltype(tmc)::value;
+    return launch_lds(dith ? kaldi_fbank_kernel<TM, true> : kaldi_fbank_kernel<TM, false>, fh_cdiv(n_frames, 16 * TM), kKfThreads,
+                      kf_smem(16 * TM, frame_len, padded_len), s, a);
+  });
 }

@@ -25,12 +25,11 @@
 //
 // A band that would make the kernel read outside its arrays sets FHVAE_MELINV_BAD_BAND in the status word (a check kernel in
 // front); the main kernel then writes nothing.
-#include "common.h"
+#include "audio_tile.h"
 
 namespace fh {
 namespace {
 
-constexpr int kMiLdsBytes = 163840;  // 160 KiB per CU on gfx950
 constexpr float kMiLogFloor = -50.f;  // the "spec" features' floor (csrc/feats.hip)
 
 __global__ void melinv_check_kernel(const int32_t* __restrict__ bin_filt, const int32_t* __restrict__ filt_first,
@@ -137,7 +136,7 @@ static inline int64_t melinv_smem(int tf, int64_t n_mels, int64_t n_bins) { retu
 // the widest tile (one frame per lane, at most a wave) whose state fits in LDS
 static inline int melinv_tf(int64_t n_mels, int64_t n_bins) {
   for (int tf = 64; tf >= 8; tf >>= 1)
-    if (melinv_smem(tf, n_mels, n_bins) <= kMiLdsBytes) return tf;
+    if (melinv_smem(tf, n_mels, n_bins) <= kCuLdsBytes) return tf;
   return 0;
 }
 
@@ -145,14 +144,9 @@ template <int TF, int NT>
 static int melinv_launch(const float* mel, int64_t n_frames, int n_mels, int n_bins, const int32_t* bin_filt, const float* bin_w,
                          const int32_t* filt_first, const int32_t* filt_off, const float* filt_w, float inv_l, const float* beta,
                          int n_iter, int flags, float* out, const int32_t* status, hipStream_t s) {
-  const int64_t smem = melinv_smem(TF, n_mels, n_bins);
-  auto fn = melinv_kernel<TF, NT>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(n_frames, TF)), dim3(NT), (size_t)smem, s, mel, n_frames, n_mels, n_bins, bin_filt,
-                     bin_w, filt_first, filt_off, filt_w, inv_l, beta, n_iter, (flags & FHVAE_MELINV_IN_LOG) != 0,
-                     (flags & FHVAE_MELINV_OUT_LOG) != 0, out, status);
-  return fh_launch_status();
+  return launch_lds(melinv_kernel<TF, NT>, fh_cdiv(n_frames, TF), NT, melinv_smem(TF, n_mels, n_bins), s, mel, n_frames, n_mels, n_bins,
+                    bin_filt, bin_w, filt_first, filt_off, filt_w, inv_l, beta, n_iter, (flags & FHVAE_MELINV_IN_LOG) != 0,
+                    (flags & FHVAE_MELINV_OUT_LOG) != 0, out, status);
 }
 
 }  // namespace

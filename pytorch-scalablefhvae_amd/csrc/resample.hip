@@ -8,7 +8,7 @@
 // A workgroup takes BM = 16 * TM consecutive rows (a tile may span utterances; each row finds its utterance by binary
 // search in row_ptr) and gathers their windows into LDS, zero-filled outside the utterance: nothing of a neighbour leaks in
 // and the ends are resampy's (no reflection).  Each wave owns whole 16-column groups of the bank for all BM rows, reads the
-// bank from L2 straight into registers one 16-k chunk ahead (as feats.hip) and multiplies only the chunks [c0, c1) in which
+// bank from L2 straight into registers one 16-k chunk ahead (audio_tile.h) and multiplies only the chunks [c0, c1) in which
 // its 16 columns have weights: the bank is banded, the rest of the window would add exact zeros.
 //
 // resampy advances its time register by repeated float64 addition, and its truncated index_step makes the filter
@@ -23,11 +23,12 @@
 // Pointer errors: a check kernel validates in_ptr / out_ptr / row_ptr against the length rule and sets
 // FHVAE_RESAMPLE_BAD_PTR; the other kernels then write nothing.  They also re-check the utterance of every row, so no
 // input makes them read or write out of bounds.
-#include "common.h"
+#include "audio_tile.h"
 
 namespace fh {
 
 constexpr int kRsThreads = 256;  // 4 waves
+using RsTm = TmSet<4, 2, 1>;
 
 // librosa's length rule in float64: resampy computes (int64)(n * ratio) samples, librosa returns ceil(n * ratio)
 __host__ __device__ inline int64_t rs_out_len(int64_t n, double ratio) { return (int64_t)__builtin_ceil((double)n * ratio); }
@@ -43,11 +44,7 @@ __device__ inline bool rs_find_row(int64_t row, const int64_t* __restrict__ in_p
                                    const int64_t* __restrict__ row_ptr, int64_t U, int64_t n_in_total, int64_t n_out_total,
                                    int64_t n_rows, int64_t PL, int64_t PM, int64_t P, int64_t WL, double ratio, RsRow& r) {
   if (row >= n_rows) return false;
-  int64_t lo = 0, hi = U - 1;  // last u with row_ptr[u] <= row
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (row_ptr[mid] <= row) lo = mid; else hi = mid - 1;
-  }
+  const int64_t lo = last_le(row_ptr, U, row);
   const int64_t i0 = in_ptr[lo], i1 = in_ptr[lo + 1], o0 = out_ptr[lo], o1 = out_ptr[lo + 1], r0 = row_ptr[lo], r1 = row_ptr[lo + 1];
   const int64_t n = i1 - i0, m = o1 - o0;
   if (!(i0 >= 0 && i1 <= n_in_total && n >= 0 && o0 >= 0 && o1 <= n_out_total && m == rs_out_len(n, ratio) && r0 <= row &&
@@ -77,37 +74,6 @@ __global__ void resample_check_kernel(const int64_t* __restrict__ in_ptr, const 
   if (u == 0) ok = ok && o0 == 0 && r0 == 0;
   if (u == U - 1) ok = ok && o1 == n_out_total && r1 == n_rows;
   if (!ok) atomicOr(status, FHVAE_RESAMPLE_BAD_PTR);
-}
-
-// acc[t] += bank fragment . window fragment over the 16-k chunks c = from, from + step, ... (to excluded), in that order;
-// the next chunk's fragments are loaded before this chunk's products (SWAP order as feats.hip: lane (i, q) ends with
-// columns 4q..4q+3 of the bank side for tile row i)
-template <int TM>
-__device__ __forceinline__ void rs_chain(f32x4 (&acc)[TM], const float* br, const float* ar, int LDA, int from, int to, int step) {
-  if (from == to) return;
-  uint4 nb = *(const uint4*)(br + 16 * from), na[TM];
-#pragma unroll
-  for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * from);
-  for (int c = from; c != to; c += step) {
-    const uint4 cb = nb;
-    uint4 ca[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ca[t] = na[t];
-    if (c + step != to) {
-      nb = *(const uint4*)(br + 16 * (c + step));
-#pragma unroll
-      for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * (c + step));
-    }
-    const float bs[4] = {__uint_as_float(cb.x), __uint_as_float(cb.y), __uint_as_float(cb.z), __uint_as_float(cb.w)};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-#pragma unroll
-      for (int t = 0; t < TM; ++t) {
-        const float as = s == 0 ? __uint_as_float(ca[t].x) : s == 1 ? __uint_as_float(ca[t].y) : s == 2 ? __uint_as_float(ca[t].z) : __uint_as_float(ca[t].w);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bs[s], as, acc[t], 0, 0, 0);
-      }
-    }
-  }
 }
 
 // LDS: windows [BM][LDA], LDA = KP + 4 (row stride an odd multiple of 16 bytes: the 16 rows of a ds_read_b128 fragment hit
@@ -158,18 +124,17 @@ __global__ void __launch_bounds__(kRsThreads) resample_kernel(const float* __res
     // two chains per output, both running from a wing of the filter towards its centre (the left half of the chunks
     // upwards, the right half downwards) and added at the end: the partial sums stay small until the last steps, so the
     // additions round at the size of the wings' terms instead of the result's.
-    f32x4 acc[TM], accr[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) acc[t] = accr[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 accl[1][TM] = {}, accr[1][TM] = {};
     if (c0 < c1) {
-      const float* br = bank + (int64_t)(16 * g + i) * KP + 4 * q;
+      const float* const br[1] = {bank + (int64_t)(16 * g + i) * KP + 4 * q};
       const float* ar = A + i * LDA + 4 * q;
       const int mid = (c0 + c1 + 1) >> 1;
-      rs_chain<TM>(acc, br, ar, LDA, c0, mid, 1);
-      rs_chain<TM>(accr, br, ar, LDA, c1 - 1, mid - 1, -1);
+      tile_product<TM, 1>(accl, br, ar, LDA, c0, mid, 1);
+      if (mid < c1) tile_product<TM, 1>(accr, br, ar, LDA, c1 - 1, mid - 1, -1);
 #pragma unroll
-      for (int t = 0; t < TM; ++t) acc[t] += accr[t];
+      for (int t = 0; t < TM; ++t) accl[0][t] += accr[0][t];
     }
+    const auto& acc = accl[0];
     // lane (i, q): columns 16g + 4q + v of tile row 16t + i
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -220,22 +185,7 @@ __global__ void __launch_bounds__(64) resample_fix_kernel(const float* __restric
 static inline int64_t rs_smem(int BM, int64_t KP) { return (int64_t)BM * 4 * (KP + 4); }
 
 static inline int rs_tm(int64_t KP) {
-  for (int tm = 4; tm >= 1; tm >>= 1)
-    if (rs_smem(16 * tm, KP) <= (int64_t)4 * FHVAE_RESAMPLE_LDS_FLOATS) return tm;
-  return 0;
-}
-
-template <int TM>
-static int rs_launch(const float* wave, const int64_t* in_ptr, const int64_t* out_ptr, const int64_t* row_ptr, int64_t U,
-                     int64_t n_in, int64_t n_out, int64_t n_rows, const float* bank, const int32_t* chunks, int L, int M, int P,
-                     int KP, int WL, double ratio, float* out, const int32_t* status, hipStream_t s) {
-  const int64_t smem = rs_smem(16 * TM, KP);
-  auto fn = resample_kernel<TM>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(n_rows, 16 * TM)), dim3(kRsThreads), (size_t)smem, s, wave, in_ptr, out_ptr,
-                     row_ptr, U, n_in, n_out, n_rows, bank, chunks, L, M, P, KP, WL, ratio, out, status);
-  return fh_launch_status();
+  return RsTm::largest((int64_t)4 * FHVAE_RESAMPLE_LDS_FLOATS, [&](int BM) { return rs_smem(BM, KP); });
 }
 
 }  // namespace fh
@@ -287,9 +237,11 @@ extern "C" int fhvae_resample_fwd(const float* wave_in, int64_t n_in, const int6
   int rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
   const int l = (int)L, m = (int)M, p = (int)P, kp = (int)KP, wl = (int)WL;
-  if (tm == 4) rc = rs_launch<4>(wave_in, in_ptr, out_ptr, row_ptr, U, n_in, n_out, n_rows, bank, chunks, l, m, p, kp, wl, ratio, wave_out, status, s);
-  else if (tm == 2) rc = rs_launch<2>(wave_in, in_ptr, out_ptr, row_ptr, U, n_in, n_out, n_rows, bank, chunks, l, m, p, kp, wl, ratio, wave_out, status, s);
-  else rc = rs_launch<1>(wave_in, in_ptr, out_ptr, row_ptr, U, n_in, n_out, n_rows, bank, chunks, l, m, p, kp, wl, ratio, wave_out, status, s);
+  rc = RsTm::dispatch(tm, [&](auto tmc) {
+    constexpr int TM = decltype(tmc)::value;
+    return launch_lds(resample_kernel<TM>, fh_cdiv(n_rows, 16 * TM), kRsThreads, rs_smem(16 * TM, KP), s, wave_in, in_ptr, out_ptr,
+                      row_ptr, U, n_in, n_out, n_rows, bank, chunks, l, m, p, kp, wl, ratio, wave_out, status);
+  });
   if (rc != FHVAE_OK || n_exc == 0) return rc;
   hipLaunchKernelGGL(resample_fix_kernel, dim3((unsigned)n_rows), dim3(64), 0, s, wave_in, in_ptr, out_ptr, row_ptr, U, n_in, n_out,
                      n_rows, exc, n_exc, alt, (int)alt_taps, (int)alt_wl, l, m, p, wl, ratio, wave_out, status);

@@ -9,7 +9,7 @@
 //                        workspace frames that cover it in increasing frame order, divides by the window's sum of squares over
 //                        the same frames (where above tiny(f32)); the centre padding is never written.  No atomics.
 //   fhvae_synth_project  waveforms -> frames (reflected centre padding, no pre-emphasis) -> forward DFT on the MFMA (the
-//                        feats.hip scheme and its basis) -> rebuilt = the complex STFT, a = rebuilt - coef * tprev,
+//                        audio_tile.h product on feats.hip's basis) -> rebuilt = the complex STFT, a = rebuilt - coef * tprev,
 //                        next = mag * a / (|a| + 1e-16): one Griffin-Lim round after the inverse, in one launch.
 //   fhvae_synth_deemph   x[t] = y[t] + coef x[t-1] per utterance, as a blocked scan: a thread restarts the recurrence from a
 //                        zero state W samples before each 256-sample block of the utterance, |coef|^W < 2^-30.
@@ -20,14 +20,14 @@
 // Pointer errors: a check kernel validates wave_ptr / frame_ptr against hop * (frames - 1) and sets FHVAE_SYNTH_BAD_PTR; the
 // kernels then write nothing.  They also re-check the utterance of everything they gather, so no input makes them read or
 // write out of bounds.
-#include "common.h"
+#include "audio_tile.h"
 
 namespace fh {
 namespace {
 
 constexpr int kSynThreads = 256;  // 4 waves
 constexpr int kSynMaxBM = 64;
-constexpr int kSynLdsBytes = 163840;  // 160 KiB per CU on gfx950
+using SynTm = TmSet<4, 2, 1>;
 constexpr int kDeemphBlock = 256;     // samples per scan block (utterance-relative)
 constexpr int kDeemphMaxWarm = 1 << 16;
 
@@ -48,24 +48,9 @@ __global__ void synth_check_kernel(const int64_t* __restrict__ wave_ptr, const i
   if (!ok) atomicOr(status, FHVAE_SYNTH_BAD_PTR);
 }
 
-// acc[t] += B-fragment . A-fragment over one 16-k chunk: lane (i, q) ends with rows 4q..4q+3 of the B side (basis rows) for
-// column i (row i of the t-th 16-row tile of A)
-template <int TM>
-__device__ __forceinline__ void syn_mfma_chunk(f32x4 (&acc)[TM], const uint4& b, const uint4 (&a)[TM]) {
-  const float bs[4] = {__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      const float as = s == 0 ? __uint_as_float(a[t].x) : s == 1 ? __uint_as_float(a[t].y) : s == 2 ? __uint_as_float(a[t].z) : __uint_as_float(a[t].w);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bs[s], as, acc[t], 0, 0, 0);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- inverse DFT
 // LDS: A [BM][LDA], LDA = K2P + 4 (row stride an odd multiple of 16 bytes).  Wave w takes 16-sample groups w, w+4, ... of all
-// BM rows; its basis fragments go from L2 straight into registers, one 16-k chunk ahead (the feats.hip scheme).
+// BM rows (the audio_tile.h scheme).
 template <int TM>
 __global__ void __launch_bounds__(kSynThreads) synth_idft_kernel(const float* __restrict__ spec, int64_t n_frames,
                                                                 const float* __restrict__ basis, int n_fft,
@@ -90,26 +75,10 @@ __global__ void __launch_bounds__(kSynThreads) synth_idft_kernel(const float* __
 
   const int NC = K2P / 16;
   for (int g = wave_id; g < GN; g += 4) {
-    f32x4 acc[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* br = basis + (int64_t)(16 * g + i) * K2P + 4 * q;
-    const float* ar = A + i * LDA + 4 * q;
-    uint4 nb = *(const uint4*)br, na[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA);
-    for (int c = 0; c < NC; ++c) {
-      const uint4 cb = nb;
-      uint4 ca[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) ca[t] = na[t];
-      if (c + 1 < NC) {
-        nb = *(const uint4*)(br + 16 * (c + 1));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * (c + 1));
-      }
-      syn_mfma_chunk<TM>(acc, cb, ca);
-    }
+    f32x4 accs[1][TM] = {};
+    const float* const br[1] = {basis + (int64_t)(16 * g + i) * K2P + 4 * q};
+    tile_product<TM, 1>(accs, br, A + i * LDA + 4 * q, LDA, 0, NC, 1);
+    const auto& acc = accs[0];
     // lane (i, q): samples 16g + 4q + v of tile row 16t + i; ws rows are KP wide (the padded samples are written as zeros)
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -128,11 +97,7 @@ __global__ void __launch_bounds__(256) synth_ola_kernel(const float* __restrict_
   if (*status & FHVAE_SYNTH_BAD_PTR) return;
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_samples) return;
-  int64_t lo = 0, hi = U - 1;  // last u with wave_ptr[u] <= s
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (wave_ptr[mid] <= s) lo = mid; else hi = mid - 1;
-  }
+  const int64_t lo = last_le(wave_ptr, U, s);
   const int64_t w0 = wave_ptr[lo], w1 = wave_ptr[lo + 1], p0 = frame_ptr[lo], p1 = frame_ptr[lo + 1];
   const int64_t F = p1 - p0;
   if (!(w0 <= s && s < w1 && w1 <= n_samples && p0 >= 0 && p1 <= n_frames && F >= 2 && w1 - w0 == (int64_t)hop * (F - 1))) return;
@@ -180,11 +145,7 @@ __global__ void __launch_bounds__(kSynThreads) synth_project_kernel(const float*
     int ok = 0;
     int64_t base = 0, start = 0, L = 0;
     if (f < n_frames) {
-      int64_t lo = 0, hi = U - 1;  // last u with frame_ptr[u] <= f
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (frame_ptr[mid] <= f) lo = mid; else hi = mid - 1;
-      }
+      const int64_t lo = last_le(frame_ptr, U, f);
       const int64_t w0 = wave_ptr[lo], w1 = wave_ptr[lo + 1], p0 = frame_ptr[lo], p1 = frame_ptr[lo + 1];
       L = w1 - w0;
       ok = w0 >= 0 && w1 <= n_samples && L >= 1 && p0 <= f && f < p1 && p1 - p0 >= 2 && L == (int64_t)hop * (p1 - p0 - 1);
@@ -222,29 +183,11 @@ __global__ void __launch_bounds__(kSynThreads) synth_project_kernel(const float*
 
   const int NC = KP / 16;
   for (int g = wave_id; g < G; g += 4) {
-    f32x4 ac[TM], as[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) ac[t] = as[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2][TM] = {};
     const float* bc = dft + (int64_t)(32 * g + i) * KP + 4 * q;
-    const float* bsn = bc + (int64_t)16 * KP;
-    const float* ar = A + i * LDA + 4 * q;
-    uint4 nc = *(const uint4*)bc, ns = *(const uint4*)bsn, na[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA);
-    for (int c = 0; c < NC; ++c) {
-      const uint4 cc = nc, cs = ns;
-      uint4 ca[TM];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) ca[t] = na[t];
-      if (c + 1 < NC) {
-        nc = *(const uint4*)(bc + 16 * (c + 1));
-        ns = *(const uint4*)(bsn + 16 * (c + 1));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) na[t] = *(const uint4*)(ar + t * 16 * LDA + 16 * (c + 1));
-      }
-      syn_mfma_chunk<TM>(ac, cc, ca);
-      syn_mfma_chunk<TM>(as, cs, ca);
-    }
+    const float* const bcs[2] = {bc, bc + (int64_t)16 * KP};
+    tile_product<TM, 2>(acc, bcs, A + i * LDA + 4 * q, LDA, 0, NC, 1);
+    const auto &ac = acc[0], &as = acc[1];
     // lane (i, q): bins 16g + 4q + v of tile row 16t + i
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -282,12 +225,7 @@ __global__ void __launch_bounds__(256) synth_deemph_kernel(const float* __restri
   int64_t t = g * kDeemphBlock;
   if (t >= n_samples) return;
   const int64_t end = t + kDeemphBlock < n_samples ? t + kDeemphBlock : n_samples;
-  int64_t lo = 0, hi = U - 1;  // last u with wave_ptr[u] <= t
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (wave_ptr[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  int64_t u = lo;
+  int64_t u = last_le(wave_ptr, U, t);
   while (t < end && u < U) {
     const int64_t w0 = wave_ptr[u], w1 = wave_ptr[u + 1];
     if (w0 < 0 || w1 > n_samples || w0 > t) return;  // (the check kernel has flagged it)
@@ -316,34 +254,7 @@ constexpr int64_t kSynStaticLds = kSynMaxBM * (3 * 8 + 4);
 // the widest tile both products of a round fit in LDS with (K2P >= KP: the inverse's rows are the longer ones)
 static inline int synth_tm(int64_t n_fft) {
   const int64_t K2P = (2 * (n_fft / 2 + 1) + 15) & ~15LL;
-  for (int tm = 4; tm >= 1; tm >>= 1)
-    if (synth_smem(16 * tm, K2P) + kSynStaticLds <= kSynLdsBytes) return tm;
-  return 0;
-}
-
-template <int TM>
-static int idft_launch(const float* spec, int64_t n_frames, const float* basis, int n_fft, float* ws, const int32_t* status,
-                       hipStream_t s) {
-  const int64_t smem = synth_smem(16 * TM, (2 * (n_fft / 2 + 1) + 15) & ~15);
-  auto fn = synth_idft_kernel<TM>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(n_frames, 16 * TM)), dim3(kSynThreads), (size_t)smem, s, spec, n_frames, basis,
-                     n_fft, ws, status);
-  return fh_launch_status();
-}
-
-template <int TM>
-static int project_launch(const float* wave, const int64_t* wave_ptr, const int64_t* frame_ptr, int64_t U, int64_t n_samples,
-                          int64_t n_frames, const float* dft, const float* mag, const float* tprev, float coef, int n_fft, int hop,
-                          float* rebuilt, float* next, const int32_t* status, hipStream_t s) {
-  const int64_t smem = synth_smem(16 * TM, (n_fft + 15) & ~15);
-  auto fn = synth_project_kernel<TM>;
-  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(fn, dim3((unsigned)fh_cdiv(n_frames, 16 * TM)), dim3(kSynThreads), (size_t)smem, s, wave, wave_ptr, frame_ptr,
-                     U, n_samples, n_frames, dft, mag, tprev, coef, n_fft, hop, rebuilt, next, status);
-  return fh_launch_status();
+  return SynTm::largest(kCuLdsBytes, [&](int BM) { return synth_smem(BM, K2P) + kSynStaticLds; });
 }
 
 // the size checks every entry point shares; FHVAE_OK or the error to return before any launch
@@ -389,10 +300,12 @@ extern "C" int fhvae_synth_istft(const float* spec, int64_t n_frames, const int6
                      n_frames, hop, status);
   rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
-  const int tm = synth_tm(n_fft), nf = (int)n_fft;
-  rc = tm == 4 ? idft_launch<4>(spec, n_frames, synth_basis, nf, frames_ws, status, s)
-     : tm == 2 ? idft_launch<2>(spec, n_frames, synth_basis, nf, frames_ws, status, s)
-               : idft_launch<1>(spec, n_frames, synth_basis, nf, frames_ws, status, s);
+  const int nf = (int)n_fft;
+  rc = SynTm::dispatch(synth_tm(n_fft), [&](auto tmc) {
+    constexpr int TM = decltype(tmc)::value;
+    return launch_lds(synth_idft_kernel<TM>, fh_cdiv(n_frames, 16 * TM), kSynThreads, synth_smem(16 * TM, (2 * (nf / 2 + 1) + 15) & ~15),
+                      s, spec, n_frames, synth_basis, nf, frames_ws, status);
+  });
   if (rc != FHVAE_OK) return rc;
   hipLaunchKernelGGL(synth_ola_kernel, dim3((unsigned)fh_cdiv(n_samples, 256)), dim3(256), 0, s, frames_ws, win_sq, wave_ptr,
                      frame_ptr, U, n_samples, n_frames, nf, (int)hop, wave_out, status);
@@ -418,10 +331,12 @@ extern "C" int fhvae_synth_project(const float* wave, int64_t n_samples, const i
                      n_frames, hop, status);
   rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
-  const int tm = synth_tm(n_fft), nf = (int)n_fft, hp = (int)hop;
-  if (tm == 4) return project_launch<4>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mag, tprev, coef, nf, hp, rebuilt, next, status, s);
-  if (tm == 2) return project_launch<2>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mag, tprev, coef, nf, hp, rebuilt, next, status, s);
-  return project_launch<1>(wave, wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mag, tprev, coef, nf, hp, rebuilt, next, status, s);
+  const int nf = (int)n_fft;
+  return SynTm::dispatch(synth_tm(n_fft), [&](auto tmc) {
+    constexpr int TM = decltype(tmc)::value;
+    return launch_lds(synth_project_kernel<TM>, fh_cdiv(n_frames, 16 * TM), kSynThreads, synth_smem(16 * TM, (nf + 15) & ~15), s, wave,
+                      wave_ptr, frame_ptr, U, n_samples, n_frames, dft_basis, mag, tprev, coef, nf, (int)hop, rebuilt, next, status);
+  });
 }
 
 extern "C" int fhvae_synth_deemph(const float* wave, const int64_t* wave_ptr, int64_t U, int64_t n_samples, float coef, float* out,

@@ -133,32 +133,44 @@ def _padded_sizes(n_fft):
     return (n_fft + 15) // 16 * 16, n_bins, (n_bins + 15) // 16
 
 
-def dft_basis(n_fft):
-    """The kernel's (32 * G, KP) f32 basis: row 32g + i = w[n] cos(2 pi n b / n_fft), row 32g + 16 + i = -w[n] sin(...), for
-    bin b = 16g + i (zero rows past n_fft // 2, zero columns past n_fft); w = periodic Hamming (scipy get_window,
-    fftbins=True).  Built in float64 with the phase reduced exactly (n * b mod n_fft), then rounded to f32."""
-    KP, n_bins, G = _padded_sizes(n_fft)
-    n = np.arange(n_fft)
-    w = 0.54 - 0.46 * np.cos(2.0 * np.pi * n / n_fft)
-    b = np.arange(n_bins)
-    ph = 2.0 * np.pi * ((b[:, None] * n[None, :]) % n_fft) / n_fft
-    out = np.zeros((G, 2, 16, KP), dtype=np.float64)
-    c = np.zeros((16 * G, n_fft))
-    s = np.zeros((16 * G, n_fft))
+def hamming(n_fft):
+    """Periodic Hamming window (scipy get_window("hamming", n_fft, fftbins=True)) in float64."""
+    return 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft)
+
+
+def _dft_layout(w, period, n_bins, n_cols):
+    """The kernels' (32 * G, n_cols) f32 DFT basis for a window w of N <= n_cols samples: row 32g + i =
+    w[n] cos(2 pi n b / period), row 32g + 16 + i = -w[n] sin(...), for bin b = 16g + i < n_bins and n < N (zero elsewhere).
+    Built in float64 with the phase reduced exactly (n * b mod period), then rounded to f32."""
+    N, G = len(w), (n_bins + 15) // 16
+    ph = 2.0 * np.pi * ((np.arange(n_bins)[:, None] * np.arange(N)[None, :]) % period) / period
+    c = np.zeros((16 * G, N))
+    s = np.zeros((16 * G, N))
     c[:n_bins] = w * np.cos(ph)
     s[:n_bins] = -w * np.sin(ph)
-    out[:, 0, :, :n_fft] = c.reshape(G, 16, n_fft)
-    out[:, 1, :, :n_fft] = s.reshape(G, 16, n_fft)
-    return out.reshape(32 * G, KP).astype(np.float32)
+    out = np.zeros((G, 2, 16, n_cols), dtype=np.float64)
+    out[:, 0, :, :N] = c.reshape(G, 16, N)
+    out[:, 1, :, :N] = s.reshape(G, 16, N)
+    return out.reshape(32 * G, n_cols).astype(np.float32)
+
+
+def _mel_layout(m):
+    """A (n_mels, n_bins) mel bank zero-padded to the kernels' f32 (16 * ceil(n_mels / 16), 16 * ceil(n_bins / 16))."""
+    out = np.zeros(((m.shape[0] + 15) // 16 * 16, (m.shape[1] + 15) // 16 * 16), dtype=np.float32)
+    out[:m.shape[0], :m.shape[1]] = m
+    return out
+
+
+def dft_basis(n_fft):
+    """The kernel's (32 * G, KP) f32 basis (_dft_layout) of the n_fft-point DFT under the periodic Hamming window, bins
+    0 .. n_fft // 2, KP = n_fft rounded up to 16."""
+    KP, n_bins, _ = _padded_sizes(n_fft)
+    return _dft_layout(hamming(n_fft), n_fft, n_bins, KP)
 
 
 def mel_basis(sr, n_fft, n_mels):
     """The kernel's (16 * ceil(n_mels / 16), 16 * G) f32 mel basis for an STFT of n_fft points (n_fft' = 2 * (n_bins - 1))."""
-    _, n_bins, G = _padded_sizes(n_fft)
-    m = mel_filters(sr, 2 * (n_bins - 1), n_mels)
-    out = np.zeros(((n_mels + 15) // 16 * 16, 16 * G), dtype=np.float32)
-    out[:n_mels, :n_bins] = m
-    return out
+    return _mel_layout(mel_filters(sr, 2 * (n_fft // 2), n_mels))
 
 
 # ---------------------------------------------------------------------------------------------------------- resampling
@@ -367,29 +379,58 @@ class _Bases:
         self.mel = torch.from_numpy(mel_basis(sr, n_fft, n_mels)).to(device) if ftype == "fbank" else None
 
 
-def _run_batch(hb, waves, n_fft, hop, n_mels, ftype, bases, device):
+def _ptr(counts):
+    """(len + 1,) int64: the running sum of `counts` behind a 0."""
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def _upload(arrays, device, scale=None):
+    """The float32 arrays concatenated (along axis 0) in a pinned buffer, times `scale`, -> their device copy."""
     import torch
 
-    lens = np.array([len(w) for w in waves], dtype=np.int64)
-    frames = num_frames(lens, n_fft, hop)
-    wave_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    frame_ptr = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    n_out = n_mels if ftype == "fbank" else n_fft // 2 + 1
-    host = torch.empty(int(wave_ptr[-1]), dtype=torch.float32, pin_memory=True)
-    np.concatenate(waves, out=host.numpy())
-    ptrs = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).pin_memory()
-    wave_d = host.to(device, non_blocking=True)
-    ptrs_d = ptrs.to(device, non_blocking=True)
-    out = torch.empty((int(frame_ptr[-1]), n_out), dtype=torch.float32, device=device)
-    status = torch.zeros(1, dtype=torch.int32, device=device)
-    hb.feats_fwd(wave_d, ptrs_d[0], ptrs_d[1], bases.dft, bases.mel, n_fft, hop, n_mels, ftype, out, status)
+    host = torch.empty((sum(len(a) for a in arrays),) + arrays[0].shape[1:], dtype=torch.float32, pin_memory=True)
+    np.concatenate(arrays, out=host.numpy())
+    if scale is not None:
+        host.mul_(scale)
+    return host.to(device, non_blocking=True)
+
+
+def _upload_ptrs(ptrs, device):
+    import torch
+
+    return torch.from_numpy(np.stack(ptrs)).pin_memory().to(device, non_blocking=True)
+
+
+def _download(out, statuses, what, ptr):
+    """The end of a batch: `out` comes back through a pinned buffer, the status word(s) are read (which synchronises: the
+    copy is done too), a set one raises RuntimeError(what % status), -> rows ptr[j] : ptr[j + 1] of the result, one array each."""
+    import torch
+
     res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
     res.copy_(out, non_blocking=True)
-    st = status.cpu()  # (synchronises: the copy above is done too)
-    if int(st.item()) != 0:
-        raise RuntimeError("fhvae_feats_fwd: status %d (inconsistent wave_ptr / frame_ptr)" % int(st.item()))
+    st = tuple(int(s.cpu().item()) for s in statuses)
+    if any(st):
+        raise RuntimeError(what % (st[0] if len(st) == 1 else (st,)))
     r = res.numpy()
-    return [r[frame_ptr[j]:frame_ptr[j + 1]].copy() for j in range(len(waves))]
+    return [r[ptr[j]:ptr[j + 1]].copy() for j in range(len(ptr) - 1)]
+
+
+def _feats_batch(hb, wave_d, lens, n_fft, hop, n_mels, ftype, bases, device, what, statuses=()):
+    """fhvae_feats_fwd on the concatenated waveforms of `lens` samples on the device -> their features; `statuses`: the status
+    words of what ran before it on the stream."""
+    import torch
+
+    frame_ptr = _ptr(num_frames(lens, n_fft, hop))
+    ptrs_d = _upload_ptrs([_ptr(lens), frame_ptr], device)
+    out = torch.empty((int(frame_ptr[-1]), n_mels if ftype == "fbank" else n_fft // 2 + 1), dtype=torch.float32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    hb.feats_fwd(wave_d, ptrs_d[0], ptrs_d[1], bases.dft, bases.mel, n_fft, hop, n_mels, ftype, out, status)
+    return _download(out, tuple(statuses) + (status,), what, frame_ptr)
+
+
+def _run_batch(hb, waves, n_fft, hop, n_mels, ftype, bases, device):
+    return _feats_batch(hb, _upload(waves, device), np.array([len(w) for w in waves], dtype=np.int64), n_fft, hop, n_mels, ftype,
+                        bases, device, "fhvae_feats_fwd: status %d (inconsistent wave_ptr / frame_ptr)")
 
 
 def batches(lengths, max_samples=BATCH_SAMPLES):
@@ -426,15 +467,13 @@ def _resample_batch(hb, waves, rd, device):
     olens = resampled_length(lens, b.sr_in, b.sr_out)
     PL = b.P * b.L
     rows = -(-olens // PL)
-    ptrs = np.stack([np.concatenate([[0], np.cumsum(v)]).astype(np.int64) for v in (lens, olens, rows)])
-    n_in, n_out, n_rows = int(ptrs[0, -1]), int(ptrs[1, -1]), int(ptrs[2, -1])
+    ptrs = [_ptr(v) for v in (lens, olens, rows)]
+    n_out, n_rows = int(ptrs[1][-1]), int(ptrs[2][-1])
     out = torch.zeros(n_out, dtype=torch.float32, device=device)
     if n_out == 0:
         return out, olens, torch.zeros(1, dtype=torch.int32, device=device)
-    host = torch.empty(n_in, dtype=torch.float32, pin_memory=True)
-    np.concatenate(waves, out=host.numpy())
-    wave_d = host.to(device, non_blocking=True)
-    ptrs_d = torch.from_numpy(ptrs).pin_memory().to(device, non_blocking=True)
+    wave_d = _upload(waves, device)
+    ptrs_d = _upload_ptrs(ptrs, device)
     exc = None
     if rd.alt is not None:
         exc = torch.from_numpy(b.exceptions(int(-(-olens.max() // b.L))).copy()).to(device)
@@ -454,62 +493,42 @@ def resample(waves, sr_in, sr_out, device="cuda", max_samples=BATCH_SAMPLES):
     waves = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in waves]
     if not waves:
         return []
-    import torch
-
     import hip_binding as hb
 
     rd = _ResampleDev(bank, device)
     out = []
     for a, b in batches([len(w) for w in waves], max_samples):
-        r = _resample_batch(hb, waves[a:b], rd, device)
-        y, olens = r[0], r[1]
-        res = torch.empty(y.shape, dtype=torch.float32, pin_memory=True)
-        res.copy_(y, non_blocking=True)
-        st = int(r[2].cpu().item())  # (synchronises: the copy above is done too)
-        if st != 0:
-            raise RuntimeError("fhvae_resample_fwd: status %d (inconsistent in_ptr / out_ptr / row_ptr)" % st)
-        ptr = np.concatenate([[0], np.cumsum(olens)])
-        rn = res.numpy()
-        out.extend(rn[ptr[j]:ptr[j + 1]].copy() for j in range(b - a))
+        y, olens, status = _resample_batch(hb, waves[a:b], rd, device)
+        out.extend(_download(y, (status,), "fhvae_resample_fwd: status %d (inconsistent in_ptr / out_ptr / row_ptr)", _ptr(olens)))
     return out
 
 
 def _features_resampled(hb, waves, rd, n_fft, hop, n_mels, ftype, bases, device, names):
     """One batch at a source rate: resampled on the device and handed to fhvae_feats_fwd there (no host round trip)."""
-    import torch
-
-    r = _resample_batch(hb, waves, rd, device)
-    y, olens = r[0], r[1]
+    y, olens, status = _resample_batch(hb, waves, rd, device)
     for j, n in enumerate(olens):
         if n < n_fft // 2 + 1:
             raise ValueError("%s: %d samples after resampling; at least n_fft // 2 + 1 = %d are needed" % (names[j], n, n_fft // 2 + 1))
-    frames = num_frames(olens, n_fft, hop)
-    wave_ptr = np.concatenate([[0], np.cumsum(olens)]).astype(np.int64)
-    frame_ptr = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    n_out = n_mels if ftype == "fbank" else n_fft // 2 + 1
-    ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).pin_memory().to(device, non_blocking=True)
-    out = torch.empty((int(frame_ptr[-1]), n_out), dtype=torch.float32, device=device)
-    status = torch.zeros(1, dtype=torch.int32, device=device)
-    hb.feats_fwd(y, ptrs_d[0], ptrs_d[1], bases.dft, bases.mel, n_fft, hop, n_mels, ftype, out, status)
-    res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
-    res.copy_(out, non_blocking=True)
-    st = (int(r[2].cpu().item()), int(status.cpu().item()))  # (synchronises: the copy above is done too)
-    if st != (0, 0):
-        raise RuntimeError("fhvae_resample_fwd / fhvae_feats_fwd: status %s (inconsistent pointers)" % (st,))
-    rn = res.numpy()
-    return [rn[frame_ptr[j]:frame_ptr[j + 1]].copy() for j in range(len(waves))]
+    return _feats_batch(hb, y, olens, n_fft, hop, n_mels, ftype, bases, device,
+                        "fhvae_resample_fwd / fhvae_feats_fwd: status %s (inconsistent pointers)", (status,))
+
+
+def _rate_groups(rates, n):
+    """{source rate: the indices of its waveforms, in order}; ValueError unless there is one rate per waveform."""
+    if len(rates) != n:
+        raise ValueError("rates has %d entries for %d waveforms" % (len(rates), n))
+    groups = {}
+    for j, r in enumerate(rates):
+        groups.setdefault(int(r), []).append(j)
+    return groups
 
 
 def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples):
     import hip_binding as hb
 
     n_fft, hop = check_params(sr, ftype, win_t, hop_t, n_mels)
-    if len(rates) != len(waves):
-        raise ValueError("rates has %d entries for %d waveforms" % (len(rates), len(waves)))
+    groups = _rate_groups(rates, len(waves))
     names = list(names) if names is not None else ["utterance %d" % j for j in range(len(waves))]
-    groups = {}
-    for j, r in enumerate(rates):
-        groups.setdefault(int(r), []).append(j)
     banks = {r: resample_bank(r, sr) for r in groups if r != sr}  # (an unsupported ratio fails before any work)
     out = [None] * len(waves)
     bases = None
@@ -569,11 +588,6 @@ def write_wav(path, y, sr):
         w.setsampwidth(2)
         w.setframerate(int(sr))
         w.writeframes(q.tobytes())
-
-
-def hamming(n_fft):
-    """Periodic Hamming window (scipy get_window("hamming", n_fft, fftbins=True)) in float64."""
-    return 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft)
 
 
 def window_sq(n_fft):
@@ -658,9 +672,8 @@ def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, l
 
     frames = np.array([len(S) for S in specs], dtype=np.int64)
     lens = hop * (frames - 1)
-    wave_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    frame_ptr = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    n_frames, n_samples, n_bins = int(frame_ptr[-1]), int(wave_ptr[-1]), n_fft // 2 + 1
+    wave_ptr, frame_ptr = _ptr(lens), _ptr(frames)
+    n_frames, n_samples = int(frame_ptr[-1]), int(wave_ptr[-1])
     ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).to(device)
     mag = spec_dev if spec_dev is not None else torch.from_numpy(np.concatenate(specs)).to(device)
     if log:
@@ -684,13 +697,7 @@ def _synth_batch(hb, specs, phases, n_fft, hop, n_iter, momentum, preemphasis, l
     hb.synth_istft(cur, ptrs_d[0], ptrs_d[1], bases.syn, bases.wsq, n_fft, hop, ws, y, status)
     out = torch.empty_like(y)
     hb.synth_deemph(y, ptrs_d[0], preemphasis, out, status)
-    res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
-    res.copy_(out, non_blocking=True)
-    st = int(status.cpu().item())  # (synchronises: the copy above is done too)
-    if st != 0:
-        raise RuntimeError("fhvae_synth_*: status %d (inconsistent wave_ptr / frame_ptr)" % st)
-    r = res.numpy()
-    return [r[wave_ptr[j]:wave_ptr[j + 1]].copy() for j in range(len(specs))]
+    return _download(out, (status,), "fhvae_synth_*: status %d (inconsistent wave_ptr / frame_ptr)", wave_ptr)
 
 
 def _check_init_phase(init_phase, shapes):
@@ -865,11 +872,8 @@ def _melinv_batch(hb, mels, md, log, device):
     """One launch: the mel features of a batch -> ((n_frames, n_bins) device tensor, status word)."""
     import torch
 
-    n = sum(len(S) for S in mels)
-    host = torch.empty((n, mels[0].shape[1]), dtype=torch.float32, pin_memory=True)
-    np.concatenate(mels, out=host.numpy())
-    mel_d = host.to(device, non_blocking=True)
-    out = torch.empty((n, md.n_bins), dtype=torch.float32, device=device)
+    mel_d = _upload(mels, device)
+    out = torch.empty((len(mel_d), md.n_bins), dtype=torch.float32, device=device)
     status = torch.zeros(1, dtype=torch.int32, device=device)
     hb.mel_invert(mel_d, md.bin_filt, md.bin_w, md.filt_first, md.filt_off, md.filt_w, md.inv_l, md.beta, out, status, in_log=log,
                   out_log=log)
@@ -889,22 +893,14 @@ def mel_to_spec(mels, sr, win_t=0.025, hop_t=0.010, n_mels=None, nnls_iters=NNLS
     n_fft, _ = check_melinv_params(sr, win_t, hop_t, n_mels, nnls_iters)
     if not mels:
         return []
-    import torch
-
     import hip_binding as hb
 
     md = _MelInvDev(sr, n_fft, n_mels, nnls_iters, device)
     out = []
     for a, b in frame_batches([len(S) for S in mels], max_frames):
         spec, status = _melinv_batch(hb, mels[a:b], md, log, device)
-        res = torch.empty(spec.shape, dtype=torch.float32, pin_memory=True)
-        res.copy_(spec, non_blocking=True)
-        st = int(status.cpu().item())  # (synchronises: the copy above is done too)
-        if st != 0:
-            raise RuntimeError("fhvae_mel_invert: status %d (the band points outside its arrays)" % st)
-        ptr = np.concatenate([[0], np.cumsum([len(S) for S in mels[a:b]])])
-        r = res.numpy()
-        out.extend(r[ptr[j]:ptr[j + 1]].copy() for j in range(b - a))
+        out.extend(_download(spec, (status,), "fhvae_mel_invert: status %d (the band points outside its arrays)",
+                             _ptr([len(S) for S in mels[a:b]])))
     return out
 
 
@@ -1060,33 +1056,15 @@ def kaldi_mel_filters(sr, P, n_mels, low=20.0, high=0.0):
     return np.where((m > left) & (m <= centre), up, np.where((m > centre) & (m < right), down, 0.0))
 
 
-def _kaldi_padded(N, P):
-    return (N + 15) // 16 * 16, P // 2, (P // 2 + 15) // 16
-
-
 def kaldi_dft_basis(N, P, window="povey", blackman_coeff=0.42):
-    """The kernel's (32 * G, KP) f32 basis: row 32g + i = w[n] cos(2 pi n b / P), row 32g + 16 + i = -w[n] sin(...), for bin
-    b = 16g + i < P / 2 and n < N (zero elsewhere); w = kaldi_window.  Built in float64 with the phase reduced exactly."""
-    KP, n_bins, G = _kaldi_padded(N, P)
-    n = np.arange(N)
-    w = kaldi_window(N, window, blackman_coeff)
-    ph = 2.0 * np.pi * ((np.arange(n_bins)[:, None] * n[None, :]) % P) / P
-    c = np.zeros((16 * G, N))
-    s = np.zeros((16 * G, N))
-    c[:n_bins] = w * np.cos(ph)
-    s[:n_bins] = -w * np.sin(ph)
-    out = np.zeros((G, 2, 16, KP), dtype=np.float64)
-    out[:, 0, :, :N] = c.reshape(G, 16, N)
-    out[:, 1, :, :N] = s.reshape(G, 16, N)
-    return out.reshape(32 * G, KP).astype(np.float32)
+    """The kernel's (32 * G, KP) f32 basis (_dft_layout) of the P-point DFT over the N samples of a frame under kaldi_window,
+    bins 0 .. P / 2 - 1, KP = N rounded up to 16."""
+    return _dft_layout(kaldi_window(N, window, blackman_coeff), P, P // 2, (N + 15) // 16 * 16)
 
 
 def kaldi_mel_basis(sr, P, n_mels, low=20.0, high=0.0):
     """The kernel's (16 * ceil(n_mels / 16), 16 * G) f32 mel basis (kaldi_mel_filters, zero-padded)."""
-    _, n_bins, G = _kaldi_padded(1, P)
-    out = np.zeros(((n_mels + 15) // 16 * 16, 16 * G), dtype=np.float32)
-    out[:n_mels, :n_bins] = kaldi_mel_filters(sr, P, n_mels, low, high)
-    return out
+    return _mel_layout(kaldi_mel_filters(sr, P, n_mels, low, high))
 
 
 def check_kaldi_options(opts):
@@ -1126,13 +1104,9 @@ def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device):
     N, S, P = sizes
     n_mels = opts["num-mel-bins"]
     lens = np.array([len(w) for w in waves], dtype=np.int64)
-    wave_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    frame_ptr = np.concatenate([[0], np.cumsum(kaldi_num_frames(lens, N, S))]).astype(np.int64)
-    host = torch.empty(int(wave_ptr[-1]), dtype=torch.float32, pin_memory=True)
-    np.concatenate(waves, out=host.numpy())
-    host.mul_(32768.0)  # Kaldi's int16 scale (exact: a power of two)
-    wave_d = host.to(device, non_blocking=True)
-    ptrs_d = torch.from_numpy(np.stack([wave_ptr, frame_ptr])).pin_memory().to(device, non_blocking=True)
+    frame_ptr = _ptr(kaldi_num_frames(lens, N, S))
+    wave_d = _upload(waves, device, scale=32768.0)  # Kaldi's int16 scale (exact: a power of two)
+    ptrs_d = _upload_ptrs([_ptr(lens), frame_ptr], device)
     dither = float(opts["dither"])
     ids_d = torch.from_numpy(np.asarray(ids, dtype=np.uint64).view(np.int64).copy()).to(device) if dither != 0.0 else None
     out = torch.empty((int(frame_ptr[-1]), n_mels), dtype=torch.float32, device=device)
@@ -1141,13 +1115,7 @@ def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device):
              | (hb.KALDI_USE_POWER if opts["use-power"] else 0))
     hb.kaldi_fbank_fwd(wave_d, ptrs_d[0], ptrs_d[1], ids_d, bases.dft, bases.mel, N, S, P, n_mels,
                        opts["preemphasis-coefficient"], dither, seed, flags, out, status)
-    res = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
-    res.copy_(out, non_blocking=True)
-    st = status.cpu()  # (synchronises: the copy above is done too)
-    if int(st.item()) != 0:
-        raise RuntimeError("fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)" % int(st.item()))
-    r = res.numpy()
-    return [r[frame_ptr[j]:frame_ptr[j + 1]].copy() for j in range(len(waves))]
+    return _download(out, (status,), "fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)", frame_ptr)
 
 
 def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, device="cuda", max_samples=BATCH_SAMPLES,
@@ -1171,12 +1139,7 @@ def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, d
     if len(ids) != len(waves) or len(names) != len(waves):
         raise ValueError("stream_ids / names must have one entry per waveform (%d)" % len(waves))
     if rates is not None:
-        if len(rates) != len(waves):
-            raise ValueError("rates has %d entries for %d waveforms" % (len(rates), len(waves)))
-        groups = {}
-        for j, r in enumerate(rates):
-            if int(r) != int(sr):
-                groups.setdefault(int(r), []).append(j)
+        groups = {r: idx for r, idx in _rate_groups(rates, len(waves)).items() if r != int(sr)}
         for r in groups:
             resample_bank(r, int(sr))  # (an unsupported ratio fails before any work)
         for r, idx in groups.items():
