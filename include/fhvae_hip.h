@@ -659,6 +659,47 @@ int fhvae_kaldi_fbank_fwd(const float* wave, int64_t n_samples, const int64_t* w
                           const float* mel_basis, int64_t frame_len, int64_t frame_shift, int64_t padded_len, int64_t n_mels,
                           float preemph, float dither, uint64_t seed, int flags, float* out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Kaldi compressed matrices (csrc/kaldi_cm.hip): the archive tokens CM, CM2 and CM3 of matrix/compressed-matrix.{h,cc},
+ * decoded into and coded from a row-major (n_frames, F) f32 matrix, a batch of U utterances per call (additions of ABI 11).
+ *   payload (n_bytes) uint8: the utterances' payloads (what follows the 16-byte header of an archive entry), each at a
+ *     byte offset that is a multiple of 4; n_bytes a multiple of 4, the pointer 4-byte aligned.
+ *     CM : cols headers of four uint16 (p0, p25, p75, p100), then cols x rows uint8, column-major
+ *     CM2: rows x cols uint16 row-major;  CM3: rows x cols uint8 row-major
+ *   desc (U): per utterance the token, its size (cols = F), the global header (min_value, range), payload_off, row0 (its
+ *     first row in the matrix) and tile0, the number of tiles of FHVAE_KALDI_CM_TILE_ROWS rows of the utterances before it
+ *     (n_tiles = the total).  A descriptor that breaks these rules or reaches outside a buffer sets
+ *     FHVAE_KALDI_CM_BAD_DESC in the int32 device word `status` (never cleared by the library) and nothing is written.
+ * decompress: f32, one rounding per operation, division correctly rounded, no contraction:
+ *     u(w) = min_value + (range * w) / 65535;  CM2: u(w);  CM3: min_value + (range * b) / 255;
+ *     CM, with P0, P25, P75, P100 = u(p0) .. u(p100) of the column: b <= 64: P0 + ((P25 - P0) * b) / 64; b <= 192:
+ *     P25 + ((P75 - P25) * (b - 64)) / 128; else P75 + ((P100 - P75) * (b - 192)) / 63.
+ * compress: the token is the caller's choice per utterance; min_value and range are WRITTEN to the descriptors: the
+ *     matrix minimum and max - min (1 + |min| for a constant matrix).  q16(v) = trunc(double(f32(clamp((v - min) / range,
+ *     0, 1) * 65535)) + 0.499), q8 with 255.  CM2 / CM3 store q16 / q8.  CM: with s the sorted column and q = rows / 4,
+ *     p0 = min(q16(s[0]), 65532), p25 = min(max(q16(s[q]), p0 + 1), 65533), p75 = min(max(q16(s[3q]), p25 + 1), 65534),
+ *     p100 = max(q16(s[rows-1]), p75 + 1) (the order statistics are exact for any number of rows); with
+ *     Pk = min + (range * 1.52590218966964e-05f) * pk a value below P25 is coded clamp(trunc(double(f * 64) + 0.5), 0, 64),
+ *     f = (v - P0) / (P25 - P0); below P75 64 + trunc(double((v - P25) / (P75 - P25) * 128) + 0.5) clamped to [64, 192];
+ *     else 192 + trunc(double((v - P75) / (P100 - P75) * 63) + 0.5) clamped to [192, 255].
+ *     ws: 2 U uint32 of device scratch.  A NaN or Inf in an utterance sets FHVAE_KALDI_CM_NONFINITE in `status`.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_KALDI_CM 1
+#define FHVAE_KALDI_CM2 2
+#define FHVAE_KALDI_CM3 3
+#define FHVAE_KALDI_CM_TILE_ROWS 128
+#define FHVAE_KALDI_CM_BAD_DESC 1
+#define FHVAE_KALDI_CM_NONFINITE 2
+typedef struct FhvaeKaldiCmDesc {
+  int32_t token, rows, cols, tile0;
+  float min_value, range;
+  int64_t payload_off, row0;
+} FhvaeKaldiCmDesc;
+int fhvae_kaldi_decompress(const uint8_t* payload, int64_t n_bytes, const FhvaeKaldiCmDesc* desc, int64_t U, int64_t n_tiles,
+                           float* out, int64_t n_frames, int64_t F, int32_t* status, void* stream);
+int fhvae_kaldi_compress(const float* feats, int64_t n_frames, int64_t F, FhvaeKaldiCmDesc* desc, int64_t U, int64_t n_tiles,
+                         uint32_t* ws, uint8_t* payload, int64_t n_bytes, int32_t* status, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

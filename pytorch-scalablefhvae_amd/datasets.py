@@ -165,14 +165,19 @@ def seq_csr(seq_nsegs, seg_seq):
 class ResidentSegmentPool:
     """All utterances of a NumpyDataset (or KaldiDataset) resident in HBM + device-side minibatch cutting (fhvae_segment_gather)."""
 
+    CM_BATCH_BYTES = 1 << 26  # bytes read from the archives per upload (and per decode launch), as features.BATCH_SAMPLES * 4
+
     def __init__(self, dataset: NumpyDataset, device="cuda"):
         import hip_binding as hb
 
         self.hb = hb
         self.T = dataset.seg_len
-        feats = [dataset.load_seq(i).astype(np.float32) for i in range(len(dataset.seq_feats))]
-        offs = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
-        self.pool = torch.from_numpy(np.concatenate(feats, axis=0)).to(device)  # (frames, F), one H2D copy per split
+        if isinstance(dataset, KaldiDataset):
+            self.pool, offs = self._kaldi_pool(dataset, device)
+        else:
+            feats = [dataset.load_seq(i).astype(np.float32) for i in range(len(dataset.seq_feats))]
+            offs = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
+            self.pool = torch.from_numpy(np.concatenate(feats, axis=0)).to(device)  # (frames, F), one H2D copy per split
         self.num_seqs = len(dataset)
         seq_of = np.array([dataset.seq2idx[s.seq] for s in dataset.segs], dtype=np.int64)
         self.seg_start = torch.from_numpy(offs[seq_of] + np.array([s.start for s in dataset.segs], dtype=np.int64)).to(device)
@@ -186,6 +191,53 @@ class ResidentSegmentPool:
             self.inv_std = torch.from_numpy((1.0 / np.asarray(dataset.mvn_params["std"], dtype=np.float64)).astype(np.float32).reshape(-1)).to(device)
         else:
             self.mean = self.inv_std = None
+
+    def _kaldi_pool(self, dataset, device):
+        """(pool (frames, F) f32 on the device, row offsets (S + 1,)) of a KaldiDataset.  Entries are read raw: runs of
+        uncompressed ones (FM, DM) are concatenated and copied as before; compressed ones (CM, CM2, CM3) are uploaded as the
+        bytes on disk, at most CM_BATCH_BYTES per batch, and decoded by one fhvae_kaldi_decompress launch per batch straight
+        into their rows of the pool -- bit for bit what kaldi_io_lite.load_mat gives.  An archive may mix both."""
+        from kaldi_io_lite import read_raw
+
+        hb = self.hb
+        raws = [read_raw(spec) for spec in dataset.seq_feats]
+        if not raws:
+            raise ValueError("no utterance to hold resident")
+        F = raws[0][4]
+        for spec, r in zip(dataset.seq_feats, raws):
+            if r[4] != F:
+                raise ValueError("%s: %d columns, the first utterance has %d" % (spec, r[4], F))
+        offs = np.concatenate([[0], np.cumsum([r[3] for r in raws])]).astype(np.int64)
+        pool = torch.empty((int(offs[-1]), F), dtype=torch.float32, device=device)
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+
+        def flush_plain(idx):
+            host = np.concatenate([raws[i][5].astype(np.float32, copy=False) for i in idx], axis=0)
+            pool[int(offs[idx[0]]):int(offs[idx[-1] + 1])].copy_(torch.from_numpy(host))
+
+        def flush_coded(idx):
+            desc, n_tiles, n_bytes = hb.kaldi_cm_descs([raws[i][0] for i in idx], [raws[i][3] for i in idx], F, offs[idx],
+                                                       [(raws[i][1], raws[i][2]) for i in idx])
+            host = torch.zeros(n_bytes, dtype=torch.uint8, pin_memory=True)
+            buf = host.numpy()
+            for i, off in zip(idx, desc["payload_off"]):
+                buf[int(off):int(off) + len(raws[i][5])] = np.frombuffer(raws[i][5], dtype=np.uint8)
+            hb.kaldi_decompress(host.to(device, non_blocking=True), torch.from_numpy(desc.view(np.uint8)).to(device), n_tiles, pool, status)
+
+        run, coded, size = [], False, 0
+        for i, r in enumerate(raws):
+            c = r[1] is not None
+            n = len(r[5]) if c else r[5].nbytes
+            if run and (c != coded or size + n > self.CM_BATCH_BYTES):
+                (flush_coded if coded else flush_plain)(np.array(run))
+                run, size = [], 0
+            run.append(i)
+            coded, size = c, size + n
+        (flush_coded if coded else flush_plain)(np.array(run))
+        st = int(status.cpu().item())
+        if st:
+            raise RuntimeError("fhvae_kaldi_decompress: status %d (inconsistent descriptors)" % st)
+        return pool, offs
 
     def __len__(self):
         return self.seg_start.shape[0]

@@ -1098,7 +1098,7 @@ class _KaldiBases:
         self.mel = torch.from_numpy(kaldi_mel_basis(sr, P, opts["num-mel-bins"], opts["low-freq"], opts["high-freq"])).to(device)
 
 
-def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device):
+def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device, compress=None, names=None):
     import torch
 
     N, S, P = sizes
@@ -1115,18 +1115,70 @@ def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device):
              | (hb.KALDI_USE_POWER if opts["use-power"] else 0))
     hb.kaldi_fbank_fwd(wave_d, ptrs_d[0], ptrs_d[1], ids_d, bases.dft, bases.mel, N, S, P, n_mels,
                        opts["preemphasis-coefficient"], dither, seed, flags, out, status)
-    return _download(out, (status,), "fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)", frame_ptr)
+    what = "fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)"
+    if compress is None:
+        return _download(out, (status,), what, frame_ptr)
+    st = int(status.cpu().item())
+    if st:
+        raise RuntimeError(what % st)
+    return kaldi_compress(out, np.diff(frame_ptr), compress, names)
+
+
+def kaldi_compress(feats, rows, method="auto", names=None):
+    """Codes the utterances stacked in `feats` ((frames, F) f32 on the device; utterance j is the next rows[j] rows) as Kaldi
+    compressed matrices on the device (fhvae_kaldi_compress) -> one kaldi_io_lite.CompressedMatrix each.  `method`: "auto"
+    (Kaldi's: CM above 8 rows, else CM2), "two-byte" (CM2) or "one-byte" (CM3).  Only the coded bytes and the (min, range)
+    headers come back from the device."""
+    import struct
+
+    import torch
+
+    import hip_binding as hb
+    import kaldi_io_lite as K
+
+    rows = [int(r) for r in rows]
+    F = int(feats.shape[1])
+    if sum(rows) != feats.shape[0] or min(rows) < 1:
+        raise ValueError("kaldi_compress: %d rows in all for a matrix of %d; every utterance needs a row" % (sum(rows), feats.shape[0]))
+    tokens = [K.token_for(r, method) for r in rows]
+    desc, n_tiles, n_bytes = hb.kaldi_cm_descs(tokens, rows, F, _ptr(rows)[:-1])
+    desc_d = torch.from_numpy(desc.view(np.uint8)).to(feats.device)
+    payload = torch.empty(n_bytes, dtype=torch.uint8, device=feats.device)
+    status = torch.zeros(1, dtype=torch.int32, device=feats.device)
+    hb.kaldi_compress(feats, desc_d, n_tiles, payload, status)
+    host = torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True)
+    host.copy_(payload, non_blocking=True)
+    got = desc_d.cpu().numpy().view(hb.KALDI_CM_DESC)
+    st = int(status.cpu().item())
+    if st & hb.KALDI_CM_NONFINITE:
+        bad = [j for j in range(len(rows)) if not (np.isfinite(got["min_value"][j]) and np.isfinite(got["range"][j]))]
+        raise ValueError("%s: NaN or Inf in the features to compress" % ", ".join((names[j] if names is not None else "utterance %d" % j) for j in bad))
+    if st:
+        raise RuntimeError("fhvae_kaldi_compress: status %d (inconsistent descriptors)" % st)
+    blob = host.numpy()
+    out = []
+    for j, (tok, r) in enumerate(zip(tokens, rows)):
+        off = int(desc["payload_off"][j])
+        out.append(K.CompressedMatrix(tok, struct.pack("<ffii", got["min_value"][j], got["range"][j], r, F),
+                                      blob[off:off + K.payload_size(tok, r, F)].tobytes()))
+    return out
 
 
 def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, device="cuda", max_samples=BATCH_SAMPLES,
-                        rates=None):
+                        rates=None, compress=None):
     """Kaldi filterbank features of every waveform -> list of float32 (nframes, num-mel-bins), in input order.  `waves` are
     float32 1-D arrays as read_wav returns them (full scale 1.0; they are put on Kaldi's int16 scale here) at the rate
     sample-frequency of `opts` (what kaldi_fbank_options takes: a config file, a dict, or None for Kaldi's defaults).  `seed` and `stream_ids` (one 64-bit
     integer per waveform, default its index) select the dither noise, which depends on nothing else: the same
     (seed, stream id) gives the same features in any batch.  `rates` (optional, one source rate per waveform): waveforms at
     another rate are first converted with `resample`; without it every waveform is taken to be at sample-frequency, as
-    Kaldi refuses other rates.  An utterance shorter than one frame is an error that names it (`names`)."""
+    Kaldi refuses other rates.  An utterance shorter than one frame is an error that names it (`names`).  With `compress`
+    ("auto", "two-byte" or "one-byte") the features stay on the device, are coded there as Kaldi compressed matrices
+    (kaldi_compress) and come back as kaldi_io_lite.CompressedMatrix (token, header, payload) instead of arrays."""
+    if compress is not None:
+        import kaldi_io_lite
+
+        kaldi_io_lite.token_for(1, compress)  # (an unknown method fails before any work)
     opts = kaldi_fbank_options(opts)
     sizes = check_kaldi_options(opts)
     sr = opts["sample-frequency"]
@@ -1156,5 +1208,5 @@ def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, d
     bases = _KaldiBases(opts, sizes[0], sizes[2], device)
     out = []
     for a, b in batches([len(w) for w in waves], max_samples):
-        out.extend(_kaldi_batch(hb, waves[a:b], ids[a:b], opts, sizes, int(seed), bases, device))
+        out.extend(_kaldi_batch(hb, waves[a:b], ids[a:b], opts, sizes, int(seed), bases, device, compress, names[a:b]))
     return out

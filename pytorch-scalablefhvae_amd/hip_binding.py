@@ -140,6 +140,8 @@ SIGNATURES = {
     "fhvae_kaldi_fbank_tile_rows": (C.c_int, [_i64, _i64, _i64]),
     "fhvae_kaldi_fbank_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, C.c_float, C.c_float,
                                         C.c_uint64, C.c_int, _vp, _vp, _vp]),
+    "fhvae_kaldi_decompress": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "fhvae_kaldi_compress": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "fhvae_synth_tile_rows": (C.c_int, [_i64]),
     "fhvae_synth_istft": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_synth_project": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.c_float, _i64, _i64, _vp, _vp, _vp, _vp]),
@@ -1455,6 +1457,69 @@ def kaldi_fbank_fwd(wave, wave_ptr, frame_ptr, stream_ids, dft_basis, mel_basis,
                                          _p(dft_basis), _p(mel_basis), frame_len, frame_shift, padded_len, n_mels, float(preemph),
                                          float(dither), int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), _p(out), _p(status), _stream()),
                "fhvae_kaldi_fbank_fwd")
+
+
+KALDI_CM_TOKENS = {"CM": 1, "CM2": 2, "CM3": 3}  # FHVAE_KALDI_CM*
+KALDI_CM_TILE_ROWS = 128  # FHVAE_KALDI_CM_TILE_ROWS
+KALDI_CM_BAD_DESC, KALDI_CM_NONFINITE = 1, 2
+#: FhvaeKaldiCmDesc
+KALDI_CM_DESC = np.dtype([("token", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("tile0", "<i4"), ("min_value", "<f4"), ("range", "<f4"),
+                          ("payload_off", "<i8"), ("row0", "<i8")])
+
+
+def kaldi_cm_descs(tokens, rows, cols, row0, headers=None):
+    """(descriptors (U,) KALDI_CM_DESC, n_tiles, n_bytes): utterance u has token tokens[u] ("CM" | "CM2" | "CM3"), rows[u] x cols
+    values, its first row at row0[u] of the matrix and (decode) the global header headers[u] = (min_value, range).  Payloads are
+    laid out one after the other, each on a multiple of 4 bytes; n_bytes (a multiple of 4) is the buffer they need."""
+    U = len(tokens)
+    d = np.zeros(U, dtype=KALDI_CM_DESC)
+    d["token"] = [KALDI_CM_TOKENS[t] for t in tokens]
+    d["rows"], d["cols"], d["row0"] = rows, cols, row0
+    r = d["rows"].astype(np.int64)
+    tiles = (r + KALDI_CM_TILE_ROWS - 1) // KALDI_CM_TILE_ROWS
+    d["tile0"] = np.concatenate([[0], np.cumsum(tiles)[:-1]])
+    size = np.where(d["token"] == 1, cols * (8 + r), np.where(d["token"] == 2, 2 * r * cols, r * cols))
+    size = (size + 3) // 4 * 4
+    d["payload_off"] = np.concatenate([[0], np.cumsum(size)[:-1]])
+    if headers is not None:
+        d["min_value"], d["range"] = [h[0] for h in headers], [h[1] for h in headers]
+    return d, int(tiles.sum()), int(size.sum())
+
+
+def _kaldi_cm_args(payload, desc, mat, status, what):
+    _need_gpu(payload, desc, mat, status)
+    if payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous() or payload.numel() % 4:
+        raise RuntimeError("%s takes the payloads as one contiguous uint8 buffer of a multiple of 4 bytes" % what)
+    if desc.dtype != torch.uint8 or not desc.is_contiguous() or desc.numel() == 0 or desc.numel() % KALDI_CM_DESC.itemsize:
+        raise RuntimeError("%s takes the descriptors as the bytes of a KALDI_CM_DESC array" % what)
+    if mat.dtype != torch.float32 or mat.dim() != 2 or not mat.is_contiguous():
+        raise RuntimeError("%s takes a contiguous 2-D f32 matrix" % what)
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise RuntimeError("%s: status must be one int32 word" % what)
+    return desc.numel() // KALDI_CM_DESC.itemsize
+
+
+def kaldi_decompress(payload, desc, n_tiles, out, status):
+    """Decodes a batch of compressed matrices into rows of `out` (n_frames, F) f32 in one launch (fhvae_kaldi_decompress):
+    payload (n_bytes,) uint8, desc the bytes of a KALDI_CM_DESC array (kaldi_cm_descs) as a uint8 tensor, status (1,) int32
+    (KALDI_CM_BAD_DESC when a descriptor breaks the layout rules: nothing is written)."""
+    U = _kaldi_cm_args(payload, desc, out, status, "kaldi_decompress")
+    lib = load_library()
+    with _Timed("fhvae_kaldi_decompress"):
+        _check(lib.fhvae_kaldi_decompress(_p(payload), payload.numel(), _p(desc), U, int(n_tiles), _p(out), out.shape[0], out.shape[1],
+                                          _p(status), _stream()), "fhvae_kaldi_decompress")
+
+
+def kaldi_compress(feats, desc, n_tiles, payload, status):
+    """Codes rows of `feats` (n_frames, F) f32 into `payload` (fhvae_kaldi_compress), the utterances, tokens and payload offsets
+    as `desc` names them (kaldi_cm_descs); the global headers (min_value, range) are written into `desc`.  status (1,) int32:
+    KALDI_CM_BAD_DESC, KALDI_CM_NONFINITE (a NaN or Inf among the values)."""
+    U = _kaldi_cm_args(payload, desc, feats, status, "kaldi_compress")
+    lib = load_library()
+    ws = torch.empty(2 * U, dtype=torch.int32, device=feats.device)
+    with _Timed("fhvae_kaldi_compress"):
+        _check(lib.fhvae_kaldi_compress(_p(feats), feats.shape[0], feats.shape[1], _p(desc), U, int(n_tiles), _p(ws), _p(payload),
+                                        payload.numel(), _p(status), _stream()), "fhvae_kaldi_compress")
 
 
 RESAMPLE_BAD_PTR = 1  # FHVAE_RESAMPLE_BAD_PTR

@@ -3,11 +3,13 @@
 features.compute_kaldi_fbank on the MI355X and kaldi_io_lite; no Kaldi binary is run).
 
     python pytorch-scalablefhvae_amd/prepare_kaldi_data.py DATASET_DIR [--fbank_conf ./misc/fbank.conf] [--set_name train]
-        [--seed 0] [--resample]
+        [--seed 0] [--resample] [--compress [--compression-method auto]]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<key> <path>"
 lines) and writes, in wav.scp order, <DATASET_DIR>/<set>/feats.ark (binary archive of float32 matrices), feats.scp
-("<key> <feats.ark>:<offset>") and len.scp ("<key> <nframes>").  --fbank_conf is a Kaldi config file the user supplies,
+("<key> <feats.ark>:<offset>") and len.scp ("<key> <nframes>").  With --compress the archive holds Kaldi compressed
+matrices (what copy-feats --compress=true writes, about a quarter of the size): the features are coded on the GPU and only
+the bytes are downloaded; --compression-method picks Kaldi's automatic method (default), "two-byte" or "one-byte".  --fbank_conf is a Kaldi config file the user supplies,
 one option per line, for example
 
     --window-type=hamming
@@ -62,10 +64,11 @@ def read_wav_scp(path):
     return entries
 
 
-def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None):
+def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None,
+                  compress=None):
     """prepare_kaldi_data.py:10-82: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (dataset_dir, feats.ark, feats.scp, len.scp)).  `timings` (optional dict) receives seconds spent in
-    "read", "gpu" and "write"."""
+    "read", "gpu" and "write".  `compress`: None (float32 matrices) or a method of kaldi_io_lite.METHODS."""
     opts = features.kaldi_fbank_options(fbank_conf)
     sr = int(opts["sample-frequency"])
     set_dir = Path(dataset_dir) / set_name
@@ -104,7 +107,7 @@ def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_r
                 feats = features.compute_kaldi_fbank([g[2] for g in got], opts, seed=seed,
                                                      stream_ids=[features.kaldi_stream_id(g[0]) for g in got],
                                                      names=["%s (%s)" % (g[0], g[1]) for g in got],
-                                                     rates=[g[3] for g in got] if resample else None)
+                                                     rates=[g[3] for g in got] if resample else None, compress=compress)
                 dt = time.time() - t0
                 t["gpu"] += dt
                 t0 = time.time()
@@ -130,6 +133,9 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0, help="Seed of the dither noise")
     p.add_argument("--resample", action="store_true",
                    help="Convert files whose rate differs from the configuration's sample-frequency on the GPU")
+    p.add_argument("--compress", action="store_true", help="Write Kaldi compressed matrices (coded on the GPU), as copy-feats --compress=true does")
+    p.add_argument("--compression-method", type=str, default="auto", choices=list(kaldi_io_lite.METHODS),
+                   help="With --compress: Kaldi's automatic method (one byte with column headers; two bytes up to 8 frames), or two or one byte per value")
     return p
 
 
@@ -143,7 +149,8 @@ def main(argv=None):
     total = 0
     try:
         for s in sets:
-            total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample)[0]
+            total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample,
+                                   compress=args.compression_method if args.compress else None)[0]
     except ValueError as e:
         print("prepare_kaldi_data: %s" % e, file=sys.stderr)
         return 1

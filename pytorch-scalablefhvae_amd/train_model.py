@@ -74,7 +74,7 @@ def build_parser() -> argparse.ArgumentParser:
     # real features in the reference's on-disk format (feats.scp / len.scp of .npy files, prepare_numpy_data.py:115-119)
     p.add_argument("--data-format", default="numpy", choices=["numpy", "kaldi"],              # train_model.py:38-43
                    help="what the feat-scp files point at: .npy files (prepare_numpy_data.py) or Kaldi archives "
-                        "(prepare_kaldi_data.py, or any Kaldi recipe's uncompressed feats.scp)")
+                        "(prepare_kaldi_data.py, or any Kaldi recipe's feats.scp, compressed or not)")
     p.add_argument("--train-feat-scp", default=None)
     p.add_argument("--train-len-scp", default=None)
     p.add_argument("--dev-feat-scp", default=None)
