@@ -700,6 +700,42 @@ int fhvae_kaldi_decompress(const uint8_t* payload, int64_t n_bytes, const FhvaeK
 int fhvae_kaldi_compress(const float* feats, int64_t n_frames, int64_t F, FhvaeKaldiCmDesc* desc, int64_t U, int64_t n_tiles,
                          uint32_t* ws, uint8_t* payload, int64_t n_bytes, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FLAC decoding (csrc/flac.hip): the frames of a batch of U files, RFC 9639, up to 24 bits per sample and 8 channels
+ * (additions of ABI 11).  The host parses the container (flac_lite.py) and passes what follows each file's metadata.
+ *   buf (n_bytes) uint8: the files' frame bytes one after the other.
+ *   desc (U): per file its byte range [byte_begin, byte_end) in buf (ascending, not overlapping), STREAMINFO's rate,
+ *     channels, bits per sample and minimum block size, and where its samples go: int32 elements
+ *     [out_off, out_off + n_samples * channels) of `out`, interleaved (sample, channel).
+ * scan:   info[p] for every byte position p: 0, or FHVAE_FLAC_CAND | block size << 8 | header bytes where a frame header
+ *     starts that is well formed, agrees with the file's STREAMINFO and carries its CRC-8.
+ * decode: one work item per candidate position cand_pos[i] (a header as the scan accepts it).  With out == NULL the frame
+ *     is parsed to its end and its CRC-16 verified; with out != NULL it is decoded into its file's part of `out` at its
+ *     coded sample position (the CRC-16 is not computed again).  Per candidate: cand_status (FHVAE_OK or a code below),
+ *     cand_end (the byte position behind the frame, -1 unless FHVAE_OK) and cand_spos (the coded sample number, or the
+ *     coded frame number times min_block).  Which candidates are frames -- the chain from the first byte of a file, each
+ *     frame starting where the one before ends -- is for the caller to decide between the two calls.
+ *     No read leaves a file's byte range and no write its part of `out`, whatever the bytes say.
+ * ------------------------------------------------------------------------------------------ */
+#define FHVAE_FLAC_CAND 0x80000000u
+#define FHVAE_FLAC_BAD_DESC 1     /* cand_pos in no file, or a descriptor that breaks the rules above */
+#define FHVAE_FLAC_BAD_HEADER 2   /* no acceptable frame header at cand_pos */
+#define FHVAE_FLAC_BAD_SUBFRAME 3 /* padding bit set, reserved type, wasted bits >= sample size, order > block size */
+#define FHVAE_FLAC_BAD_LPC 4      /* coefficient precision code 1111 or a negative shift */
+#define FHVAE_FLAC_BAD_RESIDUAL 5 /* reserved coding method, partitions that do not divide the block, residual > 32 bits */
+#define FHVAE_FLAC_TRUNCATED 6    /* the frame needs bytes behind the end of its file */
+#define FHVAE_FLAC_BAD_PADDING 7  /* non-zero bits before the byte boundary that ends the frame */
+#define FHVAE_FLAC_BAD_CRC 8      /* CRC-16 mismatch */
+#define FHVAE_FLAC_BAD_RANGE 9    /* the frame's samples do not fit its file's part of out */
+typedef struct FhvaeFlacDesc {
+  int64_t byte_begin, byte_end, out_off, n_samples;
+  int32_t rate, channels, bps, min_block;
+} FhvaeFlacDesc;
+int fhvae_flac_scan(const uint8_t* buf, int64_t n_bytes, const FhvaeFlacDesc* desc, int64_t U, uint32_t* info, void* stream);
+int fhvae_flac_decode(const uint8_t* buf, int64_t n_bytes, const FhvaeFlacDesc* desc, int64_t U, const int64_t* cand_pos,
+                      int64_t n_cand, int32_t* cand_status, int64_t* cand_end, int64_t* cand_spos, int32_t* out, int64_t n_out,
+                      void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

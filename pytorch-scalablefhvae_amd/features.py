@@ -6,6 +6,11 @@ AudioUtils.stft / rstft / to_melspec, utils.py:155-272).  Here the arithmetic ru
 
   read_wav            RIFF WAV, integer PCM (8-bit unsigned, 16, 24, 32-bit) -> float32 mono, scaled like soundfile
                       (int16 / 2**15, int24 / 2**23, int32 / 2**31, (u8 - 128) / 128); channels averaged.  No resampling here.
+  decode_flac         native FLAC files (bytes) -> int32 (n, channels) samples, decoded on the device (csrc/flac.hip: fhvae_flac_scan
+                      finds the frame headers, fhvae_flac_decode parses and decodes the frames; the container is flac_lite.py)
+  read_sphere         NIST SPHERE (TIMIT's .WAV), uncompressed PCM -> float32 mono like read_wav
+  read_audio / read_audio_batch
+                      any of the three by its first bytes (RIFF, fLaC, NIST_1A); the batch decodes all its FLAC files together
   frame_sizes         n_fft = win_length = int(sr * win_t), hop = int(sr * hop_t) (the reference's truncation)
   dft_basis           windowed cos / -sin columns (periodic Hamming), built in float64, rounded to f32, padded for the kernel
   mel_filters         librosa.filters.mel(sr, n_fft', n_mels, fmin=0, fmax=sr/2, htk=False, norm='slaney') in float64, with
@@ -88,6 +93,234 @@ def read_wav(path, channel=None):
         raise ValueError("%s: no channel %d in a file of %d channel(s)" % (path, channel, nch))
     y = x[:, channel or 0] if nch == 1 or channel is not None else x.mean(axis=1, dtype=np.float32)
     return np.ascontiguousarray(y, dtype=np.float32), sr
+
+
+def pcm_to_float(v, bps, channel=None, where="audio"):
+    """The integer -> float32 mono step shared by the FLAC and SPHERE readers, in read_wav's expressions: `v` (n, channels)
+    integers of `bps` bits -> v / 2**(bps - 1) in float32, then the float32 channel mean, or channel `channel`.  The same
+    samples therefore give the same waveform bit for bit whichever container held them."""
+    n, nch = v.shape
+    x = v.astype(np.float32) / float(1 << (bps - 1))
+    if channel is not None and not 0 <= channel < nch:
+        raise ValueError("%s: no channel %d in a file of %d channel(s)" % (where, channel, nch))
+    y = x[:, channel or 0] if nch == 1 or channel is not None else x.mean(axis=1, dtype=np.float32)
+    return np.ascontiguousarray(y, dtype=np.float32)
+
+
+SPHERE_MAGIC = b"NIST_1A\n"
+AUDIO_MAGICS = "RIFF (WAV), fLaC (FLAC) or NIST_1A (SPHERE)"
+
+
+def _sphere_samples(raw, path):
+    """(int (n, channels) samples, sample rate, bits) of a SPHERE file's bytes."""
+    try:
+        size = int(raw[8:16].split()[0])
+        lines = raw[16:size].decode("ascii", "replace").split("\n")
+    except (ValueError, IndexError):
+        raise ValueError("%s: malformed SPHERE header (no header size after NIST_1A)" % path) from None
+    if size < 16 or size > len(raw):
+        raise ValueError("%s: SPHERE header of %d bytes in a file of %d" % (path, size, len(raw)))
+    fields, ended = {}, False
+    for line in lines:
+        line = line.strip()
+        if line == "end_head":
+            ended = True
+            break
+        parts = line.split(None, 2)
+        if len(parts) == 3 and parts[1].startswith("-") and not line.startswith(";"):
+            fields[parts[0]] = parts[2]
+    if not ended:
+        raise ValueError("%s: SPHERE header without end_head" % path)
+    coding = fields.get("sample_coding", "pcm")
+    if coding != "pcm":
+        raise ValueError("%s: SPHERE sample_coding %s is not supported (only uncompressed pcm; decode shorten / wavpack / ulaw files "
+                         "with sph2pipe first)" % (path, coding))
+    try:
+        sr, nch, width = int(fields["sample_rate"]), int(fields.get("channel_count", 1)), int(fields["sample_n_bytes"])
+        n = int(fields["sample_count"])
+    except KeyError as e:
+        raise ValueError("%s: SPHERE header lacks %s" % (path, e.args[0])) from None
+    order = fields.get("sample_byte_format", "1" if width == 1 else None)
+    want = {1: ("1",), 2: ("01", "10")}.get(width)
+    if want is None or nch < 1:
+        raise ValueError("%s: unsupported SPHERE sample_n_bytes %d (1 or 2) or channel_count %d" % (path, width, nch))
+    if order not in want:
+        raise ValueError("%s: SPHERE sample_byte_format %r for %d-byte samples (expected %s)" % (path, order, width, " or ".join(want)))
+    if size + n * nch * width > len(raw):
+        raise ValueError("%s: truncated: %d samples of %d channel(s) need %d bytes behind the header, the file has %d"
+                         % (path, n, nch, n * nch * width, len(raw) - size))
+    dt = np.int8 if width == 1 else np.dtype("<i2" if order == "01" else ">i2")
+    v = np.frombuffer(raw, dtype=dt, count=n * nch, offset=size).reshape(n, nch)
+    return v, sr, 8 * width
+
+
+def read_sphere(path, channel=None):
+    """NIST SPHERE (what TIMIT's .WAV files are) -> (samples float32 (n,), sample rate), scaled and mixed like read_wav.
+    Uncompressed PCM of 1 or 2 bytes in either byte order; shorten / wavpack compressed files and ulaw are refused by name."""
+    with open(str(path), "rb") as fh:
+        raw = fh.read()
+    if raw[:8] != SPHERE_MAGIC:
+        raise ValueError("%s: not a SPHERE file (no NIST_1A header)" % path)
+    v, sr, bps = _sphere_samples(raw, path)
+    return pcm_to_float(v, bps, channel, path), sr
+
+
+def _flac_md5(x, bps):
+    import hashlib
+
+    width = (bps + 7) // 8
+    if width == 3:
+        raw = np.ascontiguousarray(x.astype("<i4")).view(np.uint8).reshape(-1, 4)[:, :3].tobytes()
+    else:
+        raw = x.astype({1: "<i1", 2: "<i2", 4: "<i4"}[width]).tobytes()
+    return hashlib.md5(raw).digest()
+
+
+def _flac_batch(hb, blobs, infos, names, device, verify_md5):
+    """decode_flac for files that fit one pair of buffers: scan, parse every candidate, walk the chains on the host, decode the
+    chains' frames."""
+    import torch
+
+    U = len(blobs)
+    lens = [len(b) - i.first_frame for b, i in zip(blobs, infos)]
+    ptr = _ptr(lens)
+    n_bytes = int(ptr[-1])
+    desc = np.zeros(U, dtype=hb.FLAC_DESC)
+    desc["byte_begin"], desc["byte_end"] = ptr[:-1], ptr[1:]
+    desc["rate"], desc["channels"], desc["bps"] = [i.sample_rate for i in infos], [i.channels for i in infos], [i.bps for i in infos]
+    desc["min_block"] = [i.min_block for i in infos]
+    counts = [0] * U
+    chain = []
+    if n_bytes:
+        host = torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True)
+        hv = host.numpy()
+        for j, (b, i) in enumerate(zip(blobs, infos)):
+            hv[ptr[j]:ptr[j + 1]] = np.frombuffer(b, dtype=np.uint8, offset=i.first_frame)
+        buf = host.to(device, non_blocking=True)
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(device)
+        info = torch.empty(n_bytes, dtype=torch.int32, device=device)
+        hb.flac_scan(buf, desc_d, info)
+        cand = torch.nonzero(info).flatten()
+        nc = cand.numel()
+        if nc:
+            st, end, spos = (torch.empty(nc, dtype=dt, device=device) for dt in (torch.int32, torch.int64, torch.int64))
+            hb.flac_decode(buf, desc_d, cand, st, end, spos)
+            words = info[cand].cpu().numpy()
+            pos_h, st_h, end_h, spos_h = (t.cpu().numpy() for t in (cand, st, end, spos))
+            bs_l = ((words & 0x7FFFFFFF) >> 8).tolist()
+            nxt = np.searchsorted(pos_h, end_h)  # the candidate that starts where this one ends, when there is one
+            linked = (pos_h[np.minimum(nxt, nc - 1)] == end_h).tolist()
+            nxt_l, st_l, end_l, spos_l = nxt.tolist(), st_h.tolist(), end_h.tolist(), spos_h.tolist()
+            first = np.searchsorted(pos_h, ptr[:-1])
+        # the chain of a file: the frame at its first byte, then the one that starts where it ends, to the end of the file
+        for j in range(U):
+            p, e, expect = int(ptr[j]), int(ptr[j + 1]), 0
+            where = lambda q: infos[j].first_frame + q - int(ptr[j])  # noqa: E731
+            if p < e:
+                k = int(first[j]) if nc else 0
+                ok = nc > 0 and k < nc and int(pos_h[k]) == p
+                while True:
+                    if not ok:
+                        raise ValueError("%s: no valid frame header at byte offset %d, where the chain of frames leads (a broken or "
+                                         "truncated FLAC stream)" % (names[j], where(p)))
+                    if st_l[k] != 0:
+                        raise ValueError("%s: the frame at byte offset %d is broken: %s" % (names[j], where(p), hb.FLAC_STATUS.get(st_l[k], st_l[k])))
+                    if spos_l[k] != expect:
+                        raise ValueError("%s: the frame at byte offset %d starts at sample %d, the frames before it end at %d"
+                                         % (names[j], where(p), spos_l[k], expect))
+                    chain.append(k)
+                    expect += bs_l[k]
+                    p = end_l[k]
+                    if p >= e:
+                        break
+                    ok, k = linked[k], nxt_l[k]
+            if infos[j].total_samples and expect != infos[j].total_samples:
+                raise ValueError("%s: the frames up to byte offset %d hold %d samples, STREAMINFO announces %d"
+                                 % (names[j], where(p), expect, infos[j].total_samples))
+            counts[j] = expect
+    elems = [c * i.channels for c, i in zip(counts, infos)]
+    optr = _ptr(elems)
+    res = np.zeros(0, dtype=np.int32)
+    if chain:
+        desc["out_off"], desc["n_samples"] = optr[:-1], counts
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(device)
+        cpos = cand[torch.from_numpy(np.asarray(chain, dtype=np.int64)).to(device)]
+        m = cpos.numel()
+        st, end, spos = (torch.empty(m, dtype=dt, device=device) for dt in (torch.int32, torch.int64, torch.int64))
+        out = torch.empty(int(optr[-1]), dtype=torch.int32, device=device)
+        hb.flac_decode(buf, desc_d, cpos, st, end, spos, out)
+        pinned = torch.empty(out.shape, dtype=torch.int32, pin_memory=True)
+        pinned.copy_(out, non_blocking=True)
+        bad = int((st != 0).sum().cpu().item())  # (synchronises: the copy is done too)
+        if bad:
+            raise RuntimeError("fhvae_flac_decode: %d frame(s) that parsed in the first pass failed in the second" % bad)
+        res = pinned.numpy()
+    out = []
+    for j, i in enumerate(infos):
+        x = res[optr[j]:optr[j + 1]].reshape(counts[j], i.channels).copy()
+        if verify_md5 and i.md5 != bytes(16) and _flac_md5(x, i.bps) != i.md5:
+            raise ValueError("%s: MD5 of the decoded audio %s differs from STREAMINFO's %s" % (names[j], _flac_md5(x, i.bps).hex(), i.md5.hex()))
+        out.append((x, i.sample_rate, i.bps))
+    return out
+
+
+def decode_flac(blobs, names=None, device="cuda", verify_md5=False, max_samples=BATCH_SAMPLES):
+    """Native FLAC files, each the bytes of a whole file -> list of (int32 (n, channels) samples, sample rate, bits per sample),
+    decoded on the device in batches of about `max_samples` samples.  A stream that is broken anywhere -- a frame that does
+    not parse, a CRC-16 mismatch, frames that do not follow each other, a sample count other than STREAMINFO's -- is a
+    ValueError naming the file (`names`) and the byte offset.  `verify_md5`: also compare the MD5 of the decoded audio with
+    STREAMINFO's (an all-zero one means "not set" and is skipped)."""
+    import flac_lite
+
+    names = list(names) if names is not None else ["FLAC file %d" % j for j in range(len(blobs))]
+    if len(names) != len(blobs):
+        raise ValueError("names must have one entry per file (%d)" % len(blobs))
+    infos = [flac_lite.parse_flac(b, n) for b, n in zip(blobs, names)]
+    if not blobs:
+        return []
+    import hip_binding as hb
+
+    # a batch is bounded by its decoded size; a file of unknown length counts as 4 samples per byte, a compression speech does not reach
+    sizes = [(i.total_samples or 4 * len(b)) * i.channels for b, i in zip(blobs, infos)]
+    out = []
+    for a, b in batches(sizes, max_samples):
+        out.extend(_flac_batch(hb, blobs[a:b], infos[a:b], names[a:b], device, verify_md5))
+    return out
+
+
+def read_audio_batch(paths, channel=None, verify_md5=False, threads=8):
+    """read_audio for many files -> list of (samples float32 (n,), sample rate) in input order.  Files are read by `threads`
+    threads; WAV and SPHERE files are converted on the host as they are read, all FLAC files are decoded together on the device."""
+    import concurrent.futures as cf
+
+    def load(path):
+        with open(str(path), "rb") as fh:
+            head = fh.read(8)
+            if head[:4] == b"fLaC" or head[:3] == b"ID3" or head[:4] == b"OggS":  # (the last two: flac_lite says why not)
+                return head + fh.read()
+        if head[:4] == b"RIFF":
+            return read_wav(path, channel)
+        if head == SPHERE_MAGIC:
+            return read_sphere(path, channel)
+        raise ValueError("%s: unknown audio format (the first bytes are %r); supported: %s" % (path, head, AUDIO_MAGICS))
+
+    paths = list(paths)
+    if threads > 1 and len(paths) > 1:
+        with cf.ThreadPoolExecutor(max_workers=threads) as pool:
+            got = list(pool.map(load, paths))
+    else:
+        got = [load(p) for p in paths]
+    idx = [j for j, g in enumerate(got) if isinstance(g, bytes)]
+    if idx:
+        dec = decode_flac([got[j] for j in idx], [str(paths[j]) for j in idx], verify_md5=verify_md5)
+        for j, (x, sr, bps) in zip(idx, dec):
+            got[j] = (pcm_to_float(x, bps, channel, paths[j]), sr)
+    return got
+
+
+def read_audio(path, channel=None):
+    """What read_wav returns, for a RIFF WAV, a native FLAC or a NIST SPHERE file, told apart by their first bytes."""
+    return read_audio_batch([path], channel)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------- sizes, bases

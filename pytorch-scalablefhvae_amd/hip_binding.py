@@ -142,6 +142,8 @@ SIGNATURES = {
                                         C.c_uint64, C.c_int, _vp, _vp, _vp]),
     "fhvae_kaldi_decompress": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "fhvae_kaldi_compress": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "fhvae_flac_scan": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "fhvae_flac_decode": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fhvae_synth_tile_rows": (C.c_int, [_i64]),
     "fhvae_synth_istft": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_synth_project": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.c_float, _i64, _i64, _vp, _vp, _vp, _vp]),
@@ -1520,6 +1522,55 @@ def kaldi_compress(feats, desc, n_tiles, payload, status):
     with _Timed("fhvae_kaldi_compress"):
         _check(lib.fhvae_kaldi_compress(_p(feats), feats.shape[0], feats.shape[1], _p(desc), U, int(n_tiles), _p(ws), _p(payload),
                                         payload.numel(), _p(status), _stream()), "fhvae_kaldi_compress")
+
+
+FLAC_CAND = 0x80000000  # FHVAE_FLAC_CAND
+#: FHVAE_FLAC_* status of a candidate
+FLAC_STATUS = {0: "ok", 1: "position in no file (bad descriptor)", 2: "no valid frame header", 3: "invalid subframe header",
+               4: "invalid LPC precision or shift", 5: "invalid residual coding", 6: "the frame runs past the end of the file",
+               7: "non-zero padding bits at the end of the frame", 8: "frame CRC-16 mismatch", 9: "samples outside the file's output range"}
+#: FhvaeFlacDesc
+FLAC_DESC = np.dtype([("byte_begin", "<i8"), ("byte_end", "<i8"), ("out_off", "<i8"), ("n_samples", "<i8"), ("rate", "<i4"),
+                      ("channels", "<i4"), ("bps", "<i4"), ("min_block", "<i4")])
+
+
+def _flac_args(buf, desc, what):
+    _need_gpu(buf, desc)
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() == 0:
+        raise RuntimeError("%s takes the frame bytes as one contiguous uint8 buffer" % what)
+    if desc.dtype != torch.uint8 or not desc.is_contiguous() or desc.numel() == 0 or desc.numel() % FLAC_DESC.itemsize:
+        raise RuntimeError("%s takes the descriptors as the bytes of a FLAC_DESC array" % what)
+    return desc.numel() // FLAC_DESC.itemsize
+
+
+def flac_scan(buf, desc, info):
+    """Stage 1 (fhvae_flac_scan): buf (n_bytes,) uint8 frame bytes of a batch of files, desc the bytes of a FLAC_DESC array as a
+    uint8 tensor, info (n_bytes,) int32 out: per byte position 0, or FLAC_CAND | block size << 8 | header bytes."""
+    U = _flac_args(buf, desc, "flac_scan")
+    _need_gpu(info)
+    if info.dtype != torch.int32 or info.numel() != buf.numel() or not info.is_contiguous():
+        raise RuntimeError("flac_scan: info must be one int32 per byte of buf")
+    lib = load_library()
+    with _Timed("fhvae_flac_scan"):
+        _check(lib.fhvae_flac_scan(_p(buf), buf.numel(), _p(desc), U, _p(info), _stream()), "fhvae_flac_scan")
+
+
+def flac_decode(buf, desc, cand_pos, cand_status, cand_end, cand_spos, out=None):
+    """Stage 2 (fhvae_flac_decode), one work item per candidate position cand_pos (n,) int64.  out None: parse every candidate to
+    its end and verify its CRC-16; out (n_out,) int32: decode the candidates into it.  cand_status (n,) int32 (FLAC_STATUS),
+    cand_end (n,) int64 (byte position behind the frame, -1 on error), cand_spos (n,) int64 (first sample of the frame)."""
+    U = _flac_args(buf, desc, "flac_decode")
+    _need_gpu(cand_pos, cand_status, cand_end, cand_spos, out)
+    n = cand_pos.numel()
+    for t, dt in ((cand_pos, torch.int64), (cand_status, torch.int32), (cand_end, torch.int64), (cand_spos, torch.int64)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError("flac_decode: the per-candidate arrays are contiguous (n,) int64 / int32 / int64 / int64")
+    if out is not None and (out.dtype != torch.int32 or out.dim() != 1 or not out.is_contiguous()):
+        raise RuntimeError("flac_decode: out is a contiguous 1-D int32 tensor")
+    lib = load_library()
+    with _Timed("fhvae_flac_decode"):
+        _check(lib.fhvae_flac_decode(_p(buf), buf.numel(), _p(desc), U, _p(cand_pos), n, _p(cand_status), _p(cand_end), _p(cand_spos),
+                                     _p(out), 0 if out is None else out.numel(), _stream()), "fhvae_flac_decode")
 
 
 RESAMPLE_BAD_PTR = 1  # FHVAE_RESAMPLE_BAD_PTR

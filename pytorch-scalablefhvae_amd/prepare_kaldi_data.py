@@ -1,9 +1,9 @@
-"""prepare_kaldi_data.py -- WAV files listed in wav.scp -> Kaldi filterbank features in the Kaldi layout the loaders read
+"""prepare_kaldi_data.py -- audio files (WAV, FLAC or SPHERE) listed in wav.scp -> Kaldi filterbank features in the Kaldi layout the loaders read
 (the reference's prepare_kaldi_data.py:10-136, with compute-fbank-feats and feat-to-len replaced by
 features.compute_kaldi_fbank on the MI355X and kaldi_io_lite; no Kaldi binary is run).
 
     python pytorch-scalablefhvae_amd/prepare_kaldi_data.py DATASET_DIR [--fbank_conf ./misc/fbank.conf] [--set_name train]
-        [--seed 0] [--resample] [--compress [--compression-method auto]]
+        [--seed 0] [--resample] [--compress [--compression-method auto]] [--verify-md5]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<key> <path>"
 lines) and writes, in wav.scp order, <DATASET_DIR>/<set>/feats.ark (binary archive of float32 matrices), feats.scp
@@ -23,7 +23,9 @@ Differences from the reference:
   * --kaldi_root is accepted and ignored.
   * dither noise comes from a counter-based generator keyed by --seed and zlib.crc32 of the utterance key, so a file's
     features are reproducible and do not depend on its place in wav.scp (Kaldi's rand() stream is neither).
-  * only plain "<key> <path>" entries: a line ending in "|" (a Kaldi pipe) is refused.  Integer PCM WAV only.
+  * only plain "<key> <path>" entries: a line ending in "|" (a Kaldi pipe) is refused.  The files are read by
+    features.read_audio_batch: integer PCM WAV, native FLAC (decoded on the GPU; --verify-md5 also checks the decoded audio
+    against the MD5 in each file) and uncompressed NIST SPHERE, so a LibriSpeech or TIMIT wav.scp needs no sox / sph2pipe pipe.
   * a multi-channel file contributes channel 0, as Kaldi reads it (prepare_numpy_data.py averages the channels).
   * a file whose rate differs from sample-frequency is an error, as in Kaldi, unless --resample converts it on the GPU
     (features.resample); a file shorter than one frame is an error that names it (Kaldi skips it with a warning).
@@ -65,7 +67,7 @@ def read_wav_scp(path):
 
 
 def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None,
-                  compress=None):
+                  compress=None, verify_md5=False):
     """prepare_kaldi_data.py:10-82: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (dataset_dir, feats.ark, feats.scp, len.scp)).  `timings` (optional dict) receives seconds spent in
     "read", "gpu" and "write".  `compress`: None (float32 matrices) or a method of kaldi_io_lite.METHODS."""
@@ -83,21 +85,20 @@ def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_r
     start_time = time.time()
     lens = []
 
-    def load(entry):
-        key, path = entry
-        y, rate = features.read_wav(path, channel=0)
-        return key, path, y, rate
+    def load(chunk):
+        got = features.read_audio_batch([path for _, path in chunk], channel=0, verify_md5=verify_md5, threads=READ_THREADS)
+        return [(key, path, y, rate) for (key, path), (y, rate) in zip(chunk, got)]
 
     def items():
         chunks = [entries[i:i + CHUNK_FILES] for i in range(0, len(entries), CHUNK_FILES)]
-        with cf.ThreadPoolExecutor(max_workers=READ_THREADS) as pool:
-            pending = [pool.submit(load, e) for e in chunks[0]] if chunks else []
+        with cf.ThreadPoolExecutor(max_workers=1) as pool:
+            pending = pool.submit(load, chunks[0]) if chunks else None
             for ci in range(len(chunks)):
                 t0 = time.time()
-                got = [f.result() for f in pending]
+                got = pending.result()
                 t["read"] += time.time() - t0
-                # the next chunk's files are read while this one is on the GPU and being written
-                pending = [pool.submit(load, e) for e in chunks[ci + 1]] if ci + 1 < len(chunks) else []
+                # the next chunk's files are read (and its FLAC files decoded) while this one is on the GPU and being written
+                pending = pool.submit(load, chunks[ci + 1]) if ci + 1 < len(chunks) else None
                 if not resample:
                     for key, path, _, rate in got:
                         if rate != sr:
@@ -133,6 +134,7 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0, help="Seed of the dither noise")
     p.add_argument("--resample", action="store_true",
                    help="Convert files whose rate differs from the configuration's sample-frequency on the GPU")
+    p.add_argument("--verify-md5", action="store_true", help="Check every FLAC file's decoded audio against the MD5 it carries")
     p.add_argument("--compress", action="store_true", help="Write Kaldi compressed matrices (coded on the GPU), as copy-feats --compress=true does")
     p.add_argument("--compression-method", type=str, default="auto", choices=list(kaldi_io_lite.METHODS),
                    help="With --compress: Kaldi's automatic method (one byte with column headers; two bytes up to 8 frames), or two or one byte per value")
@@ -150,7 +152,7 @@ def main(argv=None):
     try:
         for s in sets:
             total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample,
-                                   compress=args.compression_method if args.compress else None)[0]
+                                   compress=args.compression_method if args.compress else None, verify_md5=args.verify_md5)[0]
     except ValueError as e:
         print("prepare_kaldi_data: %s" % e, file=sys.stderr)
         return 1

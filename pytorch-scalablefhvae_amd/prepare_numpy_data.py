@@ -1,8 +1,8 @@
-"""prepare_numpy_data.py -- WAV files listed in wav.scp -> the numpy feature layout the loaders read (the reference's
+"""prepare_numpy_data.py -- audio files (WAV, FLAC or SPHERE) listed in wav.scp -> the numpy feature layout the loaders read (the reference's
 prepare_numpy_data.py:50-205, with the features computed on the MI355X by features.compute_features).
 
     python pytorch-scalablefhvae_amd/prepare_numpy_data.py DATASET_DIR [--np_dir OUT] [--set_name train]
-        [--ftype {fbank,spec}] [--sr RATE] [--resample] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80]
+        [--ftype {fbank,spec}] [--sr RATE] [--resample] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80] [--verify-md5]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<seq> <path>"
 lines) and writes, in wav.scp order, <OUT>/<set>/<seq>.npy (float32, (nframes, n_mels) or (nframes, n_fft // 2 + 1)) plus
@@ -15,7 +15,9 @@ Differences from the reference:
     file's rate is an error.  With --resample (which needs --sr, the target rate) files at other rates are converted to
     --sr on the GPU as the reference's librosa.load does (resampy kaiser_best; features.resample); files already at --sr
     go through unchanged.  The reference always resampled.
-  * integer PCM WAV only (features.read_wav); sets run one after the other on the GPU instead of a pool of 3 processes.
+  * files are read by features.read_audio_batch: integer PCM WAV, native FLAC (decoded on the GPU, a chunk of files per
+    launch; --verify-md5 also checks the decoded audio against the MD5 in each file) and uncompressed NIST SPHERE, told
+    apart by their first bytes; sets run one after the other on the GPU instead of a pool of 3 processes.
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ def read_wav_scp(path):
 
 
 def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank", sample_rate=None, win_t=0.025, hop_t=0.010,
-                  n_mels=80, timings=None, resample=False):
+                  n_mels=80, timings=None, resample=False, verify_md5=False):
     """prepare_numpy_data.py:50-129: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (wav_path, feat_path, len_path)).  `timings` (optional dict) receives seconds spent in "read", "gpu"
     and "write".  `resample`: files whose rate differs from `sample_rate` (required then) are converted to it on the GPU."""
@@ -63,21 +65,19 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
     start_time = time.time()
     count = 0
 
-    def load(entry):
-        seq, path = entry
-        y, sr = features.read_wav(path)
-        return seq, path, y, sr
+    def load(chunk):
+        got = features.read_audio_batch([path for _, path in chunk], verify_md5=verify_md5, threads=READ_THREADS)
+        return [(seq, path, y, sr) for (seq, path), (y, sr) in zip(chunk, got)]
 
     chunks = [entries[i:i + CHUNK_FILES] for i in range(0, len(entries), CHUNK_FILES)]
-    with cf.ThreadPoolExecutor(max_workers=READ_THREADS) as pool, open(feat_path, "w") as featfile, \
-            open(len_path, "w") as lenfile:
-        pending = [pool.submit(load, e) for e in chunks[0]] if chunks else []
+    with cf.ThreadPoolExecutor(max_workers=1) as pool, open(feat_path, "w") as featfile, open(len_path, "w") as lenfile:
+        pending = pool.submit(load, chunks[0]) if chunks else None
         for ci in range(len(chunks)):
             t0 = time.time()
-            got = [f.result() for f in pending]
+            got = pending.result()
             t["read"] += time.time() - t0
-            # the next chunk's files are read while this one is on the GPU and being written
-            pending = [pool.submit(load, e) for e in chunks[ci + 1]] if ci + 1 < len(chunks) else []
+            # the next chunk's files are read (and its FLAC files decoded) while this one is on the GPU and being written
+            pending = pool.submit(load, chunks[ci + 1]) if ci + 1 < len(chunks) else None
             for seq, path, _, sr in got:
                 if resample:
                     continue
@@ -117,6 +117,7 @@ def build_parser():
                    help="Sample rate every file must have (no resampling); default: the rate of the first file")
     p.add_argument("--resample", action="store_true",
                    help="Convert files whose rate differs from --sr (required then) to --sr on the GPU, as librosa.load does")
+    p.add_argument("--verify-md5", action="store_true", help="Check every FLAC file's decoded audio against the MD5 it carries")
     p.add_argument("--win_t", type=float, default=0.025, help="Window size in seconds")
     p.add_argument("--hop_t", type=float, default=0.010, help="Frame spacing in seconds")
     p.add_argument("--n_mels", type=int, default=80, help="Number of filter banks if choosing fbank")
@@ -134,7 +135,7 @@ def main(argv=None):
     total = 0
     for s in sets:
         total += prepare_numpy(args.dataset, s, args.dataset_dir, args.np_dir, args.ftype, args.sr, args.win_t, args.hop_t,
-                               args.n_mels, resample=args.resample)[0]
+                               args.n_mels, resample=args.resample, verify_md5=args.verify_md5)[0]
     if len(sets) > 1:
         print(f"Processed {total} files in {time.time() - t0} seconds.")
     return 0
