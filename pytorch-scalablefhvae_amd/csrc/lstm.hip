@@ -17,7 +17,6 @@
 #include "lstm_cell.h"
 #include "lstm_cluster.h"
 #include "wgrad.h"
-#include "wgrad_f32.h"
 #include <algorithm>
 #include <vector>
 #include "trace.h"
@@ -885,11 +884,11 @@ static int lstm_bwd_impl(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hipStr
 // d_xc stay f32 (f32 dgsum).
 constexpr int64_t kWgradMinK = 1024;  // shorter contractions stay on the generic engine (grouped 64x64 tiles)
 
-// `wq` (bf16 only): long contractions that meet wgrad.hip's preconditions are appended to it instead of being launched; the
-// caller launches everything it has collected (possibly from several nets) as one grouped launch (launch_wgrad).
+// `wq`: long contractions that meet wgrad.hip's preconditions are appended to it instead of being launched; the caller launches
+// everything it has collected (possibly from several nets) as one grouped launch (launch_wgrad).
 template <typename T>
-static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hipStream_t st, std::vector<WgProblem>* wq = nullptr,
-                            std::vector<GemmParams>* fq = nullptr, std::vector<WgProblem32>* wq32 = nullptr) {
+static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hipStream_t st, std::vector<WgProblemT<T>>* wq = nullptr,
+                            std::vector<GemmParams>* fq = nullptr) {
   const fhvae_lstm_desc* d = &bd->f;
   const int64_t B = d->B, T_ = d->T, I = d->I, Ic = d->Ic, H = d->H;
   const int L = d->L;
@@ -902,19 +901,9 @@ static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hip
   int ng = 0;
   // -> true: taken by the dedicated long-K kernel (queued in wq)
   auto wgrad_long = [&](const void* a, int64_t lda, const void* b, int64_t ldb, int64_t Kc, float* c, int64_t ldc, int64_t Ncols) {
-    if (sizeof(T) == 4) {  // f32 mode: the exact-f32 form of the long-K kernel (wgrad_f32.hip)
-      if (!wq32 || Kc < kWgradMinK) return false;
-      WgProblem32 w = {};
-      w.A = (const float*)a, w.B = (const float*)b, w.C = c;
-      w.lda = lda, w.ldb = ldb, w.ldc = ldc;
-      w.M = (int)G, w.N = (int)Ncols, w.K = (int)Kc;
-      if (!wgrad32_eligible(w)) return false;
-      wq32->push_back(w);
-      return true;
-    }
-    if (!wq || sizeof(T) != 2 || Kc < kWgradMinK) return false;
-    WgProblem w = {};
-    w.A = (const u16*)a, w.B = (const u16*)b, w.C = c;
+    if (!wq || Kc < kWgradMinK) return false;
+    WgProblemT<T> w = {};
+    w.A = (const T*)a, w.B = (const T*)b, w.C = c;
     w.lda = lda, w.ldb = ldb, w.ldc = ldc;
     w.M = (int)G, w.N = (int)Ncols, w.K = (int)Kc;
     if (!wgrad_eligible(w)) return false;
@@ -1002,6 +991,23 @@ static int lstm_dxc(const fhvae_lstm_bwd_desc* bd, hipStream_t st, bool zeroed =
   return launch_gemm(p, FHVAE_F32, st);
 }
 
+// the recurrence (+ d_xc) and / or the parameter gradients of one net, its long contractions as one grouped launch
+template <typename T>
+static int lstm_seq_bwd_t(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, bool rec, bool par, bool dxc_zeroed, hipStream_t st) {
+  int e;
+  if (rec) {
+    e = lstm_bwd_impl<T>(bd, op, st);
+    if (e) return e;
+    e = lstm_dxc(bd, st, dxc_zeroed);
+    if (e) return e;
+  }
+  if (!par) return FHVAE_OK;
+  std::vector<WgProblemT<T>> wq;
+  e = lstm_param_grads<T>(bd, op, st, getenv("FHVAE_NO_WGRAD") ? nullptr : &wq);
+  if (e) return e;
+  return launch_wgrad(wq.data(), (int)wq.size(), st);
+}
+
 extern "C" int fhvae_lstm_seq_bwd(const fhvae_lstm_bwd_desc* bd, void* stream) {
   FH_CHECK_PTR(bd);
   const fhvae_lstm_desc* d = &bd->f;
@@ -1014,32 +1020,9 @@ extern "C" int fhvae_lstm_seq_bwd(const fhvae_lstm_bwd_desc* bd, void* stream) {
   const bool rec = bd->phase != 2, par = bd->phase != 1;
   if (rec && !bd->d_hs_top && !bd->d_hn) return FHVAE_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == FHVAE_F32) {
-    Ops<float> op = ops_f32(d);
-    if (rec) {
-      e = lstm_bwd_impl<float>(bd, op, st);
-      if (e) return e;
-      e = lstm_dxc(bd, st);
-      if (e) return e;
-    }
-    if (!par) return FHVAE_OK;
-    std::vector<WgProblem32> wq32;
-    e = lstm_param_grads<float>(bd, op, st, nullptr, nullptr, getenv("FHVAE_NO_WGRAD") ? nullptr : &wq32);
-    if (e) return e;
-    return launch_wgrad32(wq32.data(), (int)wq32.size(), st);
-  }
-  Ops<u16> op = ops_bf16(d);  // filled by the forward
-  if (rec) {
-    e = lstm_bwd_impl<u16>(bd, op, st);
-    if (e) return e;
-    e = lstm_dxc(bd, st, cluster_eligible(d) && cluster_bwd_zeroes_dxc(d));
-    if (e) return e;
-  }
-  if (!par) return FHVAE_OK;
-  std::vector<WgProblem> wq;
-  e = lstm_param_grads<u16>(bd, op, st, getenv("FHVAE_NO_WGRAD") ? nullptr : &wq);
-  if (e) return e;
-  return launch_wgrad(wq.data(), (int)wq.size(), st);
+  if (d->dtype == FHVAE_F32) return lstm_seq_bwd_t<float>(bd, ops_f32(d), rec, par, false, st);
+  // (the operands were filled by the forward)
+  return lstm_seq_bwd_t<u16>(bd, ops_bf16(d), rec, par, rec && cluster_eligible(d) && cluster_bwd_zeroes_dxc(d), st);
 }
 
 // Phase 2 (parameter gradients) of n backward passes whose recurrences (phase 1) have run: the long weight-gradient
@@ -1075,7 +1058,7 @@ extern "C" int fhvae_lstm_param_grads_multi(const fhvae_lstm_bwd_desc* const* bd
     wq.push_back(p);
   }
   std::vector<GemmParams> fq;  // the f32 (B-row) contractions of the time-constant inputs
-  std::vector<WgProblem32> wq32;  // f32 mode: the long contractions of every queued net, one grouped launch (wgrad_f32.hip)
+  std::vector<WgProblem32> wq32;  // f32 mode: the long contractions of every queued net, one grouped launch
   const bool use_wq = !getenv("FHVAE_NO_WGRAD");
   for (int i = 0; i < n; ++i) {
     const fhvae_lstm_bwd_desc* bd = bds[i];
@@ -1086,7 +1069,7 @@ extern "C" int fhvae_lstm_param_grads_multi(const fhvae_lstm_bwd_desc* const* bd
     FH_CHECK_PTR(bd->dgates);
     if (d->Ic > 0) FH_CHECK_PTR(bd->dgsum);
     if (d->dtype == FHVAE_F32) {
-      e = lstm_param_grads<float>(bd, ops_f32(d), st, nullptr, nullptr, use_wq ? &wq32 : nullptr);
+      e = lstm_param_grads<float>(bd, ops_f32(d), st, use_wq ? &wq32 : nullptr);
     } else {
       e = lstm_param_grads<u16>(bd, ops_bf16(d), st, use_wq ? &wq : nullptr, &fq);
     }
@@ -1107,7 +1090,7 @@ extern "C" int fhvae_lstm_param_grads_multi(const fhvae_lstm_bwd_desc* const* bd
     i = j;
   }
   {
-    const int e = launch_wgrad32(wq32.data(), (int)wq32.size(), st);
+    const int e = launch_wgrad(wq32.data(), (int)wq32.size(), st);
     if (e) return e;
   }
   return launch_wgrad(wq.data(), (int)wq.size(), st);

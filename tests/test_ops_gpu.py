@@ -216,7 +216,7 @@ def test_wgrad_bf16_vs_cpu_matmul(hb, K, M, N):
 @pytest.mark.parametrize("K,M,N", [(20480, 1024, 256), (1280, 512, 80), (5000, 192, 112), (777, 1024, 256), (4096, 2048, 512),
                                    (32, 256, 256), (4096 + 4, 320, 136)])
 def test_wgrad_f32_vs_cpu_matmul(hb, K, M, N):
-    """fhvae_wgrad_f32: the exact-f32 form of the long-K weight-gradient kernel (csrc/wgrad_f32.hip: 256x256 / 256x128 tiles, LDS-DMA
+    """fhvae_wgrad_f32: the exact-f32 form of the long-K weight-gradient kernel (csrc/wgrad.hip's f32 instantiation: 256x256 / 256x128 tiles, LDS-DMA
     double buffer, one ds_read_b32 per operand scalar, split-K atomics), K tails / ragged M, N / odd slice counts included, against the
     f64 CPU matmul of the same f32 operands.  Exact-f32 products; what remains is the f32 accumulation (a random walk of K
     roundings at the partial sum's magnitude): 1e-5 of the output's scale sqrt(K), the bound of the bf16 kernel's test."""
@@ -260,9 +260,12 @@ def test_proj_bf16_rejects_unaligned(hb):
         hb.proj_bf16(a, b)  # K = 72 is not a multiple of 64
 
 
-def test_deferred_param_grads_match_immediate(hb):
+@pytest.mark.parametrize("compute_dtype", ["bf16", "f32"])
+def test_deferred_param_grads_match_immediate(hb, compute_dtype):
     """With gradient sinks (FusedAdam) the nets' parameter gradients are queued and flushed as one grouped call by the
-    optimizer: same gradients as the immediate path (FHVAE_NO_DEFER semantics via set_defer_param_grads(False))."""
+    optimizer: same gradients as the immediate path (FHVAE_NO_DEFER semantics via set_defer_param_grads(False)).  Both operand
+    types: the grouped launch holds several nets' problems in one group with its own K split (K = 2,432 / 2,560 rows, above the
+    long-K kernel's threshold); the f32 paths differ only in accumulation order."""
     from fhvae import FHVAE
     from hip_optim import FusedAdam
     from train_model import loss_function
@@ -276,7 +279,7 @@ def test_deferred_param_grads_match_immediate(hb):
         hb.set_defer_param_grads(defer)
         try:
             torch.manual_seed(4)
-            m = FHVAE(T * F, [H, H], [H, H], D, D, [H, H], seg_len=T, num_seqs=S, reference_compat=False, compute_dtype="bf16").cuda()
+            m = FHVAE(T * F, [H, H], [H, H], D, D, [H, H], seg_len=T, num_seqs=S, reference_compat=False, compute_dtype=compute_dtype).cuda()
             opt = FusedAdam(m.parameters(), lr=1e-3, betas=(0.95, 0.999))
             opt.zero_grad()
             out = m(x, idx, S, ns, eps=eps)

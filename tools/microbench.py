@@ -26,13 +26,16 @@ def gemm(M, K, N, dtype):
     us = timeit(f)
     print("gemm %s M=%d K=%d N=%d: %.1f us  %.1f TFLOP/s" % ("bf16" if dtype else "f32", M, K, N, us, 2.0 * M * K * N / us / 1e6))
 
-def wgrad(K, M, N, n=1):
-    """C[M,N] += A[K,M]^T . B[K,N], bf16 K-major operands (csrc/wgrad.hip): the weight-gradient contraction; n problems at once
-    through fhvae_wgrad_bf16 one by one (the model's grouped launch is timed by bench.py's op timers)."""
-    a = torch.randn(K, M, device="cuda").bfloat16(); b = torch.randn(K, N, device="cuda").bfloat16()
+def wgrad(K, M, N, dtype=hb.BF16):
+    """C[M,N] += A[K,M]^T . B[K,N], K-major bf16 or f32 operands (csrc/wgrad.hip): the weight-gradient contraction, one problem
+    through fhvae_wgrad_bf16 / fhvae_wgrad_f32 (the model's grouped launch is timed by bench.py's op timers)."""
+    a = torch.randn(K, M, device="cuda"); b = torch.randn(K, N, device="cuda")
+    if dtype == hb.BF16:
+        a, b = a.bfloat16(), b.bfloat16()
     c = torch.zeros(M, N, device="cuda")
-    us = timeit(lambda: hb.wgrad_bf16_(c, a, b))
-    print("wgrad bf16 K=%d M=%d N=%d: %.1f us  %.1f TFLOP/s" % (K, M, N, us, 2.0 * M * K * N / us / 1e6))
+    op = hb.wgrad_bf16_ if dtype == hb.BF16 else hb.wgrad_f32_
+    us = timeit(lambda: op(c, a, b))
+    print("wgrad %s K=%d M=%d N=%d: %.1f us  %.1f TFLOP/s" % ("bf16" if dtype else "f32", K, M, N, us, 2.0 * M * K * N / us / 1e6))
 
 
 def lstm(B, T, I, Ic, H, L, dtype, bwd=True):
@@ -76,6 +79,8 @@ if __name__ == "__main__":
     wgrad(40960, 1024, 80)
     wgrad(5120, 1024, 256)
     wgrad(40960, 2048, 512)
+    wgrad(81920, 1024, 256, hb.F32)
+    wgrad(81920, 1024, 80, hb.F32)
     if "--gemm-only" in sys.argv:
         sys.exit(0)
     for dt in (hb.F32, hb.BF16):
