@@ -736,6 +736,27 @@ int fhvae_flac_decode(const uint8_t* buf, int64_t n_bytes, const FhvaeFlacDesc* 
                       int64_t n_cand, int32_t* cand_status, int64_t* cand_end, int64_t* cand_spos, int32_t* out, int64_t n_out,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Speaker verification (csrc/sv.hip): the histogram of the cosine scores of all pairs of S embeddings, target and non-target
+ * trials apart, with no (S, S) temporary (an addition of ABI 11).
+ *   emb (S, D) f32 with leading dimension ld >= D; label (S) int32, -1 = no label: such a row takes part in no trial.
+ *   A trial is an unordered pair i < j with both labels >= 0; it is a target iff label[i] == label[j].
+ *   score = dot(e_i, e_j) / (n_i * n_j), n = max(sqrt(sum e^2), 1e-30): the dot on exact-f32 MFMA, the sum of squares an f32
+ *     fma chain, sqrt and the division correctly rounded; the product n_i * n_j is floored at FLT_MIN (it underflows only
+ *     where both rows are below 1e-19, and the dot is 0 there), so a zero row scores 0 against everything.
+ *   bin = clamp((int)floorf((score + 1) * (n_bins / 2)), 0, n_bins - 1), in f32.
+ *   hist (2, n_bins) uint64 on the device, overwritten: row 0 counts the target trials, row 1 the non-target trials.
+ *   The result depends on (emb, label, n_bins) alone: not on the grid, not on S relative to the tiles; score(i, j) equals
+ *   score(j, i) bit for bit, so it does not depend on the order of the rows either.  Two calls give equal bits.
+ *   ws: fhvae_sv_hist_ws_bytes(S) bytes of device scratch (the rows' norms), 4-byte aligned.
+ *   D a multiple of 16 in [16, 128], n_bins a power of two in [64, 8192], S >= 1 (S = 1: all zeros), ld >= D, ws_bytes
+ *   large enough, otherwise FHVAE_ERR_SHAPE; ld a multiple of 4 and emb 16-byte aligned, otherwise FHVAE_ERR_ALIGN;
+ *   S <= 2^24, otherwise FHVAE_ERR_LIMIT; all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fhvae_sv_hist_ws_bytes(int64_t S);
+int fhvae_sv_hist(const float* emb, int64_t ld, const int32_t* label, int64_t S, int64_t D, int64_t n_bins, void* ws,
+                  int64_t ws_bytes, uint64_t* hist, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -17,6 +17,13 @@ mu2), the decoder means are un-normalised, put back together (utils.overlap_mean
 (as many columns as the checkpoint's feature width) and the three go through features.synthesize_mel instead: linear
 magnitudes fitted to the mel magnitudes (non-negative least squares, --nnls-iters steps), then the same Griffin-Lim.
 
+With --utt2spk FILE (Kaldi's `<seq> <spk>` lines) or --spk-key-sep SEP (the speaker is the sequence key up to the first SEP: "-"
+for preprocess_librispeech.py's ids, "_" for preprocess_timit.py's; both need --feat-scp data) the factorization is measured by
+speaker verification (verification.py): every sequence against every other by the cosine of their mu2 (the rows of mu2.npy) and,
+as the control, of their z1_mean (the mean of the sequence's segments' z1_mu); summary.json gains "speaker_verification" with the
+equal error rate of both, and sv_hist_mu2.npy / sv_hist_z1_mean.npy hold the (2, --sv-bins) target / non-target score histograms
+(a DET curve can be drawn from them).  A factorized model gives a low EER on mu2 and a high one on z1_mean.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -61,7 +68,48 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--wav-ftype", default="spec", choices=["spec", "fbank"],
                    help="feature type of the --feat-scp data for --wav-out; fbank: mel inversion in front of Griffin-Lim")
     p.add_argument("--nnls-iters", type=int, default=200, help="steps of the mel inversion (--wav-ftype fbank)")
+    spk = p.add_mutually_exclusive_group()
+    spk.add_argument("--utt2spk", default=None, help="speaker verification: Kaldi utt2spk file naming each sequence's speaker (needs --feat-scp)")
+    spk.add_argument("--spk-key-sep", default=None,
+                     help="speaker verification: the speaker is the sequence key up to the first SEP (needs --feat-scp)")
+    p.add_argument("--sv-bins", type=int, default=4096, help="score bins of the verification histograms (a power of two, 64..8192)")
     return p
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    p = build_parser()
+    args = p.parse_args(argv)
+    if (args.utt2spk is not None or args.spk_key_sep is not None) and args.feat_scp is None:
+        p.error("--utt2spk / --spk-key-sep name the speakers of --feat-scp data: give --feat-scp")
+    if args.sv_bins < 64 or args.sv_bins > 8192 or args.sv_bins & (args.sv_bins - 1):
+        p.error("--sv-bins %d must be a power of two in [64, 8192]" % args.sv_bins)
+    return args
+
+
+def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
+    """--utt2spk / --spk-key-sep: the "speaker_verification" block of summary.json (see the module docstring).  keys: the key of
+    every row of mu2_rows; z1_mu (segments, D) with seq_pos the row each segment belongs to."""
+    import verification as V
+
+    if args.utt2spk is not None:
+        table = V.read_utt2spk(args.utt2spk)
+        speakers = [table.get(k) for k in keys]
+    else:
+        speakers = V.speakers_from_keys(keys, args.spk_key_sep)
+    labels, n_spk = V.labels_from_speakers(speakers)
+    n = len(keys)
+    z1 = torch.from_numpy(z1_mu).to(dev)
+    pos = torch.from_numpy(seq_pos).to(dev)
+    z1_sum = torch.zeros(n, z1.shape[1], device=dev).index_add_(0, pos, z1)
+    count = torch.zeros(n, device=dev).index_add_(0, pos, torch.ones(pos.shape[0], device=dev))
+    z1_mean = z1_sum / count.clamp(min=1.0).unsqueeze(1)
+    block = {}
+    for name, emb in (("mu2", torch.from_numpy(mu2_rows).to(dev)), ("z1_mean", z1_mean)):
+        r = V.speaker_verification(emb, labels, n_bins=args.sv_bins, device=dev)
+        np.save(os.path.join(out_dir, "sv_hist_%s.npy" % name), r.pop("hist"))
+        block[name] = r
+    block.update({"speakers": n_spk, "unlabelled": int((labels < 0).sum()), "bins": args.sv_bins})
+    return block
 
 
 def feature_width(model, seg_len):
@@ -112,7 +160,7 @@ def write_wavs(args, model, ds, mu2, dev):
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.wav_out is not None:
         import features
 
@@ -207,7 +255,8 @@ def main(argv=None) -> int:
         out("z1_mu.npy", np.concatenate(z1s)), out("z2_mu.npy", np.concatenate(z2s)), out("seq_ids.npy", np.concatenate(ids))
         seqs = sorted(mu2)
         out("mu2_seqs.npy", np.asarray(seqs, dtype=np.int64))
-        out("mu2.npy", np.stack([mu2[y].cpu().numpy() for y in seqs]) if seqs else np.zeros((0, model.z2_dim), np.float32))
+        mu2_rows = np.stack([mu2[y].cpu().numpy() for y in seqs]) if seqs else np.zeros((0, model.z2_dim), np.float32)
+        out("mu2.npy", mu2_rows)
         if recon_x and args.max_recon > 0:
             xr = torch.cat(recon_x)
             x_mu, x_lv = model.reconstruct(xr)
@@ -219,6 +268,14 @@ def main(argv=None) -> int:
                     return 1
                 c_mu, c_lv = model.convert(xr, mu2[args.convert_to])
                 out("convert_mu.npy", undo(c_mu.cpu().numpy())), out("convert_logvar.npy", c_lv.cpu().numpy())
+    sv = None
+    if args.utt2spk is not None or args.spk_key_sep is not None:
+        seq_pos = np.searchsorted(np.asarray(seqs, dtype=np.int64), np.concatenate(ids).astype(np.int64))  # (mu2 covers every segment's sequence)
+        try:
+            sv = verify_speakers(args, [ds.seq_keys[y] for y in seqs], mu2_rows, np.concatenate(z1s), seq_pos, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("speaker verification: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -232,6 +289,8 @@ def main(argv=None) -> int:
                "sequences": len(mu2), "lower_bound_per_frame": sum(lbs) / max(frames, 1)}
     if wavs is not None:
         summary["wavs"] = wavs
+    if sv is not None:
+        summary["speaker_verification"] = sv
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

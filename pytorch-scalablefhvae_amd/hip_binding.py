@@ -153,6 +153,8 @@ SIGNATURES = {
                                      _i64, _i64, _vp, _i64, _vp, _vp]),
     "fhvae_mel_invert_tile_rows": (C.c_int, [_i64, _i64]),
     "fhvae_mel_invert": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "fhvae_sv_hist_ws_bytes": (_i64, [_i64]),
+    "fhvae_sv_hist": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1707,6 +1709,37 @@ def mel_invert(mel, bin_filt, bin_w, filt_first, filt_off, filt_w, inv_l, beta, 
         _check(lib.fhvae_mel_invert(_p(mel), mel.shape[0], n_mels, n_bins, _p(bin_filt), _p(bin_w), _p(filt_first), _p(filt_off),
                                     _p(filt_w), filt_w.numel(), float(inv_l), _p(beta), beta.shape[0], flags, _p(out), _p(status),
                                     _stream()), "fhvae_mel_invert")
+
+
+def sv_hist(emb, label, n_bins=4096):
+    """All-pairs cosine scoring in one pass (fhvae_sv_hist): emb (S, D) f32, label (S,) int32 (-1: the row takes part in no
+    trial) -> (2, n_bins) int64 counts, row 0 the target trials (i < j, equal labels) and row 1 the non-target trials, a trial
+    in bin clamp(floor((cos + 1) n_bins / 2), 0, n_bins - 1).  D is padded to the next multiple of 16 with zero columns (no
+    cosine changes); rows with a leading dimension the kernel takes are read in place."""
+    _need_gpu(emb, label)
+    if emb.dtype != torch.float32 or emb.dim() != 2:
+        raise RuntimeError("sv_hist takes (S, D) float32 embeddings")
+    if label.dtype != torch.int32 or label.dim() != 1 or label.shape[0] != emb.shape[0]:
+        raise RuntimeError("sv_hist takes one int32 label per row of emb")
+    S, D = emb.shape
+    if S < 1 or D < 1 or D > 128:
+        raise RuntimeError("sv_hist: S = %d rows of D = %d columns (S >= 1, 1 <= D <= 128)" % (S, D))
+    n_bins = int(n_bins)
+    if n_bins < 64 or n_bins > 8192 or n_bins & (n_bins - 1):
+        raise RuntimeError("sv_hist: n_bins = %d must be a power of two in [64, 8192]" % n_bins)
+    emb, label = emb.detach(), label.contiguous()
+    Dp = (D + 15) // 16 * 16
+    if Dp != D or emb.stride(1) != 1 or emb.stride(0) < D or emb.stride(0) % 4 or emb.data_ptr() % 16:
+        pad = torch.zeros(S, Dp, device=emb.device, dtype=torch.float32)
+        pad[:, :D] = emb
+        emb = pad
+    lib = load_library()
+    nws = int(lib.fhvae_sv_hist_ws_bytes(S))
+    ws = torch.empty(nws, device=emb.device, dtype=torch.uint8)
+    hist = torch.empty(2, n_bins, device=emb.device, dtype=torch.int64)  # (uint64 counts; they stay far below 2^63)
+    with _Timed("fhvae_sv_hist"):
+        _check(lib.fhvae_sv_hist(_p(emb), emb.stride(0), _p(label), S, Dp, n_bins, _p(ws), nws, _p(hist), _stream()), "fhvae_sv_hist")
+    return hist
 
 
 def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):
