@@ -1310,12 +1310,22 @@ def backward(loss: torch.Tensor):
 def adam_step_(p, g, m, v, step_dev, lr, beta1, beta2, eps, grad_scale=1.0, p_lp=None, flags=0):
     """In-place fused Adam on flat f32 views (train_model.py:409-411).  step_dev: the int32 step count on the device, already
     incremented -- or, with ADAM_ADVANCE, int32[ADAM_STEP_WORDS] ([0] the count, the rest the kernel's scratch words): the launch
-    counts the step itself.  ADAM_ZERO_GRAD clears g behind its use."""
+    counts the step itself.  ADAM_ZERO_GRAD clears g behind its use.  p_lp: an optional bf16 shadow of p, written behind the update.
+    The kernel indexes p, g, m, v (and p_lp) to p.numel(): operands of another length, dtype or layout are refused here."""
     lib = load_library()
-    _need_gpu(p, g, m, v, step_dev)
+    _need_gpu(p, g, m, v, step_dev, p_lp)
     if (flags & ADAM_ADVANCE) and step_dev.numel() < ADAM_STEP_WORDS:
         raise RuntimeError("ADAM_ADVANCE needs an int32[%d] step buffer (step count + scratch words)" % ADAM_STEP_WORDS)
     n = p.numel()
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise RuntimeError("adam_step_: %s must be a contiguous float32 tensor of p's %d elements (got %s, %d elements, %s)"
+                               % (name, n, t.dtype, t.numel(), "contiguous" if t.is_contiguous() else "not contiguous"))
+    if p_lp is not None and (p_lp.dtype != torch.bfloat16 or not p_lp.is_contiguous() or p_lp.numel() != n):
+        raise RuntimeError("adam_step_: p_lp must be a contiguous bfloat16 tensor of p's %d elements (got %s, %d elements)"
+                           % (n, p_lp.dtype, p_lp.numel()))
+    if step_dev.dtype != torch.int32:
+        raise RuntimeError("adam_step_: the step count is int32 on the device (got %s)" % step_dev.dtype)
     if n == 0:  # an empty table shard (more ranks than rows)
         return
     with _Timed("fhvae_adam_step"):

@@ -75,6 +75,13 @@ def test_argument_errors_are_reported_before_any_launch(lib):
     assert lib.fhvae_gauss_reparam_bwd_pair(None, None, p, 4, p, p, 8, p, 16, None, None, 4, 8, None) == -2      # ABI 11: ld_s = 4 < D = 8
     assert lib.fhvae_adam_step(p, p, p, p, None, 16, 1e-3, 0.9, 0.999, 1e-8, 1.0, 4, p, None) == -2              # ABI 11: unknown flag bit
     assert lib.fhvae_adam_step(p, p, p, p, None, 16, 1e-3, 0.9, 0.999, 1e-8, 1.0, 3, None, None) == -1           # no step buffer
+    for k in range(4):  # each of p, g, m, v missing; n <= 0; every flag bit above the two defined
+        ptrs = [None if j == k else p for j in range(4)]
+        assert lib.fhvae_adam_step(*ptrs, None, 16, 1e-3, 0.9, 0.999, 1e-8, 1.0, 0, p, None) == -1
+    assert lib.fhvae_adam_step(p, p, p, p, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, 0, p, None) == -2
+    assert lib.fhvae_adam_step(p, p, p, p, None, -5, 1e-3, 0.9, 0.999, 1e-8, 1.0, 3, p, None) == -2
+    assert lib.fhvae_adam_step(p, p, p, p, p, 16, 1e-3, 0.9, 0.999, 1e-8, 1.0, 8 | 3, p, None) == -2
+    assert lib.fhvae_adam_step(p, p, p, p, None, 16, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1 << 30, p, None) == -2
     w = hb.WgradDesc(None, 8, 0, None, 8, None, 8, 8, 8, 64)
     assert lib.fhvae_wgrad_desc_ok(ctypes.byref(w)) == 0
     assert lib.fhvae_disc_lse_bwd_ws_bytes(2048, 28000, 32) > 0 and lib.fhvae_disc_lse_bwd_ws_bytes(8, 8, 32) == 0
