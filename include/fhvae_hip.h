@@ -757,6 +757,41 @@ int64_t fhvae_sv_hist_ws_bytes(int64_t S);
 int fhvae_sv_hist(const float* emb, int64_t ld, const int32_t* label, int64_t S, int64_t D, int64_t n_bins, void* ws,
                   int64_t ws_bytes, uint64_t* hist, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact t-SNE of N embeddings (csrc/tsne.hip) with no (N, N) array: every pass recomputes the squared distances, and the
+ * gradient recomputes p_ij, from three numbers per row (an addition of ABI 11).
+ *   x (N, D) f32 with leading dimension ld >= D (the caller subtracts the column means).
+ *   d2(i, j) = max(n_i + n_j - 2 x_i . x_j, 0): the dot on exact-f32 MFMA, n an f32 fma chain; d2(i, j) == d2(j, i) bit for bit.
+ *   j = i takes part in nothing.  m_i = min_j d2(i, j); e_ij = exp(-beta_i (d2(i, j) - m_i)); Z_i = sum_j e_ij;
+ *   p_j|i = e_ij / Z_i; p_ij = (p_j|i + p_i|j) / (2 N).
+ * fhvae_tsne_affinity: beta_i by bisection on log2 beta over [-60, 60], 48 steps and no exit that depends on the data: a step
+ *   moves the lower end up where log Z_i + beta_i sum_j e_ij (d2 - m_i) / Z_i > log(perplexity); beta_i = 2^(the middle of the
+ *   last interval).  Writes beta, m, Z (each (N) f32 on the device).  One launch, 50 streaming passes inside it.
+ * fhvae_tsne_step: one iteration at y (N, 2), nothing read back:
+ *   w_ij = 1 / (1 + |y_i - y_j|^2); F_i = exaggeration sum_j p_ij w_ij (y_i - y_j); R_i = sum_j w_ij^2 (y_i - y_j);
+ *   W_i = sum_j w_ij; Zq = sum_i W_i; grad_i = 4 (F_i - R_i / Zq);
+ *   inc = v grad < 0; g = inc ? g + 0.2 : 0.8 g; g = max(g, 0.01); v = momentum v - lr g grad; y += v   (y, v, g (N, 2) f32).
+ *   kl (device, 1 f32, may be NULL): KL = sum_{i != j} p_ij log(p_ij Zq / w_ij) at the y the call was given, without the
+ *   exaggeration (a term with p_ij < 1e-30 counts as 0).
+ * fhvae_tsne_grad: the same pass without the update: out (N, 7) f32 = F (2, with the exaggeration), R (2), W, grad (2) per
+ *   row, scal (2) f32 = Zq, KL.
+ *   The j range is split into chunks; per-row partials per chunk go to the workspace and are added in index order, Zq in a
+ *   fixed order in double: no floating-point atomic, two calls give equal bits.
+ *   ws: fhvae_tsne_ws_bytes(N, D) bytes of device scratch, 16-byte aligned (0 for an N the entries refuse): the norms, 7 N
+ *   floats per chunk, 4 per workgroup; chunks <= max(1, 2048 / ceil(N / 256)) and <= ceil(N / 512): N * chunks <= max(N, 2^19).
+ *   8 <= N, D a multiple of 16 in [16, 128], ld >= D, 1 <= perplexity <= (N - 1) / 3, ws_bytes large enough, otherwise
+ *   FHVAE_ERR_SHAPE; ld a multiple of 4, x and ws 16-byte, y 8-byte and the rest 4-byte aligned, otherwise FHVAE_ERR_ALIGN;
+ *   N <= 2^22, otherwise FHVAE_ERR_LIMIT; all before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fhvae_tsne_ws_bytes(int64_t N, int64_t D);
+int fhvae_tsne_affinity(const float* x, int64_t ld, int64_t N, int64_t D, float perplexity, float* beta, float* m, float* z,
+                        void* ws, int64_t ws_bytes, void* stream);
+int fhvae_tsne_step(const float* x, int64_t ld, int64_t N, int64_t D, const float* beta, const float* m, const float* z, float* y,
+                    float* v, float* g, float exaggeration, float momentum, float lr, float* kl, void* ws, int64_t ws_bytes,
+                    void* stream);
+int fhvae_tsne_grad(const float* x, int64_t ld, int64_t N, int64_t D, const float* beta, const float* m, const float* z,
+                    const float* y, float exaggeration, float* out, float* scal, void* ws, int64_t ws_bytes, void* stream);
+
 /* small utilities used by the host side */
 /* (B,T,F) batch-major f32 -> (T,B,F) time-major in operand dtype `dtype` (and optionally f32) */
 int fhvae_to_time_major(const float* x_btf, void* x_tbf, float* x_tbf_f32, int64_t B, int64_t T,

@@ -1,5 +1,5 @@
-"""eval_model.py -- what the reference's eval_model.py leaves as TODOs (eval_model.py:57-59: load data, evaluate, visualise),
-without the plotting: load a checkpoint, then write as .npy files under --out
+"""eval_model.py -- what the reference's eval_model.py leaves as TODOs (eval_model.py:57-59: load data, evaluate, visualise):
+load a checkpoint, then write as .npy files under --out
 
   z1_mu.npy, z2_mu.npy        per-segment posterior means (model.encode)
   seq_ids.npy                 the sequence index of every segment
@@ -23,6 +23,13 @@ speaker verification (verification.py): every sequence against every other by th
 as the control, of their z1_mean (the mean of the sequence's segments' z1_mu); summary.json gains "speaker_verification" with the
 equal error rate of both, and sv_hist_mu2.npy / sv_hist_z1_mean.npy hold the (2, --sv-bins) target / non-target score histograms
 (a DET curve can be drawn from them).  A factorized model gives a low EER on mu2 and a high one on z1_mean.
+
+With --tsne (needs --feat-scp data; --tsne-perplexity, --tsne-iters, --tsne-seed) the same two embeddings are also drawn: exact
+t-SNE maps (tsne.py) go to tsne_mu2.npy and tsne_z1_mean.npy, both (sequences, 2), and to tsne.tsv, one line per sequence: the
+key, the speaker (or "-"), the mu2 and the z1_mean coordinates; summary.json gains "tsne" with the perplexity, the iterations,
+the seed and the final KL divergence of both maps.  With the speakers known (--utt2spk / --spk-key-sep) and matplotlib
+importable, tsne_mu2.png and tsne_z1_mean.png are scatter plots with one colour per speaker: one island per speaker on mu2 and
+none on z1_mean is what a factorized model shows.
 
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
@@ -73,6 +80,10 @@ def build_parser() -> argparse.ArgumentParser:
     spk.add_argument("--spk-key-sep", default=None,
                      help="speaker verification: the speaker is the sequence key up to the first SEP (needs --feat-scp)")
     p.add_argument("--sv-bins", type=int, default=4096, help="score bins of the verification histograms (a power of two, 64..8192)")
+    p.add_argument("--tsne", action="store_true", help="write exact t-SNE maps of mu2 and of the sequences' mean z1 (needs --feat-scp)")
+    p.add_argument("--tsne-perplexity", type=float, default=30.0, help="at most (sequences - 1) / 3")
+    p.add_argument("--tsne-iters", type=int, default=1000)
+    p.add_argument("--tsne-seed", type=int, default=0, help="seed of the initial map")
     return p
 
 
@@ -83,7 +94,34 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--utt2spk / --spk-key-sep name the speakers of --feat-scp data: give --feat-scp")
     if args.sv_bins < 64 or args.sv_bins > 8192 or args.sv_bins & (args.sv_bins - 1):
         p.error("--sv-bins %d must be a power of two in [64, 8192]" % args.sv_bins)
+    if args.tsne and args.feat_scp is None:
+        p.error("--tsne draws the sequences of --feat-scp data: give --feat-scp")
+    if not args.tsne_perplexity >= 1.0:
+        p.error("--tsne-perplexity %g must be at least 1" % args.tsne_perplexity)
+    if args.tsne_iters < 1:
+        p.error("--tsne-iters %d must be at least 1" % args.tsne_iters)
+    if args.tsne_seed < 0 or args.tsne_seed >= 2 ** 32:
+        p.error("--tsne-seed %d must lie in [0, 2^32)" % args.tsne_seed)
     return args
+
+
+def speakers_of(args, keys):
+    """--utt2spk / --spk-key-sep: the speaker of every key (None = unknown)."""
+    import verification as V
+
+    if args.utt2spk is not None:
+        table = V.read_utt2spk(args.utt2spk)
+        return [table.get(k) for k in keys]
+    return V.speakers_from_keys(keys, args.spk_key_sep)
+
+
+def sequence_means(z1_mu, seq_pos, n, dev):
+    """z1_mu (segments, D) with seq_pos the row each segment belongs to -> (n, D) means on dev."""
+    z1 = torch.from_numpy(z1_mu).to(dev)
+    pos = torch.from_numpy(seq_pos).to(dev)
+    z1_sum = torch.zeros(n, z1.shape[1], device=dev).index_add_(0, pos, z1)
+    count = torch.zeros(n, device=dev).index_add_(0, pos, torch.ones(pos.shape[0], device=dev))
+    return z1_sum / count.clamp(min=1.0).unsqueeze(1)
 
 
 def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
@@ -91,24 +129,39 @@ def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
     every row of mu2_rows; z1_mu (segments, D) with seq_pos the row each segment belongs to."""
     import verification as V
 
-    if args.utt2spk is not None:
-        table = V.read_utt2spk(args.utt2spk)
-        speakers = [table.get(k) for k in keys]
-    else:
-        speakers = V.speakers_from_keys(keys, args.spk_key_sep)
-    labels, n_spk = V.labels_from_speakers(speakers)
-    n = len(keys)
-    z1 = torch.from_numpy(z1_mu).to(dev)
-    pos = torch.from_numpy(seq_pos).to(dev)
-    z1_sum = torch.zeros(n, z1.shape[1], device=dev).index_add_(0, pos, z1)
-    count = torch.zeros(n, device=dev).index_add_(0, pos, torch.ones(pos.shape[0], device=dev))
-    z1_mean = z1_sum / count.clamp(min=1.0).unsqueeze(1)
+    labels, n_spk = V.labels_from_speakers(speakers_of(args, keys))
+    z1_mean = sequence_means(z1_mu, seq_pos, len(keys), dev)
     block = {}
     for name, emb in (("mu2", torch.from_numpy(mu2_rows).to(dev)), ("z1_mean", z1_mean)):
         r = V.speaker_verification(emb, labels, n_bins=args.sv_bins, device=dev)
         np.save(os.path.join(out_dir, "sv_hist_%s.npy" % name), r.pop("hist"))
         block[name] = r
     block.update({"speakers": n_spk, "unlabelled": int((labels < 0).sum()), "bins": args.sv_bins})
+    return block
+
+
+def draw_tsne(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
+    """--tsne: the maps, tsne.tsv, the pictures and the "tsne" block of summary.json (see the module docstring)."""
+    import tsne as T
+    import verification as V
+
+    known = args.utt2spk is not None or args.spk_key_sep is not None
+    speakers = speakers_of(args, keys) if known else [None] * len(keys)
+    labels, _ = V.labels_from_speakers(speakers)
+    block = {"perplexity": args.tsne_perplexity, "iterations": args.tsne_iters, "seed": args.tsne_seed}
+    maps = {}
+    for name, emb in (("mu2", torch.from_numpy(mu2_rows).to(dev)), ("z1_mean", sequence_means(z1_mu, seq_pos, len(keys), dev))):
+        maps[name], info = T.tsne(emb, perplexity=args.tsne_perplexity, n_iter=args.tsne_iters, seed=args.tsne_seed, device=dev)
+        np.save(os.path.join(out_dir, "tsne_%s.npy" % name), maps[name])
+        block["kl_%s" % name] = info["kl"]
+    with open(os.path.join(out_dir, "tsne.tsv"), "w") as f:
+        for k, spk, a, b in zip(keys, speakers, maps["mu2"], maps["z1_mean"]):
+            f.write("%s\t%s\t%.6g\t%.6g\t%.6g\t%.6g\n" % (k, "-" if spk is None else spk, a[0], a[1], b[0], b[1]))
+    if known:
+        for name in maps:
+            if not T.scatter_png(os.path.join(out_dir, "tsne_%s.png" % name), maps[name], labels, "t-SNE of %s by speaker" % name):
+                print("--tsne: matplotlib is not installed, no tsne_*.png (the maps are in tsne_*.npy and tsne.tsv)")
+                break
     return block
 
 
@@ -276,6 +329,14 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("speaker verification: %s" % e, file=sys.stderr)
             return 1
+    tsne_block = None
+    if args.tsne:
+        seq_pos = np.searchsorted(np.asarray(seqs, dtype=np.int64), np.concatenate(ids).astype(np.int64))
+        try:
+            tsne_block = draw_tsne(args, [ds.seq_keys[y] for y in seqs], mu2_rows, np.concatenate(z1s), seq_pos, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("--tsne: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -291,6 +352,8 @@ def main(argv=None) -> int:
         summary["wavs"] = wavs
     if sv is not None:
         summary["speaker_verification"] = sv
+    if tsne_block is not None:
+        summary["tsne"] = tsne_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

@@ -155,6 +155,10 @@ SIGNATURES = {
     "fhvae_mel_invert": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     "fhvae_sv_hist_ws_bytes": (_i64, [_i64]),
     "fhvae_sv_hist": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "fhvae_tsne_ws_bytes": (_i64, [_i64, _i64]),
+    "fhvae_tsne_affinity": (C.c_int, [_vp, _i64, _i64, _i64, C.c_float, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "fhvae_tsne_step": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp, _i64, _vp]),
+    "fhvae_tsne_grad": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _i64, _vp]),
     "fhvae_trace_enable": (C.c_int, [C.c_int]),
     "fhvae_trace_collect": (_i64, [_vp, _vp, _vp, _i64]),
     "fhvae_to_time_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp]),
@@ -1750,6 +1754,87 @@ def sv_hist(emb, label, n_bins=4096):
     with _Timed("fhvae_sv_hist"):
         _check(lib.fhvae_sv_hist(_p(emb), emb.stride(0), _p(label), S, Dp, n_bins, _p(ws), nws, _p(hist), _stream()), "fhvae_sv_hist")
     return hist
+
+
+def _tsne_rows(x, what):
+    """(N, D) f32 rows as the t-SNE kernels take them (D padded to a multiple of 16 with zero columns: no distance changes)."""
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise RuntimeError("%s takes (N, D) float32 rows" % what)
+    N, D = x.shape
+    if N < 8 or D < 1 or D > 128:
+        raise RuntimeError("%s: N = %d rows of D = %d columns (N >= 8, 1 <= D <= 128)" % (what, N, D))
+    x = x.detach()
+    Dp = (D + 15) // 16 * 16
+    if Dp != D or x.stride(1) != 1 or x.stride(0) < D or x.stride(0) % 4 or x.data_ptr() % 16:
+        pad = torch.zeros(N, Dp, device=x.device, dtype=torch.float32)
+        pad[:, :D] = x
+        x = pad
+    return x, N, Dp
+
+
+def tsne_workspace(x):
+    """The scratch buffer tsne_affinity / tsne_step / tsne_grad take for these rows (uint8, on their device)."""
+    x, N, Dp = _tsne_rows(x, "tsne_workspace")
+    return torch.empty(int(load_library().fhvae_tsne_ws_bytes(N, Dp)), device=x.device, dtype=torch.uint8)
+
+
+def _tsne_vec(t, N, cols, what):
+    _need_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != ((N,) if cols == 1 else (N, cols)):
+        raise RuntimeError("%s must be a contiguous float32 tensor of shape %s" % (what, (N,) if cols == 1 else (N, cols)))
+    return t
+
+
+def tsne_affinity(x, perplexity, ws=None):
+    """The perplexity search of exact t-SNE (fhvae_tsne_affinity): x (N, D) f32, centred by the caller -> (beta, m, Z), each (N,)
+    f32: p_j|i = exp(-beta_i (d2(i, j) - m_i)) / Z_i has the perplexity asked for.  No (N, N) array is made."""
+    x, N, Dp = _tsne_rows(x, "tsne_affinity")
+    perplexity = float(perplexity)
+    if not (1.0 <= perplexity <= (N - 1) / 3.0):
+        raise RuntimeError("tsne_affinity: perplexity %g must lie in [1, (N - 1) / 3 = %g] for N = %d rows" % (perplexity, (N - 1) / 3.0, N))
+    if ws is None:
+        ws = tsne_workspace(x)
+    beta, m, z = (torch.empty(N, device=x.device, dtype=torch.float32) for _ in range(3))
+    with _Timed("fhvae_tsne_affinity"):
+        _check(load_library().fhvae_tsne_affinity(_p(x), x.stride(0), N, Dp, perplexity, _p(beta), _p(m), _p(z), _p(ws), ws.numel(),
+                                                  _stream()), "fhvae_tsne_affinity")
+    return beta, m, z
+
+
+def tsne_step(x, beta, m, z, y, v, g, exaggeration, momentum, lr, kl=None, ws=None):
+    """One t-SNE iteration in place on y, v (velocity), g (gains), each (N, 2) f32 (fhvae_tsne_step); kl: a 1-element f32
+    tensor that receives the KL divergence at the y the call was given, or None.  Nothing is read back; x as tsne_affinity
+    took it (a caller that loops passes rows the kernel reads in place, and one ws)."""
+    x, N, Dp = _tsne_rows(x, "tsne_step")
+    for name, t in (("beta", beta), ("m", m), ("z", z)):
+        _tsne_vec(t, N, 1, "tsne_step: " + name)
+    for name, t in (("y", y), ("v", v), ("g", g)):
+        _tsne_vec(t, N, 2, "tsne_step: " + name)
+    if kl is not None and (kl.dtype != torch.float32 or kl.numel() != 1 or not kl.is_cuda):
+        raise RuntimeError("tsne_step: kl must be a one-element float32 tensor on the device")
+    if ws is None:
+        ws = tsne_workspace(x)
+    with _Timed("fhvae_tsne_step"):
+        _check(load_library().fhvae_tsne_step(_p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), _p(v), _p(g), float(exaggeration),
+                                              float(momentum), float(lr), _p(kl), _p(ws), ws.numel(), _stream()), "fhvae_tsne_step")
+
+
+def tsne_grad(x, beta, m, z, y, exaggeration=1.0, ws=None):
+    """The gradient pass of tsne_step without the update (fhvae_tsne_grad) -> (out (N, 7) f32: F (2, with the exaggeration),
+    R (2), W, grad (2) per row; scal (2,) f32: Zq, KL)."""
+    x, N, Dp = _tsne_rows(x, "tsne_grad")
+    for name, t in (("beta", beta), ("m", m), ("z", z)):
+        _tsne_vec(t, N, 1, "tsne_grad: " + name)
+    _tsne_vec(y, N, 2, "tsne_grad: y")
+    if ws is None:
+        ws = tsne_workspace(x)
+    out = torch.empty(N, 7, device=x.device, dtype=torch.float32)
+    scal = torch.empty(2, device=x.device, dtype=torch.float32)
+    with _Timed("fhvae_tsne_grad"):
+        _check(load_library().fhvae_tsne_grad(_p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), float(exaggeration), _p(out),
+                                              _p(scal), _p(ws), ws.numel(), _stream()), "fhvae_tsne_grad")
+    return out, scal
 
 
 def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):
