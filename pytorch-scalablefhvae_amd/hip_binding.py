@@ -189,16 +189,6 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
-# ---------------------------------------------------------------------------------------------
-# second stream: the weight-gradient contractions of a net (wide GEMMs, many workgroups) run there, under the
-# next net's recurrence (<= 128 workgroups per launch, latency-bound).  Used only when every parameter has a
-# gradient sink (hip_optim.FusedAdam): nothing downstream reads those gradients before the optimizer, which joins.
-# ---------------------------------------------------------------------------------------------
-# MEASURED (MI355X, c2, B=256, bf16): enabling it made the step SLOWER (2.61 -> 2.98 ms under graph replay): the
-# concurrent GEMM workgroups take L2/LDS bandwidth from the latency-bound cells on the critical path.  Off by default.
-_SIDE = {"stream": None, "pending": False, "keep": [], "enabled": False}
-
-
 #: optional callback(sinks) fired when a net's backward recurrence has been enqueued (its parameter gradients queued behind it, or
 #: about to run): the data-parallel wrapper flushes the queue / starts the gradient all-reduce of the finished buckets there
 LSTM_BWD_REC_HOOK = {"fn": None}
@@ -222,12 +212,10 @@ def flush_param_grads():
     pend, extra = _DEFER["pending"], _DEFER["extra"]
     if not pend and not extra:
         return
-    lib = load_library()
     n, nx = len(pend), len(extra)
     arr = (C.POINTER(LstmBwdDesc) * n)(*[C.pointer(bd) for bd, _ in pend]) if n else None
     xs = (WgradDesc * nx)(*[x for x, _ in extra]) if nx else None
-    with _Timed("fhvae_lstm_param_grads_multi"):
-        _check(lib.fhvae_lstm_param_grads_multi(arr, n, xs, nx, _stream()), "fhvae_lstm_param_grads_multi")
+    _call("fhvae_lstm_param_grads_multi", arr, n, xs, nx)
     pend.clear()  # (the caching allocator keeps the released buffers ordered behind this stream's queued work)
     extra.clear()
 
@@ -247,23 +235,9 @@ def set_defer_param_grads(on: bool):
     _DEFER["enabled"] = bool(on)
 
 
-def side_stream():
-    if _SIDE["stream"] is None:
-        _SIDE["stream"] = torch.cuda.Stream()
-    return _SIDE["stream"]
-
-
 def join_side_stream():
-    """Make the current stream wait for the side stream's pending work (call before reading the gradient arena)."""
-    if _SIDE["pending"]:
-        torch.cuda.current_stream().wait_stream(_SIDE["stream"])
-        _SIDE["pending"] = False
-        _SIDE["keep"].clear()  # safe to release: the current stream is now ordered after their last use
-
-
-def set_side_stream_enabled(on: bool):
-    join_side_stream()
-    _SIDE["enabled"] = bool(on)
+    """Does nothing: the weight-gradient contractions once had a second stream to run on (measured slower, 2.61 -> 2.98 ms per
+    step under graph replay, and removed) and the optimizer joined it here.  Kept for callers outside the package."""
 
 
 class _OpTimer:
@@ -304,7 +278,7 @@ OP_TIMER = _OpTimer()
 
 def cell_trace(enable: bool):
     """Turn the in-library per-launch event trace of the LSTM step cells on/off (clears it)."""
-    _check(load_library().fhvae_trace_enable(int(enable)), "fhvae_trace_enable")
+    _check(load_library().fhvae_trace_enable(int(enable)), "fhvae_trace_enable")  # (host-side switch: no stream, no launch)
 
 
 def cell_trace_collect(cap: int = 65536):
@@ -322,7 +296,7 @@ def cell_trace_collect(cap: int = 65536):
 
 
 class _Timed:
-    """`with _Timed("fhvae_xxx"):` around a library call."""
+    """`with _Timed("fhvae_xxx"):` around several library calls that are timed as one (a single call: _call)."""
 
     def __init__(self, name):
         self.name = name
@@ -339,6 +313,19 @@ def _check(code: int, what: str):
     if code != 0:
         msg = load_library().fhvae_strerror(code).decode()
         raise RuntimeError("%s failed: %s (code %d)" % (what, msg, code))
+
+
+def _call(symbol: str, *args, timed: bool = True, label: Optional[str] = None):
+    """The one way a kernel entry point is called: `lib.<symbol>(*args, current stream)`, under the op timer as `label or symbol`
+    (timed=False: a small launch the roofline leg counts with its neighbour, or one inside a `with _Timed`), its return code
+    checked under the symbol's name.  Host-only queries (*_bytes, *_elems, fhvae_lstm_form, ...) take no stream and are called
+    on the library directly."""
+    fn = getattr(load_library(), symbol)
+    e0 = OP_TIMER.start() if (timed and OP_TIMER.on) else None
+    code = fn(*args, _stream())
+    if e0 is not None:
+        OP_TIMER.stop(label or symbol, e0)
+    _check(code, symbol)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -377,19 +364,15 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 # raw (no-autograd) calls used by the Functions below and by tests
 # ---------------------------------------------------------------------------------------------
 def raw_linear_fwd(x, w, b, relu=False):
-    lib = load_library()
     M, K = x.shape
     N = w.shape[0]
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    with _Timed("fhvae_linear_fwd"):
-        _check(lib.fhvae_linear_fwd(_p(x), x.stride(0), _p(w), w.stride(0), _p(b), _p(y), N, None, M, K, N, int(relu), F32,
-                                    _stream()), "fhvae_linear_fwd")
+    _call("fhvae_linear_fwd", _p(x), x.stride(0), _p(w), w.stride(0), _p(b), _p(y), N, None, M, K, N, int(relu), F32)
     return y
 
 
 def raw_linear_bwd(x, w, y, dy, relu, need_dx=True, need_dw=True, need_db=True, dx_out=None, dw_sink=None, db_sink=None):
     """dw_sink / db_sink: existing buffers to accumulate into (returned dw / db are then None)."""
-    lib = load_library()
     M, K = x.shape
     N = w.shape[0]
     dev = x.device
@@ -398,10 +381,8 @@ def raw_linear_bwd(x, w, y, dy, relu, need_dx=True, need_dw=True, need_db=True, 
     dx = dx_out if acc else (torch.empty(M, K, device=dev, dtype=torch.float32) if need_dx else None)
     dw = dw_sink if dw_sink is not None else (torch.zeros(N, K, device=dev, dtype=torch.float32) if need_dw else None)
     db = db_sink if db_sink is not None else (torch.zeros(N, device=dev, dtype=torch.float32) if need_db else None)
-    with _Timed("fhvae_linear_bwd"):
-        _check(lib.fhvae_linear_bwd(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), N if y is not None else 0, _p(dy),
-                                    dy.stride(0), _p(masked), _p(dx), K, _p(dw), K, _p(db), M, K, N, int(relu), int(acc),
-                                    _stream()), "fhvae_linear_bwd")
+    _call("fhvae_linear_bwd", _p(x), x.stride(0), _p(w), w.stride(0), _p(y), N if y is not None else 0, _p(dy), dy.stride(0),
+          _p(masked), _p(dx), K, _p(dw), K, _p(db), M, K, N, int(relu), int(acc))
     return dx, dw, db
 
 
@@ -444,7 +425,6 @@ class _GaussHead(torch.autograd.Function):
     def forward(ctx, h, w_mu, b_mu, w_lv, b_lv, eps):
         _need_gpu(h, w_mu, b_mu, w_lv, b_lv, eps)
         ctx.set_materialize_grads(False)  # unused outputs arrive as None in backward (no zero tensors, no reads of them)
-        lib = load_library()
         ctx.sinks = tuple(_sink(t) for t in (w_mu, b_mu, w_lv, b_lv))
         h, w_mu, b_mu, w_lv, b_lv = _f32c(h), _f32c(w_mu), _f32c(b_mu), _f32c(w_lv), _f32c(b_lv)
         M, K = h.shape
@@ -456,9 +436,8 @@ class _GaussHead(torch.autograd.Function):
             smp = torch.empty_like(mu)
         else:
             smp = None
-        with _Timed("fhvae_gauss_head_reparam_fwd"):
-            _check(lib.fhvae_gauss_head_reparam_fwd(_p(h), h.stride(0), _p(w_mu), _p(w_lv), _p(b_mu), _p(b_lv), _p(eps), _p(mu),
-                                                    _p(lv), _p(smp), M, K, D, F32, _stream()), "fhvae_gauss_head_reparam_fwd")
+        _call("fhvae_gauss_head_reparam_fwd", _p(h), h.stride(0), _p(w_mu), _p(w_lv), _p(b_mu), _p(b_lv), _p(eps), _p(mu),
+              _p(lv), _p(smp), M, K, D, F32)
         ctx.save_for_backward(h, w_mu, w_lv, eps, lv)
         if smp is None:
             smp = mu.new_empty(())  # placeholder output (value never read), never differentiable
@@ -467,7 +446,6 @@ class _GaussHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_mu, d_lv, d_s):
-        lib = load_library()
         h, w_mu, w_lv, eps, lv = ctx.saved_tensors
         if eps is None:
             d_s = None
@@ -484,10 +462,8 @@ class _GaussHead(torch.autograd.Function):
         dw_mu, db_mu, dw_lv, db_lv = outs
         g_ws = torch.empty(M, 2 * D, device=h.device, dtype=torch.float32)
         dh = torch.empty(M, K, device=h.device, dtype=torch.float32) if need_dh else None
-        with _Timed("fhvae_gauss_head_bwd"):
-            _check(lib.fhvae_gauss_head_bwd(_p(h), h.stride(0), _p(w_mu), _p(w_lv), _p(d_mu), _p(d_lv), _p(d_s), _p(eps), _p(lv),
-                                            _p(g_ws), _p(dh), K, _p(dw_mu), _p(dw_lv), _p(db_mu), _p(db_lv), M, K, D, _stream()),
-                   "fhvae_gauss_head_bwd")
+        _call("fhvae_gauss_head_bwd", _p(h), h.stride(0), _p(w_mu), _p(w_lv), _p(d_mu), _p(d_lv), _p(d_s), _p(eps), _p(lv),
+              _p(g_ws), _p(dh), K, _p(dw_mu), _p(dw_lv), _p(db_mu), _p(db_lv), M, K, D)
         dw_mu, db_mu, dw_lv, db_lv = (None if k is not None else o for k, o in zip(sk, outs))
         return dh, dw_mu, db_mu, dw_lv, db_lv, None
 
@@ -518,7 +494,6 @@ class _GaussHeadLp(torch.autograd.Function):
         """shadows: (wl, wt) already produced for these weights in this step (the LSTM forward's operand-cast launch,
         fhvae_lstm_desc.head_*), else one fhvae_head_pair_weights launch here."""
         _need_gpu(h, h_lp, w_mu, b_mu, w_lv, b_lv, eps)
-        lib = load_library()
         ctx.set_materialize_grads(False)
         ctx.sinks = tuple(_sink(t) for t in (w_mu, b_mu, w_lv, b_lv))
         w_mu, b_mu, w_lv, b_lv = _f32c(w_mu), _f32c(b_mu), _f32c(w_lv), _f32c(b_lv)
@@ -532,16 +507,14 @@ class _GaussHeadLp(torch.autograd.Function):
         else:
             wl = torch.empty(2 * D, K, device=dev, dtype=torch.bfloat16)   # [W_mu; W_lv]
             wt = torch.empty(K, ldg, device=dev, dtype=torch.bfloat16)     # [W_mu^T | W_lv^T | 0]: the backward's operand
-            _check(lib.fhvae_head_pair_weights(_p(w_mu), _p(w_lv), _p(wl), _p(wt), ldg, D, K, _stream()), "fhvae_head_pair_weights")
+            _call("fhvae_head_pair_weights", _p(w_mu), _p(w_lv), _p(wl), _p(wt), ldg, D, K, timed=False)
         out = torch.empty(M, 2 * D, device=dev, dtype=torch.float32)
         with _Timed("fhvae_gauss_head_reparam_fwd"):
-            _check(lib.fhvae_gauss_head_pair_fwd(_p(h_lp), K, _p(wl), _p(b_mu), _p(b_lv), _p(out), 2 * D, M, K, D, _stream()),
-                   "fhvae_gauss_head_pair_fwd")
+            _call("fhvae_gauss_head_pair_fwd", _p(h_lp), K, _p(wl), _p(b_mu), _p(b_lv), _p(out), 2 * D, M, K, D, timed=False)
             if eps is not None:  # a sampling head (the latents): contiguous mu, logvar and the sample from one more small launch
                 eps = _f32c(eps)
                 mu, lv, smp = (torch.empty(M, D, device=dev, dtype=torch.float32) for _ in range(3))
-                _check(lib.fhvae_gauss_reparam_pair_fwd(_p(out), 2 * D, _p(eps), _p(smp), _p(mu), _p(lv), M, D, _stream()),
-                       "fhvae_gauss_reparam_pair_fwd")
+                _call("fhvae_gauss_reparam_pair_fwd", _p(out), 2 * D, _p(eps), _p(smp), _p(mu), _p(lv), M, D, timed=False)
             else:  # the per-frame head: mu | logvar stay side by side (the lower bound reads them in place)
                 mu, lv = out[:, :D], out[:, D:]
                 smp = mu.new_empty(())  # placeholder (value never read)
@@ -582,20 +555,19 @@ class _GaussHeadLp(torch.autograd.Function):
                     d_s = _f32c(d_s)  # (a column slice of the next net's input gradient -- cat's backward -- goes in as it is)
                 g_lp = torch.empty(M, ldg, device=dev, dtype=torch.bfloat16)
                 # (the two bias gradients = column sums of g_lp come out of the same launch)
-                _check(lib.fhvae_gauss_reparam_bwd_pair(_p(d_mu), _p(d_lv), _p(d_s), d_s.stride(0) if d_s is not None else D, _p(eps), _p(lv), lv.stride(0), _p(g_lp), ldg,
-                                                        _p(outs[1]), _p(outs[3]), M, D, _stream()), "fhvae_gauss_reparam_bwd_pair")
+                _call("fhvae_gauss_reparam_bwd_pair", _p(d_mu), _p(d_lv), _p(d_s), d_s.stride(0) if d_s is not None else D,
+                      _p(eps), _p(lv), lv.stride(0), _p(g_lp), ldg, _p(outs[1]), _p(outs[3]), M, D, timed=False)
                 db_done = True
             # every parameter has a gradient sink: the two weight-gradient contractions join the nets' grouped launch
             xs = None
-            if _DEFER["enabled"] and not _SIDE["enabled"] and all(k is not None for k in sk):
+            if _DEFER["enabled"] and all(k is not None for k in sk):
                 xs = [WgradDesc(_p(g_lp) + 2 * i * D, ldg, i * D, _p(h_lp), K, _p(outs[2 * i]), K, D, K, M) for i in range(2)]
                 if not all(lib.fhvae_wgrad_desc_ok(C.byref(x)) for x in xs):
                     xs = None
             dws = (None, None) if xs is not None else (outs[0], outs[2])
-            _check(lib.fhvae_gauss_head_bwd_pair(_p(h_lp), K, _p(wt), ldg, _p(g_lp), ldg, _p(colsum), colsum.shape[0] if colsum is not None else 0, _p(dh), K,
-                                                 _p(dws[0]), _p(dws[1]),
-                                                 None if db_done else _p(outs[1]), None if db_done else _p(outs[3]), M, K, D, _stream()),
-                   "fhvae_gauss_head_bwd_pair")
+            _call("fhvae_gauss_head_bwd_pair", _p(h_lp), K, _p(wt), ldg, _p(g_lp), ldg, _p(colsum),
+                  colsum.shape[0] if colsum is not None else 0, _p(dh), K, _p(dws[0]), _p(dws[1]),
+                  None if db_done else _p(outs[1]), None if db_done else _p(outs[3]), M, K, D, timed=False)
             if xs is not None:
                 _DEFER["extra"].extend((x, (g_lp, h_lp, outs[0], outs[2])) for x in xs)
         dw_mu, db_mu, dw_lv, db_lv = (None if k is not None else o for k, o in zip(sk, outs))
@@ -626,7 +598,7 @@ def cast_bf16(t: torch.Tensor) -> torch.Tensor:
     t = _f32c(t.detach())
     out = torch.empty(t.shape, device=t.device, dtype=torch.bfloat16)
     R = t.shape[0]
-    _check(load_library().fhvae_cast_bf16(_p(t), _p(out), None, R, t.numel() // R, _stream()), "fhvae_cast_bf16")
+    _call("fhvae_cast_bf16", _p(t), _p(out), None, R, t.numel() // R, timed=False)
     return out
 
 
@@ -634,18 +606,15 @@ def to_time_major(x: torch.Tensor, with_bf16: bool = False):
     """(B,T,F) -> (T,B,F) copy (input data: no gradient).  with_bf16: also return the bf16 copy the bf16 LSTM nets
     consume (one pass produces both, and both encoders share it)."""
     _need_gpu(x)
-    lib = load_library()
     x = _f32c(x.detach())
     B, T, F_ = x.shape
     out = torch.empty(T, B, F_, device=x.device, dtype=torch.float32)
     if with_bf16:
         lp = torch.empty(T, B, F_, device=x.device, dtype=torch.bfloat16)
-        with _Timed("fhvae_to_time_major"):
-            _check(lib.fhvae_to_time_major(_p(x), _p(lp), _p(out), B, T, F_, BF16, _stream()), "fhvae_to_time_major")
+        _call("fhvae_to_time_major", _p(x), _p(lp), _p(out), B, T, F_, BF16)
         out._fh_lp = lp  # rides along with the f32 tensor; hip_binding.lstm_seq picks it up
         return out
-    with _Timed("fhvae_to_time_major"):
-        _check(lib.fhvae_to_time_major(_p(x), _p(out), None, B, T, F_, F32, _stream()), "fhvae_to_time_major")
+    _call("fhvae_to_time_major", _p(x), _p(out), None, B, T, F_, F32)
     return out
 
 
@@ -720,6 +689,86 @@ def lstm_sync_status() -> int:
     return st
 
 
+def _lstm_forward(x_tm, xc, x_lp, T, dtype, top, head, params, save):
+    """What the saving forward (_LstmSeq.forward, save=True: fhvae_lstm_seq_fwd) and the inference forward (lstm_seq_infer,
+    save=False: fhvae_lstm_seq_infer) share: operand normalisation and shape checks, the outputs, the descriptor, the bf16
+    workspace, the head's stacked operands, the layer-0 projection workspace, the call and the `_fh_lp` / `_fh_head` tags of
+    the outputs.  save: also the (L,T,B,H) cell states, the activated gates, the workspace in f32 mode (transposed weights for
+    the backward cells) and an f32 tensor that routes the gradient for top == 1; otherwise gates = NULL and the cell states
+    are what fhvae_lstm_infer_cs_elems asks for.
+    -> (out or None (top == 0), hn, dims, layout id, the tensors the backward reads)."""
+    lib = load_library()
+    _need_gpu(x_tm, xc, *params)
+    L = len(params) // 4
+    assert len(params) == 4 * L and 1 <= L <= MAX_LAYERS
+    params = [_f32c(p) for p in params]
+    H = params[1].shape[1]
+    x_tm = _f32c(x_tm) if x_tm is not None else None
+    xc = _f32c(xc) if xc is not None else None
+    I = x_tm.shape[2] if x_tm is not None else 0
+    Ic = xc.shape[1] if xc is not None else 0
+    B = x_tm.shape[1] if x_tm is not None else xc.shape[0]
+    if x_tm is not None:
+        assert x_tm.shape[0] == T
+    assert params[0].shape == (4 * H, I + Ic), (params[0].shape, H, I, Ic)
+    dev = params[0].device
+    f32 = dict(device=dev, dtype=torch.float32)
+    bf = dtype == BF16
+    if not bf:
+        top = 2
+    hs = torch.empty(L, T, B, H, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
+    hn = torch.empty(B, L * H, **f32)
+    # the latent head's bf16 operand: only where the final states ARE the output (the encoders: top == 0)
+    hn_lp = torch.empty(B, L * H, device=dev, dtype=torch.bfloat16) if (bf and top == 0) else None
+    hs_top = torch.empty(T, B, H, **f32) if (bf and (top == 2 or (save and top == 1))) else None
+    cs = torch.empty(L, T, B, H, **f32) if save else None
+    gates = torch.empty(L, T, B, 4 * H, device=dev, dtype=hs.dtype) if save else None
+    d = LstmDesc()
+    dims = (L, B, T, I, Ic, H)
+    _fill_lstm_desc(d, dtype, dims, x_tm, xc, params, x_lp)
+    # workspace: bf16 operand copies + sync block (bf16 mode) / transposed f32 weights for the backward cells (f32 mode)
+    lp = torch.empty(int(lib.fhvae_lstm_lp_bytes(C.byref(d))), device=dev, dtype=torch.uint8) if (bf or save) else None
+    if bf:
+        LSTM_WORKSPACES.append(lp)
+        del LSTM_WORKSPACES[:-16]
+    d.hs, d.cs, d.gates, d.hn, d.hs_top_f32, d.lp = _p(hs), _p(cs), _p(gates), _p(hn), _p(hs_top if top == 2 else None), _p(lp)
+    d.hn_lp = _p(hn_lp)
+    shadows = None
+    if bf and head is not None and head_shadow_shapes(head[0]) is not None:
+        hw_mu, hw_lv = _f32c(head[0].detach()), _f32c(head[1].detach())
+        (sl, st_) = head_shadow_shapes(hw_mu)
+        shadows = (torch.empty(sl, device=dev, dtype=torch.bfloat16), torch.empty(st_, device=dev, dtype=torch.bfloat16))
+        d.head_w_mu, d.head_w_lv, d.head_wl, d.head_wt = _p(hw_mu), _p(hw_lv), _p(shadows[0]), _p(shadows[1])
+        d.head_D, d.head_K, d.head_ldt = hw_mu.shape[0], hw_mu.shape[1], st_[1]
+    # layer-0 input projection workspace: (T,B,4H) only for the schedules that read it (168 MB per net at B = 2048, H = 256)
+    pre = torch.empty(max(1, int(lib.fhvae_lstm_pre_elems(C.byref(d)))), **f32)
+    d.pre = _p(pre)
+    if not save:  # a two-slot ring for the per-step schedules, nothing for the persistent ones
+        n_cs = int(lib.fhvae_lstm_infer_cs_elems(C.byref(d)))
+        cs = torch.empty(n_cs, **f32) if n_cs > 0 else None
+        d.cs = _p(cs)
+    LAST_LSTM_FORM["form"] = int(lib.fhvae_lstm_form(C.byref(d)))
+    _call("fhvae_lstm_seq_fwd" if save else "fhvae_lstm_seq_infer", C.byref(d))
+    layout_id = LAST_LSTM_FORM["layout"] = int(lib.fhvae_lstm_layout_id(C.byref(d)))  # the schedule this forward took
+    if hn_lp is not None:
+        hn._fh_lp = hn_lp  # the same values in bf16, written by the forward itself (fhvae_lstm_desc.hn_lp)
+    hn._fh_head = shadows
+    out = None
+    if top != 0:
+        # (inference, bf16, top == 1: the bf16 top-layer states themselves -- no f32 tensor to route a gradient through)
+        out = hs_top if hs_top is not None else hs[L - 1]
+        if bf:
+            out._fh_lp = hs[L - 1]  # the same values in bf16 (what the recurrence itself consumed): operand of a bf16 head
+        out._fh_head = shadows
+    return out, hn, dims, layout_id, (x_tm, xc, hs, cs, gates, lp, *params)
+
+
+def _lstm_bwd_phase(bd, phase, label=None):
+    """fhvae_lstm_seq_bwd: phase 0 = recurrence + parameter gradients, 1 = the recurrence only, 2 = the parameter gradients."""
+    bd.phase = phase
+    _call("fhvae_lstm_seq_bwd", C.byref(bd), label=label)
+
+
 class _LstmSeq(torch.autograd.Function):
     """Multi-layer LSTM over the whole segment (K1).  Inputs: x_tm (T,B,I) or None, xc (B,Ic) or None,
     then per layer w_ih, w_hh, b_ih, b_hh (all f32).  Outputs: hs_top (T,B,H) f32 and hn (B, L*H).
@@ -731,75 +780,15 @@ class _LstmSeq(torch.autograd.Function):
         gradient, its values are undefined and the data is its `_fh_lp` bf16 twin; 0 = no per-step output at all (only hn).
         head: None or (w_mu, w_lv) of the Gaussian head that reads this net's output (bf16 mode): its stacked bf16 operands are
         made by the forward's operand-cast launch and ride on the outputs as `_fh_head`."""
-        lib = load_library()
         ctx.set_materialize_grads(False)  # encoders use only hn, the decoder only hs_top: the other gradient stays None
-        _need_gpu(x_tm, xc, *params)
-        L = len(params) // 4
-        assert len(params) == 4 * L and 1 <= L <= MAX_LAYERS
         ctx.sinks = [_sink(p) for p in params]
-        params = [_f32c(p) for p in params]
-        H = params[1].shape[1]
-        x_lp = getattr(x_tm, "_fh_lp", None) if x_tm is not None else None
-        x_tm = _f32c(x_tm) if x_tm is not None else None
-        xc = _f32c(xc) if xc is not None else None
-        I = x_tm.shape[2] if x_tm is not None else 0
-        Ic = xc.shape[1] if xc is not None else 0
-        B = x_tm.shape[1] if x_tm is not None else xc.shape[0]
-        if x_tm is not None:
-            assert x_tm.shape[0] == T
-        assert params[0].shape == (4 * H, I + Ic), (params[0].shape, H, I, Ic)
-        dev = params[0].device
-        f32 = dict(device=dev, dtype=torch.float32)
-        bf = dtype == BF16
-        hs = torch.empty(L, T, B, H, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
-        cs = torch.empty(L, T, B, H, **f32)
-        gates = torch.empty(L, T, B, 4 * H, device=dev, dtype=hs.dtype)
-        hn = torch.empty(B, L * H, **f32)
-        # the latent head's bf16 operand: only where the final states ARE the output (the encoders: top == 0)
-        hn_lp = torch.empty(B, L * H, device=dev, dtype=torch.bfloat16) if (bf and top == 0) else None
-        if not bf:
-            top = 2
-        hs_top = torch.empty(T, B, H, **f32) if (bf and top != 0) else None
-        d = LstmDesc()
-        dims = (L, B, T, I, Ic, H)
-        _fill_lstm_desc(d, dtype, dims, x_tm, xc, params, x_lp)
-        # workspace: bf16 operand copies + sync block (bf16 mode) / transposed f32 weights for the backward cells (f32 mode)
-        lp = torch.empty(int(lib.fhvae_lstm_lp_bytes(C.byref(d))), device=dev, dtype=torch.uint8)
-        if bf:
-            LSTM_WORKSPACES.append(lp)
-            del LSTM_WORKSPACES[:-16]
-        d.lp = _p(lp)
-        d.hs, d.cs, d.gates, d.hn, d.hs_top_f32, d.lp = _p(hs), _p(cs), _p(gates), _p(hn), _p(hs_top if top == 2 else None), _p(lp)
-        d.hn_lp = _p(hn_lp)
-        shadows = None
-        if bf and head is not None and head_shadow_shapes(head[0]) is not None:
-            hw_mu, hw_lv = _f32c(head[0].detach()), _f32c(head[1].detach())
-            (sl, st_) = head_shadow_shapes(hw_mu)
-            shadows = (torch.empty(sl, device=dev, dtype=torch.bfloat16), torch.empty(st_, device=dev, dtype=torch.bfloat16))
-            d.head_w_mu, d.head_w_lv, d.head_wl, d.head_wt = _p(hw_mu), _p(hw_lv), _p(shadows[0]), _p(shadows[1])
-            d.head_D, d.head_K, d.head_ldt = hw_mu.shape[0], hw_mu.shape[1], st_[1]
-        # layer-0 input projection workspace: (T,B,4H) only for the schedules that read it (168 MB per net at B = 2048, H = 256)
-        pre = torch.empty(max(1, int(lib.fhvae_lstm_pre_elems(C.byref(d)))), **f32)
-        d.pre = _p(pre)
-        LAST_LSTM_FORM["form"] = int(lib.fhvae_lstm_form(C.byref(d)))
-        with _Timed("fhvae_lstm_seq_fwd"):
-            _check(lib.fhvae_lstm_seq_fwd(C.byref(d), _stream()), "fhvae_lstm_seq_fwd")
-        ctx.dims, ctx.dtype = dims, dtype
-        ctx.x_lp = x_lp
-        ctx.layout_id = int(lib.fhvae_lstm_layout_id(C.byref(d)))  # the schedule this forward took (see backward)
-        LAST_LSTM_FORM["layout"] = ctx.layout_id
-        ctx.save_for_backward(x_tm, xc, hs, cs, gates, lp, *params)
-        if hn_lp is not None:
-            hn._fh_lp = hn_lp  # the same values in bf16, written by the forward itself (fhvae_lstm_desc.hn_lp)
-        hn._fh_head = shadows
-        if top == 0:
+        ctx.x_lp = getattr(x_tm, "_fh_lp", None)
+        out, hn, ctx.dims, ctx.layout_id, saved = _lstm_forward(x_tm, xc, ctx.x_lp, T, dtype, top, head, params, save=True)
+        ctx.dtype = dtype
+        ctx.save_for_backward(*saved)
+        if out is None:
             out = hn.new_empty(())  # placeholder (value never read): this net's per-step states are not an output
             ctx.mark_non_differentiable(out)
-            return out, hn
-        out = hs_top if bf else hs[L - 1]
-        if bf:
-            out._fh_lp = hs[L - 1]  # the same values in bf16 (what the recurrence itself consumed): operand of a bf16 head
-        out._fh_head = shadows
         return out, hn
 
     @staticmethod
@@ -835,42 +824,21 @@ class _LstmSeq(torch.autograd.Function):
         n_below = int(lib.fhvae_lstm_ws_below_elems(C.byref(d)))
         ws_below = torch.empty(n_below, **f32) if n_below > 0 else None
         bd.ws_below = _p(ws_below)
-        if (_DEFER["enabled"] and not _SIDE["enabled"] and all(sk is not None for sk in ctx.sinks)):
+        hook = LSTM_BWD_REC_HOOK["fn"]
+        if _DEFER["enabled"] and all(sk is not None for sk in ctx.sinks):
             # recurrence now; the parameter gradients with those of the other nets at the optimizer (flush_param_grads)
-            bd.phase = 1
-            with _Timed("fhvae_lstm_seq_bwd"):
-                _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
+            _lstm_bwd_phase(bd, 1)
             _DEFER["pending"].append((bd, (x_tm, xc, hs, cs, gates, lp, pre, dgates, dgsum, dc, d_hs_top, d_hn, params, ctx.x_lp)))
-            if LSTM_BWD_REC_HOOK["fn"] is not None:  # the distributed runner decides when to flush the queue and start collectives
-                LSTM_BWD_REC_HOOK["fn"](ctx.sinks)
-            return (None, d_xc, None, None, None, None, *[None] * len(params))
-        if _SIDE["enabled"] and all(sk is not None for sk in ctx.sinks):
-            # recurrence on this stream; the weight-gradient contractions on the side stream, joined by the optimizer
-            bd.phase = 1
-            with _Timed("fhvae_lstm_seq_bwd"):
-                _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
-            main, side = torch.cuda.current_stream(), side_stream()
-            side.wait_stream(main)
-            bd.phase = 2
-            with torch.cuda.stream(side):
-                with _Timed("fhvae_lstm_seq_bwd(param grads, side stream)"):
-                    _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
-            _SIDE["pending"] = True
-            _SIDE["keep"].append((x_tm, xc, hs, cs, gates, lp, dgates, dgsum, dc, d_hs_top, d_hn, params))
-        elif LSTM_BWD_REC_HOOK["fn"] is not None:
+            if hook is not None:  # the distributed runner decides when to flush the queue and start collectives
+                hook(ctx.sinks)
+        elif hook is not None:
             # recurrence, hook (the distributed runner starts collectives that may overlap the weight-gradient
             # contractions but must not overlap a persistent recurrence kernel), then the parameter gradients
-            bd.phase = 1
-            with _Timed("fhvae_lstm_seq_bwd"):
-                _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
-            LSTM_BWD_REC_HOOK["fn"](ctx.sinks)
-            bd.phase = 2
-            with _Timed("fhvae_lstm_seq_bwd(param grads)"):
-                _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
+            _lstm_bwd_phase(bd, 1)
+            hook(ctx.sinks)
+            _lstm_bwd_phase(bd, 2, "fhvae_lstm_seq_bwd(param grads)")
         else:
-            bd.phase = 0
-            with _Timed("fhvae_lstm_seq_bwd"):
-                _check(lib.fhvae_lstm_seq_bwd(C.byref(bd), _stream()), "fhvae_lstm_seq_bwd")
+            _lstm_bwd_phase(bd, 0)
         return (None, d_xc, None, None, None, None, *[None if sk is not None else g for g, sk in zip(grads, ctx.sinks)])
 
 
@@ -887,67 +855,9 @@ def lstm_seq_infer(x_tm, xc, T, params: Sequence[torch.Tensor], dtype: int = F32
     Same arguments, same schedule, bit-identical values; returns (hs_top or None (top == 0), hn) with the same `_fh_lp` /
     `_fh_head` attributes (bf16, top == 1: hs_top is the bf16 top-layer states, as its `_fh_lp`).  Not differentiable: for
     inference (encode / decode)."""
-    lib = load_library()
-    _need_gpu(x_tm, xc, *params)
-    L = len(params) // 4
-    assert len(params) == 4 * L and 1 <= L <= MAX_LAYERS
-    T, dtype, top = int(T), int(dtype), int(top)
-    params = [_f32c(p.detach()) for p in params]
-    H = params[1].shape[1]
-    x_lp = getattr(x_tm, "_fh_lp", None) if x_tm is not None else None
-    x_tm = _f32c(x_tm.detach()) if x_tm is not None else None
-    xc = _f32c(xc.detach()) if xc is not None else None
-    I = x_tm.shape[2] if x_tm is not None else 0
-    Ic = xc.shape[1] if xc is not None else 0
-    B = x_tm.shape[1] if x_tm is not None else xc.shape[0]
-    if x_tm is not None:
-        assert x_tm.shape[0] == T
-    assert params[0].shape == (4 * H, I + Ic), (params[0].shape, H, I, Ic)
-    dev = params[0].device
-    f32 = dict(device=dev, dtype=torch.float32)
-    bf = dtype == BF16
-    hs = torch.empty(L, T, B, H, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
-    hn = torch.empty(B, L * H, **f32)
-    hn_lp = torch.empty(B, L * H, device=dev, dtype=torch.bfloat16) if (bf and top == 0) else None
-    if not bf:
-        top = 2
-    hs_top = torch.empty(T, B, H, **f32) if (bf and top == 2) else None
-    d = LstmDesc()
-    dims = (L, B, T, I, Ic, H)
-    _fill_lstm_desc(d, dtype, dims, x_tm, xc, params, x_lp)
-    lp = None
-    if bf:  # bf16 operand copies + the persistent kernels' sync block (f32 mode: the workspace only serves the backward)
-        lp = torch.empty(int(lib.fhvae_lstm_lp_bytes(C.byref(d))), device=dev, dtype=torch.uint8)
-        LSTM_WORKSPACES.append(lp)
-        del LSTM_WORKSPACES[:-16]
-    d.lp = _p(lp)
-    d.hs, d.gates, d.hn, d.hs_top_f32, d.hn_lp = _p(hs), None, _p(hn), _p(hs_top), _p(hn_lp)
-    shadows = None
-    if bf and head is not None and head_shadow_shapes(head[0]) is not None:
-        hw_mu, hw_lv = _f32c(head[0].detach()), _f32c(head[1].detach())
-        (sl, st_) = head_shadow_shapes(hw_mu)
-        shadows = (torch.empty(sl, device=dev, dtype=torch.bfloat16), torch.empty(st_, device=dev, dtype=torch.bfloat16))
-        d.head_w_mu, d.head_w_lv, d.head_wl, d.head_wt = _p(hw_mu), _p(hw_lv), _p(shadows[0]), _p(shadows[1])
-        d.head_D, d.head_K, d.head_ldt = hw_mu.shape[0], hw_mu.shape[1], st_[1]
-    pre = torch.empty(max(1, int(lib.fhvae_lstm_pre_elems(C.byref(d)))), **f32)
-    d.pre = _p(pre)
-    n_cs = int(lib.fhvae_lstm_infer_cs_elems(C.byref(d)))
-    cs = torch.empty(n_cs, **f32) if n_cs > 0 else None
-    d.cs = _p(cs)
-    LAST_LSTM_FORM["form"] = int(lib.fhvae_lstm_form(C.byref(d)))
-    with _Timed("fhvae_lstm_seq_infer"):
-        _check(lib.fhvae_lstm_seq_infer(C.byref(d), _stream()), "fhvae_lstm_seq_infer")
-    LAST_LSTM_FORM["layout"] = int(lib.fhvae_lstm_layout_id(C.byref(d)))
-    if hn_lp is not None:
-        hn._fh_lp = hn_lp
-    hn._fh_head = shadows
-    if top == 0:
-        return None, hn
-    # (bf16, top == 1: the returned tensor is the bf16 top-layer states themselves -- no f32 tensor to route a gradient through)
-    out = hs_top if (bf and top == 2) else hs[L - 1]
-    if bf:
-        out._fh_lp = hs[L - 1]
-    out._fh_head = shadows
+    x_lp = getattr(x_tm, "_fh_lp", None)
+    x_tm, xc = (t.detach() if t is not None else None for t in (x_tm, xc))
+    out, hn = _lstm_forward(x_tm, xc, x_lp, int(T), int(dtype), int(top), head, [p.detach() for p in params], save=False)[:2]
     return out, hn
 
 
@@ -967,23 +877,17 @@ def lstm_seq_eval(x_tm, xc, T, params, dtype=F32, top=2, head=None):
 
 def raw_gather_rows(table, idx, idx_offset=0):
     """rows = table[idx - idx_offset], zeros where the row is outside the table (a shard's view)."""
-    lib = load_library()
     S, D = table.shape
     B = idx.shape[0]
     out = torch.empty(B, D, device=table.device, dtype=torch.float32)
-    with _Timed("fhvae_mu2_gather_fwd"):
-        _check(lib.fhvae_mu2_gather_fwd(_p(table), _p(idx), idx_offset, _p(out), B, S, D, None, _stream()),
-               "fhvae_mu2_gather_fwd")
+    _call("fhvae_mu2_gather_fwd", _p(table), _p(idx), idx_offset, _p(out), B, S, D, None)
     return out
 
 
 def raw_scatter_rows_(dtable, drows, idx, idx_offset=0, scale=1.0):
     """dtable[idx - idx_offset] += scale * drows (rows outside the table skipped)."""
-    lib = load_library()
     S, D = dtable.shape
-    with _Timed("fhvae_mu2_gather_bwd"):
-        _check(lib.fhvae_mu2_gather_bwd(_p(drows), _p(idx), idx_offset, _p(dtable), idx.shape[0], S, D, float(scale),
-                                        _stream()), "fhvae_mu2_gather_bwd")
+    _call("fhvae_mu2_gather_bwd", _p(drows), _p(idx), idx_offset, _p(dtable), idx.shape[0], S, D, float(scale))
 
 
 class _Mu2Gather(torch.autograd.Function):
@@ -1030,7 +934,6 @@ class _Elbo(torch.autograd.Function):
     def forward(ctx, x, x_mu, x_lv, z1_mu, z1_lv, z2_mu, z2_lv, mu2, num_segs, layout, reference_detach):
         _need_gpu(x, x_mu, x_lv, z1_mu, z1_lv, z2_mu, z2_lv, mu2)
         ctx.set_materialize_grads(False)  # the loss uses lower_bound only; the four reporting outputs carry no gradient
-        lib = load_library()
         B, T, F_, xs, xos = layout
         # mu | logvar side by side in one (rows, 2F) buffer (the per-frame head's single projection): read in place through the
         # row stride, and the backward writes its two gradients side by side too
@@ -1048,8 +951,7 @@ class _Elbo(torch.autograd.Function):
         d = ElboDesc()
         _fill_elbo_desc(d, ts[0], xs, ts[1], ts[2], xos, *ts[3:], num_segs, B, T, F_)
         d.lower_bound, d.log_px_z, d.neg_kld_z1, d.neg_kld_z2, d.log_pmu2 = (_p(o) for o in outs)
-        with _Timed("fhvae_elbo_fwd"):
-            _check(lib.fhvae_elbo_fwd(C.byref(d), _stream()), "fhvae_elbo_fwd")
+        _call("fhvae_elbo_fwd", C.byref(d))
         ctx.layout, ctx.detach = layout, bool(reference_detach)
         ctx.nsegs = num_segs
         ctx.save_for_backward(*ts)
@@ -1087,8 +989,7 @@ class _Elbo(torch.autograd.Function):
         dz = [torch.empty_like(t) for t in ts[3:8]]
         bd.d_x_mu, bd.d_x_lv = _p(d_xmu), _p(d_xlv)
         bd.d_z1_mu, bd.d_z1_lv, bd.d_z2_mu, bd.d_z2_lv, bd.d_mu2 = (_p(t) for t in dz)
-        with _Timed("fhvae_elbo_bwd"):
-            _check(lib.fhvae_elbo_bwd(C.byref(bd), _stream()), "fhvae_elbo_bwd")
+        _call("fhvae_elbo_bwd", C.byref(bd))
         if side is not None:
             _PAIR_GRAD["latest"] = side + (dbuf._version,)  # (recorded after the kernel call: ctypes writes do not count)
         return (None, d_xmu, d_xlv, *dz, None, None, None)
@@ -1106,23 +1007,18 @@ class _FusedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lower_bound, log_qy, alpha):
         _need_gpu(lower_bound, log_qy)
-        lib = load_library()
         lb, qy = _f32c(lower_bound), _f32c(log_qy)
         out = torch.empty((), device=lb.device, dtype=torch.float32)
-        with _Timed("fhvae_loss_fwd"):
-            _check(lib.fhvae_loss_fwd(_p(lb), _p(qy), float(alpha), _p(out), lb.numel(), _device_words(lb.device)[1:].data_ptr(),
-                                      _stream()), "fhvae_loss_fwd")
+        _call("fhvae_loss_fwd", _p(lb), _p(qy), float(alpha), _p(out), lb.numel(), _device_words(lb.device)[1:].data_ptr())
         ctx.alpha, ctx.B = float(alpha), lb.numel()
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = load_library()
         g = _f32c(g)
         d_lb = torch.empty(ctx.B, device=g.device, dtype=torch.float32)
         d_qy = torch.empty((), device=g.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
-        with _Timed("fhvae_loss_bwd"):
-            _check(lib.fhvae_loss_bwd(_p(g), ctx.alpha, _p(d_lb), _p(d_qy), ctx.B, _stream()), "fhvae_loss_bwd")
+        _call("fhvae_loss_bwd", _p(g), ctx.alpha, _p(d_lb), _p(d_qy), ctx.B)
         return d_lb, d_qy, None
 
 
@@ -1141,9 +1037,8 @@ def raw_disc_fwd(q, table, idx, row0=0, want_ce=True, lp=False, out3=None, ce_sc
     ws = torch.empty(max(int(lib.fhvae_disc_lse_ws_bytes(B, S)), 8), device=dev, dtype=torch.uint8)
     rmax, rsum, tgt = (out3[0], out3[1], out3[2]) if out3 is not None else (torch.empty(B, device=dev, dtype=torch.float32) for _ in range(3))
     ce = torch.empty((), device=dev, dtype=torch.float32) if want_ce else None
-    with _Timed("fhvae_disc_lse_fwd"):
-        _check(lib.fhvae_disc_lse_fwd(_p(q), _p(table), _p(idx), row0, INV_TWO_VAR, _p(rmax), _p(rsum), _p(tgt), _p(ce), float(ce_scale),
-                                      _p(ws), B, S, D, BF16 if lp else F32, _stream()), "fhvae_disc_lse_fwd")
+    _call("fhvae_disc_lse_fwd", _p(q), _p(table), _p(idx), row0, INV_TWO_VAR, _p(rmax), _p(rsum), _p(tgt), _p(ce),
+          float(ce_scale), _p(ws), B, S, D, BF16 if lp else F32)
     return rmax, rsum, tgt, ce
 
 
@@ -1164,64 +1059,54 @@ def raw_disc_bwd(q, table, idx, rmax, rsum, g_scale, g_mul, row0=0, need_dq=True
         ws_bytes = DISC_BWD_WS["bytes"]
     nws = int(lib.fhvae_disc_lse_bwd_ws_bytes(B, S, D)) if ws_bytes is None else int(ws_bytes)
     ws = torch.empty(nws, device=q.device, dtype=torch.uint8) if (need_dq and dt is not None and nws > 0) else None
-    with _Timed("fhvae_disc_lse_bwd"):
-        _check(lib.fhvae_disc_lse_bwd(_p(q), _p(table), _p(idx), row0, INV_TWO_VAR, _p(rmax), _p(rsum), _p(g_scale), float(g_mul),
-                                      _p(dq), _p(dt), _p(ws), nws if ws is not None else 0, B, S, D, BF16 if lp else F32, _stream()),
-               "fhvae_disc_lse_bwd")
+    _call("fhvae_disc_lse_bwd", _p(q), _p(table), _p(idx), row0, INV_TWO_VAR, _p(rmax), _p(rsum), _p(g_scale), float(g_mul),
+          _p(dq), _p(dt), _p(ws), nws if ws is not None else 0, B, S, D, BF16 if lp else F32)
     return dq, (None if dt_sink is not None else dt)
 
 
 def shard_pack(q, idx):
     """[q | int32 bits of idx] rows (fhvae_shard_pack)."""
-    lib = load_library()
     B, D = q.shape
     out = torch.empty(B, D + 1, device=q.device, dtype=torch.float32)
-    _check(lib.fhvae_shard_pack(_p(q), _p(idx), _p(out), B, D, _stream()), "fhvae_shard_pack")
+    _call("fhvae_shard_pack", _p(q), _p(idx), _p(out), B, D, timed=False)
     return out
 
 
 def shard_unpack(pk):
-    lib = load_library()
     N, D = pk.shape[0], pk.shape[1] - 1
     q = torch.empty(N, D, device=pk.device, dtype=torch.float32)
     idx = torch.empty(N, device=pk.device, dtype=torch.int64)
-    _check(lib.fhvae_shard_unpack(_p(pk), _p(q), _p(idx), N, D, _stream()), "fhvae_shard_unpack")
+    _call("fhvae_shard_unpack", _p(pk), _p(q), _p(idx), N, D, timed=False)
     return q, idx
 
 
 def disc_merge_partials(parts):
     """parts (W, 3, N) -> (row_max, row_sumexp, tgt_logit) of the whole table (fhvae_disc_merge_partials)."""
-    lib = load_library()
     W, _, N = parts.shape
     m, s, t = (torch.empty(N, device=parts.device, dtype=torch.float32) for _ in range(3))
-    _check(lib.fhvae_disc_merge_partials(_p(parts), _p(m), _p(s), _p(t), W, N, _stream()), "fhvae_disc_merge_partials")
+    _call("fhvae_disc_merge_partials", _p(parts), _p(m), _p(s), _p(t), W, N, timed=False)
     return m, s, t
 
 
 def shard_bwd_pack(dq_all, dq_scale, dmu2_local, own0, n_all, D):
-    lib = load_library()
     ref = dq_all if dq_all is not None else dmu2_local
     out = torch.empty(n_all, 2 * D, device=ref.device, dtype=torch.float32)
     n_own = dmu2_local.shape[0] if dmu2_local is not None else 0
-    _check(lib.fhvae_shard_bwd_pack(_p(dq_all), float(dq_scale), _p(dmu2_local), own0, n_own, _p(out), n_all, D, _stream()),
-           "fhvae_shard_bwd_pack")
+    _call("fhvae_shard_bwd_pack", _p(dq_all), float(dq_scale), _p(dmu2_local), own0, n_own, _p(out), n_all, D, timed=False)
     return out
 
 
 def shard_bwd_unpack(buf, own0, n_own, want_dq=True, want_dmu2=True):
-    lib = load_library()
     N, D = buf.shape[0], buf.shape[1] // 2
     dq = torch.empty(n_own, D, device=buf.device, dtype=torch.float32) if want_dq else None
     dm = torch.empty(N, D, device=buf.device, dtype=torch.float32) if want_dmu2 else None
-    _check(lib.fhvae_shard_bwd_unpack(_p(buf), own0, n_own, _p(dq), _p(dm), N, D, _stream()), "fhvae_shard_bwd_unpack")
+    _call("fhvae_shard_bwd_unpack", _p(buf), own0, n_own, _p(dq), _p(dm), N, D, timed=False)
     return dq, dm
 
 
 def raw_disc_ce_mean(m, s, tgt, scale=1.0):
-    lib = load_library()
     ce = torch.empty((), device=m.device, dtype=torch.float32)
-    with _Timed("fhvae_disc_ce_mean"):
-        _check(lib.fhvae_disc_ce_mean(_p(m), _p(s), _p(tgt), _p(ce), float(scale), m.numel(), _stream()), "fhvae_disc_ce_mean")
+    _call("fhvae_disc_ce_mean", _p(m), _p(s), _p(tgt), _p(ce), float(scale), m.numel())
     return ce
 
 
@@ -1255,43 +1140,35 @@ def disc_lse(q, table, idx, lp=False, sign=1.0):
     return _DiscLse.apply(q, table, idx, bool(lp), float(sign))
 
 
-def wgrad_bf16_(c, a, b):
-    """c[M,N] (f32) += a[K,M]^T . b[K,N] for bf16 a, b whose rows are the contraction index (fhvae_wgrad_bf16)."""
-    lib = load_library()
+def _wgrad_(symbol, dtype, c, a, b):
     _need_gpu(c, a, b)
-    assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and c.dtype == torch.float32
+    assert a.dtype == dtype and b.dtype == dtype and c.dtype == torch.float32
     assert a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1 and a.shape[0] == b.shape[0]
     K, M = a.shape
     N = b.shape[1]
-    with _Timed("fhvae_wgrad_bf16"):
-        _check(lib.fhvae_wgrad_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0), M, N, K, _stream()), "fhvae_wgrad_bf16")
+    _call(symbol, _p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0), M, N, K)
     return c
+
+
+def wgrad_bf16_(c, a, b):
+    """c[M,N] (f32) += a[K,M]^T . b[K,N] for bf16 a, b whose rows are the contraction index (fhvae_wgrad_bf16)."""
+    return _wgrad_("fhvae_wgrad_bf16", torch.bfloat16, c, a, b)
 
 
 def wgrad_f32_(c, a, b):
     """c[M,N] (f32) += a[K,M]^T . b[K,N] for f32 a, b whose rows are the contraction index (fhvae_wgrad_f32: exact-f32 MFMA)."""
-    lib = load_library()
-    _need_gpu(c, a, b)
-    assert a.dtype == torch.float32 and b.dtype == torch.float32 and c.dtype == torch.float32
-    assert a.stride(1) == 1 and b.stride(1) == 1 and c.stride(1) == 1 and a.shape[0] == b.shape[0]
-    K, M = a.shape
-    N = b.shape[1]
-    with _Timed("fhvae_wgrad_f32"):
-        _check(lib.fhvae_wgrad_f32(_p(a), a.stride(0), _p(b), b.stride(0), _p(c), c.stride(0), M, N, K, _stream()), "fhvae_wgrad_f32")
-    return c
+    return _wgrad_("fhvae_wgrad_f32", torch.float32, c, a, b)
 
 
 def proj_bf16(a, w, bias=None, out=None):
     """out[M,N] (f32) = a[M,K] . w[N,K]^T (+ bias) for bf16 a, w with contiguous rows (fhvae_proj_bf16: csrc/proj.hip)."""
-    lib = load_library()
     _need_gpu(a, w)
     assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a.stride(1) == 1 and w.stride(1) == 1 and a.shape[1] == w.shape[1]
     M, K = a.shape
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    with _Timed("fhvae_proj_bf16"):
-        _check(lib.fhvae_proj_bf16(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, _stream()), "fhvae_proj_bf16")
+    _call("fhvae_proj_bf16", _p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), M, N, K)
     return out
 
 
@@ -1316,7 +1193,6 @@ def adam_step_(p, g, m, v, step_dev, lr, beta1, beta2, eps, grad_scale=1.0, p_lp
     incremented -- or, with ADAM_ADVANCE, int32[ADAM_STEP_WORDS] ([0] the count, the rest the kernel's scratch words): the launch
     counts the step itself.  ADAM_ZERO_GRAD clears g behind its use.  p_lp: an optional bf16 shadow of p, written behind the update.
     The kernel indexes p, g, m, v (and p_lp) to p.numel(): operands of another length, dtype or layout are refused here."""
-    lib = load_library()
     _need_gpu(p, g, m, v, step_dev, p_lp)
     if (flags & ADAM_ADVANCE) and step_dev.numel() < ADAM_STEP_WORDS:
         raise RuntimeError("ADAM_ADVANCE needs an int32[%d] step buffer (step count + scratch words)" % ADAM_STEP_WORDS)
@@ -1332,9 +1208,8 @@ def adam_step_(p, g, m, v, step_dev, lr, beta1, beta2, eps, grad_scale=1.0, p_lp
         raise RuntimeError("adam_step_: the step count is int32 on the device (got %s)" % step_dev.dtype)
     if n == 0:  # an empty table shard (more ranks than rows)
         return
-    with _Timed("fhvae_adam_step"):
-        _check(lib.fhvae_adam_step(_p(p), _p(g), _p(m), _p(v), _p(p_lp), n, lr, beta1, beta2, eps, grad_scale, int(flags), _p(step_dev),
-                                   _stream()), "fhvae_adam_step")
+    _call("fhvae_adam_step", _p(p), _p(g), _p(m), _p(v), _p(p_lp), n, lr, beta1, beta2, eps, grad_scale, int(flags),
+          _p(step_dev))
 
 
 
@@ -1344,15 +1219,13 @@ def adam_step_(p, g, m, v, step_dev, lr, beta1, beta2, eps, grad_scale=1.0, p_lp
 def segment_gather(pool, start, T, mean=None, inv_std=None, time_major=False):
     """Cut B segments of T frames out of the HBM-resident utterance pool (frames, F) at absolute frame offsets
     `start` (B,) int64, with optional fused mean/variance normalisation.  Returns (B,T,F) (and (T,B,F) if asked)."""
-    lib = load_library()
     _need_gpu(pool, start, mean, inv_std)
     pool = _f32c(pool)
     B, F_ = start.shape[0], pool.shape[1]
     out = torch.empty(B, T, F_, device=pool.device, dtype=torch.float32)
     out_tm = torch.empty(T, B, F_, device=pool.device, dtype=torch.float32) if time_major else None
-    with _Timed("fhvae_segment_gather"):
-        _check(lib.fhvae_segment_gather(_p(pool), pool.shape[0], _p(start), _p(mean), _p(inv_std), _p(out), _p(out_tm), B, T, F_,
-                                        None, _stream()), "fhvae_segment_gather")
+    _call("fhvae_segment_gather", _p(pool), pool.shape[0], _p(start), _p(mean), _p(inv_std), _p(out), _p(out_tm), B, T, F_,
+          None)
     return (out, out_tm) if time_major else out
 
 
@@ -1365,20 +1238,31 @@ class Mu2Estimator:
         self.count = torch.zeros(self.S, device=device, dtype=torch.float32)
 
     def add(self, z2_mu, idx):
-        lib = load_library()
         _need_gpu(z2_mu, idx)
         z2_mu = _f32c(z2_mu.detach())
-        with _Timed("fhvae_mu2_accumulate"):
-            _check(lib.fhvae_mu2_accumulate(_p(z2_mu), _p(idx), _p(self.zsum), _p(self.count), z2_mu.shape[0], self.S, self.D,
-                                            _stream()), "fhvae_mu2_accumulate")
+        _call("fhvae_mu2_accumulate", _p(z2_mu), _p(idx), _p(self.zsum), _p(self.count), z2_mu.shape[0], self.S, self.D)
 
     def result(self, ratio: float):
-        lib = load_library()
         mu2 = torch.empty_like(self.zsum)
-        with _Timed("fhvae_mu2_finalize"):
-            _check(lib.fhvae_mu2_finalize(_p(self.zsum), _p(self.count), _p(mu2), self.S, self.D, float(ratio), _stream()),
-                   "fhvae_mu2_finalize")
+        _call("fhvae_mu2_finalize", _p(self.zsum), _p(self.count), _p(mu2), self.S, self.D, float(ratio))
         return mu2, self.count
+
+
+def _want(op, name, t, dtype, ndim=None, shape=None, numel=None, optional=False, contiguous=True):
+    """The argument check of the data ops below: refuses tensor `t`, argument `name` of wrapper `op`, unless it has `dtype`, is
+    contiguous, and has `ndim` dimensions / the `shape` (None entries: any size) / `numel` elements where these are given.
+    optional: None passes.  The kernels index raw pointers by these sizes: a wrong argument is no Python error further down."""
+    if t is None and optional:
+        return
+    if (t is None or t.dtype != dtype or (contiguous and not t.is_contiguous()) or (ndim is not None and t.dim() != ndim)
+            or (numel is not None and t.numel() != numel)
+            or (shape is not None and (t.dim() != len(shape) or any(e is not None and e != n for e, n in zip(shape, t.shape))))):
+        want = ", ".join(w for w in ("%d-D" % ndim if ndim is not None else "",
+                                     "shape (%s)" % ", ".join("*" if e is None else str(e) for e in shape) if shape is not None else "",
+                                     "%d elements" % numel if numel is not None else "") if w)
+        got = "None" if t is None else "%s %s%s" % (t.dtype, tuple(t.shape), "" if t.is_contiguous() else ", not contiguous")
+        raise RuntimeError("%s: %s must be a%s %s tensor%s (got %s)"
+                           % (op, name, " contiguous" if contiguous else "", dtype, " of " + want if want else "", got))
 
 
 # --- hierarchical sampling (csrc/hs.hip) ----------------------------------------------------------------------------------
@@ -1396,15 +1280,12 @@ def hs_select(seq_ptr, block_seqs, seg_ids, local_idx, n_out, status):
     """The block's segments in CSR order: seg_ids[:n], local_idx[:n] (n = *n_out, on the device; writes stop at the buffers'
     capacity).  seq_ptr (S+1,), block_seqs (K,), seg_ids / local_idx (cap,) int64; n_out (1,) int64; status (1,) int32."""
     _need_gpu(seq_ptr, block_seqs, seg_ids, local_idx, n_out, status)
-    for t in (seq_ptr, block_seqs, seg_ids, local_idx, n_out):
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise RuntimeError("hs_select takes contiguous int64 tensors")
-    if status.dtype != torch.int32 or seg_ids.shape != local_idx.shape:
-        raise RuntimeError("hs_select: status must be int32 and seg_ids / local_idx the same length")
-    lib = load_library()
-    with _Timed("fhvae_hs_select"):
-        _check(lib.fhvae_hs_select(_p(seq_ptr), seq_ptr.shape[0] - 1, _p(block_seqs), block_seqs.shape[0], _p(seg_ids),
-                                   _p(local_idx), _p(n_out), seg_ids.shape[0], _p(status), _stream()), "fhvae_hs_select")
+    for name, t in (("seq_ptr", seq_ptr), ("block_seqs", block_seqs), ("seg_ids", seg_ids), ("n_out", n_out)):
+        _want("hs_select", name, t, torch.int64)
+    _want("hs_select", "local_idx", local_idx, torch.int64, shape=tuple(seg_ids.shape))
+    _want("hs_select", "status", status, torch.int32, contiguous=False)
+    _call("fhvae_hs_select", _p(seq_ptr), seq_ptr.shape[0] - 1, _p(block_seqs), block_seqs.shape[0], _p(seg_ids),
+          _p(local_idx), _p(n_out), seg_ids.shape[0], _p(status))
 
 
 FEATS_TYPES = {"fbank": 0, "spec": 1}  # FHVAE_FEATS_FBANK / FHVAE_FEATS_SPEC
@@ -1416,27 +1297,18 @@ def feats_fwd(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, n_fft, hop, n_mel
     wave_ptr / frame_ptr (U+1,) int64, dft_basis / mel_basis in the header's padded layouts (mel_basis None for "spec"),
     out (frame_ptr[U], n_out) f32, status (1,) int32 (FEATS_BAD_PTR when the pointers break the framing rule)."""
     _need_gpu(wave, wave_ptr, frame_ptr, dft_basis, mel_basis, out, status)
-    for t in (wave, dft_basis, out) + ((mel_basis,) if mel_basis is not None else ()):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("feats_fwd takes contiguous f32 samples, bases and output")
-    for t in (wave_ptr, frame_ptr):
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise RuntimeError("feats_fwd takes contiguous int64 wave_ptr / frame_ptr")
-    if status.dtype != torch.int32 or wave_ptr.shape != frame_ptr.shape or out.dim() != 2:
-        raise RuntimeError("feats_fwd: status must be int32, wave_ptr / frame_ptr the same length and out 2-D")
     n_out = n_mels if ftype == "fbank" else n_fft // 2 + 1
     G = (n_fft // 2 + 16) // 16  # 16-bin groups
-    if tuple(dft_basis.shape) != (32 * G, (n_fft + 15) // 16 * 16):
-        raise RuntimeError("feats_fwd: dft_basis must be (%d, %d) for n_fft %d" % (32 * G, (n_fft + 15) // 16 * 16, n_fft))
-    if ftype == "fbank" and (mel_basis is None or tuple(mel_basis.shape) != ((n_mels + 15) // 16 * 16, 16 * G)):
-        raise RuntimeError("feats_fwd: mel_basis must be (%d, %d)" % ((n_mels + 15) // 16 * 16, 16 * G))
-    if out.shape[1] != n_out:
-        raise RuntimeError("feats_fwd: out has %d columns, %s needs %d" % (out.shape[1], ftype, n_out))
-    lib = load_library()
-    with _Timed("fhvae_feats_fwd"):
-        _check(lib.fhvae_feats_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
-                                   _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status),
-                                   _stream()), "fhvae_feats_fwd")
+    fbank = ftype == "fbank"
+    _want("feats_fwd", "wave", wave, torch.float32)
+    _want("feats_fwd", "dft_basis", dft_basis, torch.float32, shape=(32 * G, (n_fft + 15) // 16 * 16))
+    _want("feats_fwd", "mel_basis", mel_basis, torch.float32, shape=((n_mels + 15) // 16 * 16, 16 * G) if fbank else None, optional=not fbank)
+    _want("feats_fwd", "out", out, torch.float32, shape=(None, n_out))
+    _want("feats_fwd", "wave_ptr", wave_ptr, torch.int64)
+    _want("feats_fwd", "frame_ptr", frame_ptr, torch.int64, shape=tuple(wave_ptr.shape))
+    _want("feats_fwd", "status", status, torch.int32, contiguous=False)
+    _call("fhvae_feats_fwd", _p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, out.shape[0],
+          _p(dft_basis), _p(mel_basis), n_fft, hop, n_mels, FEATS_TYPES[ftype], _p(out), _p(status))
 
 
 KALDI_REMOVE_DC, KALDI_USE_LOG, KALDI_USE_POWER = 1, 2, 4  # FHVAE_KALDI_*
@@ -1450,31 +1322,22 @@ def kaldi_fbank_fwd(wave, wave_ptr, frame_ptr, stream_ids, dft_basis, mel_basis,
     dither is 0), dft_basis / mel_basis in the header's padded layouts, out (frame_ptr[U], n_mels) f32, status (1,) int32
     (KALDI_BAD_PTR when the pointers break the snip-edges framing rule)."""
     _need_gpu(wave, wave_ptr, frame_ptr, stream_ids, dft_basis, mel_basis, out, status)
-    for t in (wave, dft_basis, mel_basis, out):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("kaldi_fbank_fwd takes contiguous f32 samples, bases and output")
-    for t in (wave_ptr, frame_ptr) + ((stream_ids,) if stream_ids is not None else ()):
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            raise RuntimeError("kaldi_fbank_fwd takes contiguous int64 wave_ptr / frame_ptr / stream_ids")
-    if status.dtype != torch.int32 or status.numel() != 1 or wave_ptr.shape != frame_ptr.shape or out.dim() != 2:
-        raise RuntimeError("kaldi_fbank_fwd: status must be one int32 word, wave_ptr / frame_ptr the same length and out 2-D")
-    U = wave_ptr.shape[0] - 1
-    if dither != 0 and (stream_ids is None or stream_ids.shape[0] != U):
-        raise RuntimeError("kaldi_fbank_fwd: dither needs one stream id per utterance")
+    op = "kaldi_fbank_fwd"
     G = (padded_len // 2 + 15) // 16  # 16-bin groups
-    if tuple(dft_basis.shape) != (32 * G, (frame_len + 15) // 16 * 16):
-        raise RuntimeError("kaldi_fbank_fwd: dft_basis must be (%d, %d) for a frame of %d samples padded to %d"
-                           % (32 * G, (frame_len + 15) // 16 * 16, frame_len, padded_len))
-    if tuple(mel_basis.shape) != ((n_mels + 15) // 16 * 16, 16 * G):
-        raise RuntimeError("kaldi_fbank_fwd: mel_basis must be (%d, %d)" % ((n_mels + 15) // 16 * 16, 16 * G))
-    if out.shape[1] != n_mels:
-        raise RuntimeError("kaldi_fbank_fwd: out has %d columns for %d mel bins" % (out.shape[1], n_mels))
-    lib = load_library()
-    with _Timed("fhvae_kaldi_fbank_fwd"):
-        _check(lib.fhvae_kaldi_fbank_fwd(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), _p(stream_ids), U, out.shape[0],
-                                         _p(dft_basis), _p(mel_basis), frame_len, frame_shift, padded_len, n_mels, float(preemph),
-                                         float(dither), int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), _p(out), _p(status), _stream()),
-               "fhvae_kaldi_fbank_fwd")
+    _want(op, "wave", wave, torch.float32)
+    _want(op, "dft_basis", dft_basis, torch.float32, shape=(32 * G, (frame_len + 15) // 16 * 16))
+    _want(op, "mel_basis", mel_basis, torch.float32, shape=((n_mels + 15) // 16 * 16, 16 * G))
+    _want(op, "out", out, torch.float32, shape=(None, n_mels))
+    _want(op, "wave_ptr", wave_ptr, torch.int64)
+    _want(op, "frame_ptr", frame_ptr, torch.int64, shape=tuple(wave_ptr.shape))
+    _want(op, "status", status, torch.int32, numel=1, contiguous=False)
+    U = wave_ptr.shape[0] - 1
+    _want(op, "stream_ids", stream_ids, torch.int64, optional=dither == 0)  # (dither needs one stream id per utterance)
+    if dither != 0 and stream_ids.shape[0] != U:
+        raise RuntimeError("kaldi_fbank_fwd: stream_ids must hold one id per utterance (%d) when dither is on" % U)
+    _call("fhvae_kaldi_fbank_fwd", _p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), _p(stream_ids), U, out.shape[0],
+          _p(dft_basis), _p(mel_basis), frame_len, frame_shift, padded_len, n_mels, float(preemph), float(dither),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, int(flags), _p(out), _p(status))
 
 
 KALDI_CM_TOKENS = {"CM": 1, "CM2": 2, "CM3": 3}  # FHVAE_KALDI_CM*
@@ -1506,15 +1369,20 @@ def kaldi_cm_descs(tokens, rows, cols, row0, headers=None):
 
 def _kaldi_cm_args(payload, desc, mat, status, what):
     _need_gpu(payload, desc, mat, status)
-    if payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous() or payload.numel() % 4:
-        raise RuntimeError("%s takes the payloads as one contiguous uint8 buffer of a multiple of 4 bytes" % what)
-    if desc.dtype != torch.uint8 or not desc.is_contiguous() or desc.numel() == 0 or desc.numel() % KALDI_CM_DESC.itemsize:
-        raise RuntimeError("%s takes the descriptors as the bytes of a KALDI_CM_DESC array" % what)
-    if mat.dtype != torch.float32 or mat.dim() != 2 or not mat.is_contiguous():
-        raise RuntimeError("%s takes a contiguous 2-D f32 matrix" % what)
-    if status.dtype != torch.int32 or status.numel() != 1:
-        raise RuntimeError("%s: status must be one int32 word" % what)
-    return desc.numel() // KALDI_CM_DESC.itemsize
+    _want(what, "payload", payload, torch.uint8, ndim=1)
+    if payload.numel() % 4:
+        raise RuntimeError("%s: payload must be a multiple of 4 bytes (got %d)" % (what, payload.numel()))
+    _want(what, "the matrix", mat, torch.float32, ndim=2)
+    _want(what, "status", status, torch.int32, numel=1, contiguous=False)
+    return _desc_count(what, desc, KALDI_CM_DESC, "KALDI_CM_DESC")
+
+
+def _desc_count(op, desc, np_dtype, type_name):
+    """Number of descriptors in `desc`, the bytes of a numpy array of `np_dtype` as a uint8 tensor."""
+    _want(op, "desc", desc, torch.uint8)
+    if desc.numel() == 0 or desc.numel() % np_dtype.itemsize:
+        raise RuntimeError("%s: desc must be the bytes of a %s array (got %d bytes)" % (op, type_name, desc.numel()))
+    return desc.numel() // np_dtype.itemsize
 
 
 def kaldi_decompress(payload, desc, n_tiles, out, status):
@@ -1522,10 +1390,8 @@ def kaldi_decompress(payload, desc, n_tiles, out, status):
     payload (n_bytes,) uint8, desc the bytes of a KALDI_CM_DESC array (kaldi_cm_descs) as a uint8 tensor, status (1,) int32
     (KALDI_CM_BAD_DESC when a descriptor breaks the layout rules: nothing is written)."""
     U = _kaldi_cm_args(payload, desc, out, status, "kaldi_decompress")
-    lib = load_library()
-    with _Timed("fhvae_kaldi_decompress"):
-        _check(lib.fhvae_kaldi_decompress(_p(payload), payload.numel(), _p(desc), U, int(n_tiles), _p(out), out.shape[0], out.shape[1],
-                                          _p(status), _stream()), "fhvae_kaldi_decompress")
+    _call("fhvae_kaldi_decompress", _p(payload), payload.numel(), _p(desc), U, int(n_tiles), _p(out), out.shape[0],
+          out.shape[1], _p(status))
 
 
 def kaldi_compress(feats, desc, n_tiles, payload, status):
@@ -1533,11 +1399,9 @@ def kaldi_compress(feats, desc, n_tiles, payload, status):
     as `desc` names them (kaldi_cm_descs); the global headers (min_value, range) are written into `desc`.  status (1,) int32:
     KALDI_CM_BAD_DESC, KALDI_CM_NONFINITE (a NaN or Inf among the values)."""
     U = _kaldi_cm_args(payload, desc, feats, status, "kaldi_compress")
-    lib = load_library()
     ws = torch.empty(2 * U, dtype=torch.int32, device=feats.device)
-    with _Timed("fhvae_kaldi_compress"):
-        _check(lib.fhvae_kaldi_compress(_p(feats), feats.shape[0], feats.shape[1], _p(desc), U, int(n_tiles), _p(ws), _p(payload),
-                                        payload.numel(), _p(status), _stream()), "fhvae_kaldi_compress")
+    _call("fhvae_kaldi_compress", _p(feats), feats.shape[0], feats.shape[1], _p(desc), U, int(n_tiles), _p(ws), _p(payload),
+          payload.numel(), _p(status))
 
 
 FLAC_CAND = 0x80000000  # FHVAE_FLAC_CAND
@@ -1552,11 +1416,10 @@ FLAC_DESC = np.dtype([("byte_begin", "<i8"), ("byte_end", "<i8"), ("out_off", "<
 
 def _flac_args(buf, desc, what):
     _need_gpu(buf, desc)
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() == 0:
-        raise RuntimeError("%s takes the frame bytes as one contiguous uint8 buffer" % what)
-    if desc.dtype != torch.uint8 or not desc.is_contiguous() or desc.numel() == 0 or desc.numel() % FLAC_DESC.itemsize:
-        raise RuntimeError("%s takes the descriptors as the bytes of a FLAC_DESC array" % what)
-    return desc.numel() // FLAC_DESC.itemsize
+    _want(what, "buf", buf, torch.uint8, ndim=1)
+    if buf.numel() == 0:
+        raise RuntimeError("%s: buf is empty" % what)
+    return _desc_count(what, desc, FLAC_DESC, "FLAC_DESC")
 
 
 def flac_scan(buf, desc, info):
@@ -1564,11 +1427,8 @@ def flac_scan(buf, desc, info):
     uint8 tensor, info (n_bytes,) int32 out: per byte position 0, or FLAC_CAND | block size << 8 | header bytes."""
     U = _flac_args(buf, desc, "flac_scan")
     _need_gpu(info)
-    if info.dtype != torch.int32 or info.numel() != buf.numel() or not info.is_contiguous():
-        raise RuntimeError("flac_scan: info must be one int32 per byte of buf")
-    lib = load_library()
-    with _Timed("fhvae_flac_scan"):
-        _check(lib.fhvae_flac_scan(_p(buf), buf.numel(), _p(desc), U, _p(info), _stream()), "fhvae_flac_scan")
+    _want("flac_scan", "info", info, torch.int32, numel=buf.numel())  # (one word per byte of buf)
+    _call("fhvae_flac_scan", _p(buf), buf.numel(), _p(desc), U, _p(info))
 
 
 def flac_decode(buf, desc, cand_pos, cand_status, cand_end, cand_spos, out=None):
@@ -1578,15 +1438,12 @@ def flac_decode(buf, desc, cand_pos, cand_status, cand_end, cand_spos, out=None)
     U = _flac_args(buf, desc, "flac_decode")
     _need_gpu(cand_pos, cand_status, cand_end, cand_spos, out)
     n = cand_pos.numel()
-    for t, dt in ((cand_pos, torch.int64), (cand_status, torch.int32), (cand_end, torch.int64), (cand_spos, torch.int64)):
-        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise RuntimeError("flac_decode: the per-candidate arrays are contiguous (n,) int64 / int32 / int64 / int64")
-    if out is not None and (out.dtype != torch.int32 or out.dim() != 1 or not out.is_contiguous()):
-        raise RuntimeError("flac_decode: out is a contiguous 1-D int32 tensor")
-    lib = load_library()
-    with _Timed("fhvae_flac_decode"):
-        _check(lib.fhvae_flac_decode(_p(buf), buf.numel(), _p(desc), U, _p(cand_pos), n, _p(cand_status), _p(cand_end), _p(cand_spos),
-                                     _p(out), 0 if out is None else out.numel(), _stream()), "fhvae_flac_decode")
+    for name, t, dt in (("cand_pos", cand_pos, torch.int64), ("cand_status", cand_status, torch.int32), ("cand_end", cand_end, torch.int64),
+                        ("cand_spos", cand_spos, torch.int64)):
+        _want("flac_decode", name, t, dt, numel=n)
+    _want("flac_decode", "out", out, torch.int32, ndim=1, optional=True)
+    _call("fhvae_flac_decode", _p(buf), buf.numel(), _p(desc), U, _p(cand_pos), n, _p(cand_status), _p(cand_end),
+          _p(cand_spos), _p(out), 0 if out is None else out.numel())
 
 
 RESAMPLE_BAD_PTR = 1  # FHVAE_RESAMPLE_BAD_PTR
@@ -1598,41 +1455,36 @@ def resample_fwd(wave_in, in_ptr, out_ptr, row_ptr, n_rows, bank, chunks, L, M, 
     builds them, exc (n_exc,) uint8 with alt (alt_taps,) f32 or both None, wave_out (out_ptr[U],) f32, status (1,) int32
     (RESAMPLE_BAD_PTR when the pointers break the length rule)."""
     _need_gpu(wave_in, in_ptr, out_ptr, row_ptr, bank, chunks, exc, alt, wave_out, status)
-    for t in (wave_in, bank, wave_out) + ((alt,) if alt is not None else ()):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("resample_fwd takes contiguous f32 samples, bank and output")
-    for t in (in_ptr, out_ptr, row_ptr):
-        if t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.shape != in_ptr.shape or t.shape[0] < 2:
-            raise RuntimeError("resample_fwd takes contiguous int64 in_ptr / out_ptr / row_ptr of one length (U + 1)")
-    if status.dtype != torch.int32 or status.numel() != 1 or wave_in.dim() != 1 or wave_out.dim() != 1:
-        raise RuntimeError("resample_fwd: status must be one int32 word, wave_in and wave_out 1-D")
+    op = "resample_fwd"
     NCP = (P * L + 15) // 16 * 16
-    if bank.dim() != 2 or bank.shape[0] != NCP or bank.shape[1] % 16 != 0:
-        raise RuntimeError("resample_fwd: bank must be (%d, KP) with KP a multiple of 16" % NCP)
-    if chunks.dtype != torch.int32 or not chunks.is_contiguous() or tuple(chunks.shape) != (NCP // 16, 2):
-        raise RuntimeError("resample_fwd: chunks must be contiguous int32 (%d, 2)" % (NCP // 16))
-    if (exc is None) != (alt is None) or (exc is not None and (exc.dtype != torch.uint8 or not exc.is_contiguous() or exc.dim() != 1)):
-        raise RuntimeError("resample_fwd: exc (uint8, 1-D) and alt come together")
-    lib = load_library()
-    with _Timed("fhvae_resample_fwd"):
-        _check(lib.fhvae_resample_fwd(_p(wave_in), wave_in.numel(), _p(in_ptr), _p(out_ptr), _p(row_ptr), in_ptr.shape[0] - 1,
-                                      n_rows, _p(bank), _p(chunks), L, M, P, bank.shape[1], WL, float(ratio), _p(exc),
-                                      0 if exc is None else exc.numel(), _p(alt), 0 if alt is None else alt.numel(), alt_wl,
-                                      _p(wave_out), wave_out.numel(), _p(status), _stream()), "fhvae_resample_fwd")
+    _want(op, "wave_in", wave_in, torch.float32, ndim=1)
+    _want(op, "wave_out", wave_out, torch.float32, ndim=1)
+    _want(op, "bank", bank, torch.float32, shape=(NCP, None))
+    if bank.shape[1] % 16 != 0:
+        raise RuntimeError("resample_fwd: bank must be (%d, KP) with KP a multiple of 16 (got KP = %d)" % (NCP, bank.shape[1]))
+    _want(op, "chunks", chunks, torch.int32, shape=(NCP // 16, 2))
+    _ptr_args(op, status, in_ptr=in_ptr, out_ptr=out_ptr, row_ptr=row_ptr)
+    if (exc is None) != (alt is None):
+        raise RuntimeError("resample_fwd: exc and alt come together")
+    _want(op, "exc", exc, torch.uint8, ndim=1, optional=True)
+    _want(op, "alt", alt, torch.float32, optional=True)
+    _call("fhvae_resample_fwd", _p(wave_in), wave_in.numel(), _p(in_ptr), _p(out_ptr), _p(row_ptr), in_ptr.shape[0] - 1,
+          n_rows, _p(bank), _p(chunks), L, M, P, bank.shape[1], WL, float(ratio), _p(exc), 0 if exc is None else exc.numel(),
+          _p(alt), 0 if alt is None else alt.numel(), alt_wl, _p(wave_out), wave_out.numel(), _p(status))
 
 
 SYNTH_BAD_PTR = 1  # FHVAE_SYNTH_BAD_PTR
 
 
-def _synth_args(name, f32, ptrs, status):
-    for t in f32:
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise RuntimeError("%s takes contiguous f32 tensors" % name)
-    for t in ptrs:
-        if t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1 or t.shape != ptrs[0].shape or t.shape[0] < 2:
-            raise RuntimeError("%s takes contiguous int64 wave_ptr / frame_ptr of one length (U + 1)" % name)
-    if status.dtype != torch.int32 or status.numel() != 1:
-        raise RuntimeError("%s: status must be one int32 word" % name)
+def _ptr_args(op, status, **ptrs):
+    """The (U + 1,) int64 offset arrays of a batch of utterances (all of one length, U >= 1) and its one-word int32 status."""
+    first = next(iter(ptrs.values()))
+    for name, t in ptrs.items():
+        _want(op, name, t, torch.int64, ndim=1)
+        if t.shape != first.shape or t.shape[0] < 2:
+            raise RuntimeError("%s: %s must be one length (U + 1 >= 2) with the other offset arrays (got %d, %d)"
+                               % (op, " / ".join(ptrs), first.shape[0], t.shape[0]))
+    _want(op, "status", status, torch.int32, numel=1, contiguous=False)
 
 
 def synth_istft(spec, wave_ptr, frame_ptr, synth_basis, win_sq, n_fft, hop, frames_ws, wave_out, status):
@@ -1640,19 +1492,16 @@ def synth_istft(spec, wave_ptr, frame_ptr, synth_basis, win_sq, n_fft, hop, fram
     (U+1,) int64, synth_basis / win_sq as features.synth_basis / features.window_sq, frames_ws (n_frames, KP) f32 workspace,
     wave_out (wave_ptr[U],) f32, status (1,) int32 (SYNTH_BAD_PTR when the pointers break hop * (frames - 1))."""
     _need_gpu(spec, wave_ptr, frame_ptr, synth_basis, win_sq, frames_ws, wave_out, status)
-    _synth_args("synth_istft", (spec, synth_basis, win_sq, frames_ws, wave_out), (wave_ptr, frame_ptr), status)
+    op = "synth_istft"
     n_bins, KP = n_fft // 2 + 1, (n_fft + 15) // 16 * 16
-    if spec.dim() != 3 or tuple(spec.shape[1:]) != (n_bins, 2):
-        raise RuntimeError("synth_istft: spec must be (n_frames, %d, 2) for n_fft %d" % (n_bins, n_fft))
-    if tuple(synth_basis.shape) != (KP, (2 * n_bins + 15) // 16 * 16) or tuple(win_sq.shape) != (n_fft,):
-        raise RuntimeError("synth_istft: synth_basis must be (%d, %d) and win_sq (%d,)" % (KP, (2 * n_bins + 15) // 16 * 16, n_fft))
-    if tuple(frames_ws.shape) != (spec.shape[0], KP) or wave_out.dim() != 1:
-        raise RuntimeError("synth_istft: frames_ws must be (%d, %d) and wave_out 1-D" % (spec.shape[0], KP))
-    lib = load_library()
-    with _Timed("fhvae_synth_istft"):
-        _check(lib.fhvae_synth_istft(_p(spec), spec.shape[0], _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, wave_out.numel(),
-                                     _p(synth_basis), _p(win_sq), n_fft, hop, _p(frames_ws), _p(wave_out), _p(status), _stream()),
-               "fhvae_synth_istft")
+    _want(op, "spec", spec, torch.float32, shape=(None, n_bins, 2))
+    _want(op, "synth_basis", synth_basis, torch.float32, shape=(KP, (2 * n_bins + 15) // 16 * 16))
+    _want(op, "win_sq", win_sq, torch.float32, shape=(n_fft,))
+    _want(op, "frames_ws", frames_ws, torch.float32, shape=(spec.shape[0], KP))
+    _want(op, "wave_out", wave_out, torch.float32, ndim=1)
+    _ptr_args(op, status, wave_ptr=wave_ptr, frame_ptr=frame_ptr)
+    _call("fhvae_synth_istft", _p(spec), spec.shape[0], _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, wave_out.numel(),
+          _p(synth_basis), _p(win_sq), n_fft, hop, _p(frames_ws), _p(wave_out), _p(status))
 
 
 def synth_project(wave, wave_ptr, frame_ptr, dft_basis, mag, tprev, coef, n_fft, hop, rebuilt, nxt, status):
@@ -1660,33 +1509,26 @@ def synth_project(wave, wave_ptr, frame_ptr, dft_basis, mag, tprev, coef, n_fft,
     nxt = mag * a / (|a| + 1e-16).  mag (n_frames, n_bins) f32; tprev / rebuilt / nxt (n_frames, n_bins, 2) f32 (tprev None =
     zero, rebuilt None = not stored)."""
     _need_gpu(wave, wave_ptr, frame_ptr, dft_basis, mag, tprev, rebuilt, nxt, status)
-    _synth_args("synth_project", (wave, dft_basis, mag, tprev, rebuilt, nxt), (wave_ptr, frame_ptr), status)
+    op = "synth_project"
     n_bins = n_fft // 2 + 1
     G = (n_bins + 15) // 16
-    if tuple(dft_basis.shape) != (32 * G, (n_fft + 15) // 16 * 16):
-        raise RuntimeError("synth_project: dft_basis must be (%d, %d) for n_fft %d" % (32 * G, (n_fft + 15) // 16 * 16, n_fft))
-    if mag.dim() != 2 or mag.shape[1] != n_bins or wave.dim() != 1:
-        raise RuntimeError("synth_project: mag must be (n_frames, %d) and wave 1-D" % n_bins)
-    for t in (tprev, rebuilt, nxt):
-        if t is not None and tuple(t.shape) != (mag.shape[0], n_bins, 2):
-            raise RuntimeError("synth_project: complex arrays must be (%d, %d, 2)" % (mag.shape[0], n_bins))
-    lib = load_library()
-    with _Timed("fhvae_synth_project"):
-        _check(lib.fhvae_synth_project(_p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, mag.shape[0],
-                                       _p(dft_basis), _p(mag), _p(tprev), float(coef), n_fft, hop, _p(rebuilt), _p(nxt), _p(status),
-                                       _stream()), "fhvae_synth_project")
+    _want(op, "wave", wave, torch.float32, ndim=1)
+    _want(op, "dft_basis", dft_basis, torch.float32, shape=(32 * G, (n_fft + 15) // 16 * 16))
+    _want(op, "mag", mag, torch.float32, shape=(None, n_bins))
+    for name, t in (("tprev", tprev), ("rebuilt", rebuilt), ("nxt", nxt)):
+        _want(op, name, t, torch.float32, shape=(mag.shape[0], n_bins, 2), optional=True)
+    _ptr_args(op, status, wave_ptr=wave_ptr, frame_ptr=frame_ptr)
+    _call("fhvae_synth_project", _p(wave), wave.numel(), _p(wave_ptr), _p(frame_ptr), wave_ptr.shape[0] - 1, mag.shape[0],
+          _p(dft_basis), _p(mag), _p(tprev), float(coef), n_fft, hop, _p(rebuilt), _p(nxt), _p(status))
 
 
 def synth_deemph(wave, wave_ptr, coef, out, status):
     """out[t] = wave[t] + coef * out[t-1] within every utterance (fhvae_synth_deemph); coef 0 copies."""
     _need_gpu(wave, wave_ptr, out, status)
-    _synth_args("synth_deemph", (wave, out), (wave_ptr,), status)
-    if wave.dim() != 1 or out.shape != wave.shape:
-        raise RuntimeError("synth_deemph: wave and out must be 1-D of one length")
-    lib = load_library()
-    with _Timed("fhvae_synth_deemph"):
-        _check(lib.fhvae_synth_deemph(_p(wave), _p(wave_ptr), wave_ptr.shape[0] - 1, wave.numel(), float(coef), _p(out), _p(status),
-                                      _stream()), "fhvae_synth_deemph")
+    _want("synth_deemph", "wave", wave, torch.float32, ndim=1)
+    _want("synth_deemph", "out", out, torch.float32, shape=tuple(wave.shape))
+    _ptr_args("synth_deemph", status, wave_ptr=wave_ptr)
+    _call("fhvae_synth_deemph", _p(wave), _p(wave_ptr), wave_ptr.shape[0] - 1, wave.numel(), float(coef), _p(out), _p(status))
 
 
 MELINV_BAD_BAND = 1  # FHVAE_MELINV_BAD_BAND
@@ -1700,29 +1542,22 @@ def mel_invert(mel, bin_filt, bin_w, filt_first, filt_off, filt_w, inv_l, beta, 
     f32 momentum factors, out (n_frames, n_bins) f32 magnitudes (`out_log`: max(log, -50)), status (1,) int32
     (MELINV_BAD_BAND when the band points outside its arrays)."""
     _need_gpu(mel, bin_filt, bin_w, filt_first, filt_off, filt_w, beta, out, status)
-    for t in (mel, bin_w, filt_w, beta, out):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("mel_invert takes contiguous f32 mel, bin_w, filt_w, beta and out")
-    for t in (bin_filt, filt_first, filt_off):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
-            raise RuntimeError("mel_invert takes contiguous 1-D int32 bin_filt / filt_first / filt_off")
-    if status.dtype != torch.int32 or status.numel() != 1:
-        raise RuntimeError("mel_invert: status must be one int32 word")
-    if mel.dim() != 2 or out.dim() != 2 or out.shape[0] != mel.shape[0]:
-        raise RuntimeError("mel_invert: mel must be (n_frames, n_mels) and out (n_frames, n_bins)")
+    op = "mel_invert"
+    _want(op, "mel", mel, torch.float32, ndim=2)
+    _want(op, "out", out, torch.float32, shape=(mel.shape[0], None))
     n_mels, n_bins = mel.shape[1], out.shape[1]
-    if bin_filt.shape[0] != n_bins or tuple(bin_w.shape) != (n_bins, 2):
-        raise RuntimeError("mel_invert: bin_filt must be (%d,) and bin_w (%d, 2)" % (n_bins, n_bins))
-    if filt_first.shape[0] != n_mels or filt_off.shape[0] != n_mels + 1 or filt_w.dim() != 1:
-        raise RuntimeError("mel_invert: filt_first must be (%d,), filt_off (%d,) and filt_w 1-D" % (n_mels, n_mels + 1))
-    if beta.dim() != 1 or beta.shape[0] < 1:
+    _want(op, "bin_filt", bin_filt, torch.int32, shape=(n_bins,))
+    _want(op, "bin_w", bin_w, torch.float32, shape=(n_bins, 2))
+    _want(op, "filt_first", filt_first, torch.int32, shape=(n_mels,))
+    _want(op, "filt_off", filt_off, torch.int32, shape=(n_mels + 1,))
+    _want(op, "filt_w", filt_w, torch.float32, ndim=1)
+    _want(op, "beta", beta, torch.float32, ndim=1)
+    if beta.shape[0] < 1:
         raise RuntimeError("mel_invert: beta must hold one factor per iteration")
-    lib = load_library()
+    _want(op, "status", status, torch.int32, numel=1, contiguous=False)
     flags = (MELINV_IN_LOG if in_log else 0) | (MELINV_OUT_LOG if out_log else 0)
-    with _Timed("fhvae_mel_invert"):
-        _check(lib.fhvae_mel_invert(_p(mel), mel.shape[0], n_mels, n_bins, _p(bin_filt), _p(bin_w), _p(filt_first), _p(filt_off),
-                                    _p(filt_w), filt_w.numel(), float(inv_l), _p(beta), beta.shape[0], flags, _p(out), _p(status),
-                                    _stream()), "fhvae_mel_invert")
+    _call("fhvae_mel_invert", _p(mel), mel.shape[0], n_mels, n_bins, _p(bin_filt), _p(bin_w), _p(filt_first), _p(filt_off),
+          _p(filt_w), filt_w.numel(), float(inv_l), _p(beta), beta.shape[0], flags, _p(out), _p(status))
 
 
 def sv_hist(emb, label, n_bins=4096):
@@ -1731,10 +1566,8 @@ def sv_hist(emb, label, n_bins=4096):
     in bin clamp(floor((cos + 1) n_bins / 2), 0, n_bins - 1).  D is padded to the next multiple of 16 with zero columns (no
     cosine changes); rows with a leading dimension the kernel takes are read in place."""
     _need_gpu(emb, label)
-    if emb.dtype != torch.float32 or emb.dim() != 2:
-        raise RuntimeError("sv_hist takes (S, D) float32 embeddings")
-    if label.dtype != torch.int32 or label.dim() != 1 or label.shape[0] != emb.shape[0]:
-        raise RuntimeError("sv_hist takes one int32 label per row of emb")
+    _want("sv_hist", "emb", emb, torch.float32, ndim=2, contiguous=False)
+    _want("sv_hist", "label", label, torch.int32, shape=(emb.shape[0],), contiguous=False)  # (one per row of emb)
     S, D = emb.shape
     if S < 1 or D < 1 or D > 128:
         raise RuntimeError("sv_hist: S = %d rows of D = %d columns (S >= 1, 1 <= D <= 128)" % (S, D))
@@ -1751,16 +1584,14 @@ def sv_hist(emb, label, n_bins=4096):
     nws = int(lib.fhvae_sv_hist_ws_bytes(S))
     ws = torch.empty(nws, device=emb.device, dtype=torch.uint8)
     hist = torch.empty(2, n_bins, device=emb.device, dtype=torch.int64)  # (uint64 counts; they stay far below 2^63)
-    with _Timed("fhvae_sv_hist"):
-        _check(lib.fhvae_sv_hist(_p(emb), emb.stride(0), _p(label), S, Dp, n_bins, _p(ws), nws, _p(hist), _stream()), "fhvae_sv_hist")
+    _call("fhvae_sv_hist", _p(emb), emb.stride(0), _p(label), S, Dp, n_bins, _p(ws), nws, _p(hist))
     return hist
 
 
 def _tsne_rows(x, what):
     """(N, D) f32 rows as the t-SNE kernels take them (D padded to a multiple of 16 with zero columns: no distance changes)."""
     _need_gpu(x)
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise RuntimeError("%s takes (N, D) float32 rows" % what)
+    _want(what, "x", x, torch.float32, ndim=2, contiguous=False)
     N, D = x.shape
     if N < 8 or D < 1 or D > 128:
         raise RuntimeError("%s: N = %d rows of D = %d columns (N >= 8, 1 <= D <= 128)" % (what, N, D))
@@ -1779,13 +1610,6 @@ def tsne_workspace(x):
     return torch.empty(int(load_library().fhvae_tsne_ws_bytes(N, Dp)), device=x.device, dtype=torch.uint8)
 
 
-def _tsne_vec(t, N, cols, what):
-    _need_gpu(t)
-    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != ((N,) if cols == 1 else (N, cols)):
-        raise RuntimeError("%s must be a contiguous float32 tensor of shape %s" % (what, (N,) if cols == 1 else (N, cols)))
-    return t
-
-
 def tsne_affinity(x, perplexity, ws=None):
     """The perplexity search of exact t-SNE (fhvae_tsne_affinity): x (N, D) f32, centred by the caller -> (beta, m, Z), each (N,)
     f32: p_j|i = exp(-beta_i (d2(i, j) - m_i)) / Z_i has the perplexity asked for.  No (N, N) array is made."""
@@ -1796,9 +1620,7 @@ def tsne_affinity(x, perplexity, ws=None):
     if ws is None:
         ws = tsne_workspace(x)
     beta, m, z = (torch.empty(N, device=x.device, dtype=torch.float32) for _ in range(3))
-    with _Timed("fhvae_tsne_affinity"):
-        _check(load_library().fhvae_tsne_affinity(_p(x), x.stride(0), N, Dp, perplexity, _p(beta), _p(m), _p(z), _p(ws), ws.numel(),
-                                                  _stream()), "fhvae_tsne_affinity")
+    _call("fhvae_tsne_affinity", _p(x), x.stride(0), N, Dp, perplexity, _p(beta), _p(m), _p(z), _p(ws), ws.numel())
     return beta, m, z
 
 
@@ -1807,33 +1629,34 @@ def tsne_step(x, beta, m, z, y, v, g, exaggeration, momentum, lr, kl=None, ws=No
     tensor that receives the KL divergence at the y the call was given, or None.  Nothing is read back; x as tsne_affinity
     took it (a caller that loops passes rows the kernel reads in place, and one ws)."""
     x, N, Dp = _tsne_rows(x, "tsne_step")
+    _need_gpu(beta, m, z, y, v, g)
     for name, t in (("beta", beta), ("m", m), ("z", z)):
-        _tsne_vec(t, N, 1, "tsne_step: " + name)
+        _want("tsne_step", name, t, torch.float32, shape=(N,))
     for name, t in (("y", y), ("v", v), ("g", g)):
-        _tsne_vec(t, N, 2, "tsne_step: " + name)
-    if kl is not None and (kl.dtype != torch.float32 or kl.numel() != 1 or not kl.is_cuda):
-        raise RuntimeError("tsne_step: kl must be a one-element float32 tensor on the device")
+        _want("tsne_step", name, t, torch.float32, shape=(N, 2))
+    _want("tsne_step", "kl", kl, torch.float32, numel=1, optional=True, contiguous=False)
+    if kl is not None and not kl.is_cuda:
+        raise RuntimeError("tsne_step: kl must be on the device")
     if ws is None:
         ws = tsne_workspace(x)
-    with _Timed("fhvae_tsne_step"):
-        _check(load_library().fhvae_tsne_step(_p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), _p(v), _p(g), float(exaggeration),
-                                              float(momentum), float(lr), _p(kl), _p(ws), ws.numel(), _stream()), "fhvae_tsne_step")
+    _call("fhvae_tsne_step", _p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), _p(v), _p(g), float(exaggeration),
+          float(momentum), float(lr), _p(kl), _p(ws), ws.numel())
 
 
 def tsne_grad(x, beta, m, z, y, exaggeration=1.0, ws=None):
     """The gradient pass of tsne_step without the update (fhvae_tsne_grad) -> (out (N, 7) f32: F (2, with the exaggeration),
     R (2), W, grad (2) per row; scal (2,) f32: Zq, KL)."""
     x, N, Dp = _tsne_rows(x, "tsne_grad")
+    _need_gpu(beta, m, z, y)
     for name, t in (("beta", beta), ("m", m), ("z", z)):
-        _tsne_vec(t, N, 1, "tsne_grad: " + name)
-    _tsne_vec(y, N, 2, "tsne_grad: y")
+        _want("tsne_grad", name, t, torch.float32, shape=(N,))
+    _want("tsne_grad", "y", y, torch.float32, shape=(N, 2))
     if ws is None:
         ws = tsne_workspace(x)
     out = torch.empty(N, 7, device=x.device, dtype=torch.float32)
     scal = torch.empty(2, device=x.device, dtype=torch.float32)
-    with _Timed("fhvae_tsne_grad"):
-        _check(load_library().fhvae_tsne_grad(_p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), float(exaggeration), _p(out),
-                                              _p(scal), _p(ws), ws.numel(), _stream()), "fhvae_tsne_grad")
+    _call("fhvae_tsne_grad", _p(x), x.stride(0), N, Dp, _p(beta), _p(m), _p(z), _p(y), float(exaggeration), _p(out), _p(scal),
+          _p(ws), ws.numel())
     return out, scal
 
 
@@ -1842,44 +1665,34 @@ def mu2_accumulate_sorted(z2_mu, local_idx, zsum, count, status):
     reproducible for a fixed chunking).  Errors in the data set bits of `status`."""
     _need_gpu(z2_mu, local_idx, zsum, count, status)
     z2_mu = _f32c(z2_mu.detach())
-    if local_idx.dtype != torch.int64 or not local_idx.is_contiguous() or status.dtype != torch.int32:
-        raise RuntimeError("mu2_accumulate_sorted takes contiguous int64 indices and an int32 status word")
     N, D = z2_mu.shape
+    _want("mu2_accumulate_sorted", "local_idx", local_idx, torch.int64)
+    _want("mu2_accumulate_sorted", "status", status, torch.int32, contiguous=False)
     if local_idx.shape[0] != N or zsum.shape[1] != D or count.shape[0] != zsum.shape[0]:
-        raise RuntimeError("mu2_accumulate_sorted: shapes do not agree")
+        raise RuntimeError("mu2_accumulate_sorted: z2_mu %s, local_idx %s, zsum %s and count %s do not agree"
+                           % tuple(tuple(t.shape) for t in (z2_mu, local_idx, zsum, count)))
     if N == 0:
         return
-    lib = load_library()
-    with _Timed("fhvae_mu2_accumulate_sorted"):
-        _check(lib.fhvae_mu2_accumulate_sorted(_p(z2_mu), _p(local_idx), _p(zsum), _p(count), N, zsum.shape[0], D, _p(status),
-                                               _stream()), "fhvae_mu2_accumulate_sorted")
+    _call("fhvae_mu2_accumulate_sorted", _p(z2_mu), _p(local_idx), _p(zsum), _p(count), N, zsum.shape[0], D, _p(status))
 
 
 def mu2_load_table(zsum, count, table, m_rows, v_rows, ratio):
     """table = zsum / (count + ratio) (0 where count is 0), m_rows = v_rows = 0, zsum = count = 0: one launch, in place."""
     _need_gpu(zsum, count, table, m_rows, v_rows)
     K, D = table.shape
-    for t in (zsum, table, m_rows, v_rows):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != K * D:
-            raise RuntimeError("mu2_load_table: every row buffer must be contiguous f32 of %d x %d" % (K, D))
-    if count.shape != (K,) or count.dtype != torch.float32:
-        raise RuntimeError("mu2_load_table: count must be (%d,) f32" % K)
-    lib = load_library()
-    with _Timed("fhvae_mu2_load_table"):
-        _check(lib.fhvae_mu2_load_table(_p(zsum), _p(count), _p(table), _p(m_rows), _p(v_rows), K, D, float(ratio), _stream()),
-               "fhvae_mu2_load_table")
+    for name, t in (("zsum", zsum), ("table", table), ("m_rows", m_rows), ("v_rows", v_rows)):
+        _want("mu2_load_table", name, t, torch.float32, numel=K * D)
+    _want("mu2_load_table", "count", count, torch.float32, shape=(K,), contiguous=False)
+    _call("fhvae_mu2_load_table", _p(zsum), _p(count), _p(table), _p(m_rows), _p(v_rows), K, D, float(ratio))
 
 
 def hs_pack_partials(zsum, count, out):
     """out (K, D+1) = [zsum | count], then zsum = count = 0: one launch (the buffer one all-gather moves across ranks)."""
     _need_gpu(zsum, count, out)
     K, D = zsum.shape
-    for t, shape in ((zsum, (K, D)), (count, (K,)), (out, (K, D + 1))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise RuntimeError("hs_pack_partials: zsum (K, D), count (K,) and out (K, D+1) must be contiguous f32")
-    lib = load_library()
-    with _Timed("fhvae_hs_pack_partials"):
-        _check(lib.fhvae_hs_pack_partials(_p(zsum), _p(count), _p(out), K, D, _stream()), "fhvae_hs_pack_partials")
+    for name, t, shape in (("zsum", zsum, (K, D)), ("count", count, (K,)), ("out", out, (K, D + 1))):
+        _want("hs_pack_partials", name, t, torch.float32, shape=shape)
+    _call("fhvae_hs_pack_partials", _p(zsum), _p(count), _p(out), K, D)
 
 
 def mu2_merge_load_shard(parts, row0, row1, shard, m_rows, v_rows, ratio):
@@ -1888,29 +1701,24 @@ def mu2_merge_load_shard(parts, row0, row1, shard, m_rows, v_rows, ratio):
     _need_gpu(parts)
     W, K, D1 = parts.shape
     D, n = D1 - 1, row1 - row0
-    if parts.dtype != torch.float32 or not parts.is_contiguous() or not 0 <= row0 <= row1 <= K:
-        raise RuntimeError("mu2_merge_load_shard: parts must be contiguous f32 (W, K, D+1) and 0 <= row0 <= row1 <= K")
-    for t in (shard, m_rows, v_rows):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n * D:
-            raise RuntimeError("mu2_merge_load_shard: shard / m_rows / v_rows must be contiguous f32 of %d x %d" % (n, D))
+    _want("mu2_merge_load_shard", "parts", parts, torch.float32)
+    if not 0 <= row0 <= row1 <= K:
+        raise RuntimeError("mu2_merge_load_shard: rows [%d, %d) lie outside parts' %d rows" % (row0, row1, K))
+    for name, t in (("shard", shard), ("m_rows", m_rows), ("v_rows", v_rows)):
+        _want("mu2_merge_load_shard", name, t, torch.float32, numel=n * D)
     if n == 0:
         return
     _need_gpu(shard, m_rows, v_rows)
-    lib = load_library()
-    with _Timed("fhvae_mu2_merge_load_shard"):
-        _check(lib.fhvae_mu2_merge_load_shard(_p(parts), W, K, row0, row1, _p(shard), _p(m_rows), _p(v_rows), D, float(ratio),
-                                              _stream()), "fhvae_mu2_merge_load_shard")
+    _call("fhvae_mu2_merge_load_shard", _p(parts), W, K, row0, row1, _p(shard), _p(m_rows), _p(v_rows), D, float(ratio))
 
 
-class SortedMu2Estimator:
+class SortedMu2Estimator(Mu2Estimator):
     """Closed-form mu2 estimate (utils.py:45-60) over batches whose indices are non-decreasing ACROSS the whole run of add()
     calls (a segment pool walked in CSR order): fhvae_mu2_accumulate_sorted, bitwise reproducible for a fixed chunking.
     Data errors land in `status` (one int32 device word); `check()` reads it (one host sync)."""
 
     def __init__(self, num_seqs: int, dim: int, device, status=None):
-        self.S, self.D = int(num_seqs), int(dim)
-        self.zsum = torch.zeros(self.S, self.D, device=device, dtype=torch.float32)
-        self.count = torch.zeros(self.S, device=device, dtype=torch.float32)
+        super().__init__(num_seqs, dim, device)
         self.status = status if status is not None else torch.zeros(1, device=device, dtype=torch.int32)
 
     def add(self, z2_mu, idx):
@@ -1920,14 +1728,6 @@ class SortedMu2Estimator:
         st = int(self.status.item())
         if st != 0:
             raise RuntimeError("sorted mu2 estimate: %s (status %d)" % (hs_status_message(st), st))
-
-    def result(self, ratio: float):
-        lib = load_library()
-        mu2 = torch.empty_like(self.zsum)
-        with _Timed("fhvae_mu2_finalize"):
-            _check(lib.fhvae_mu2_finalize(_p(self.zsum), _p(self.count), _p(mu2), self.S, self.D, float(ratio), _stream()),
-                   "fhvae_mu2_finalize")
-        return mu2, self.count
 
     def load_into(self, table, m_rows, v_rows, ratio: float):
         """Write the estimate into `table` in place, zero the moment rows, clear the accumulators (fhvae_mu2_load_table)."""

@@ -99,7 +99,6 @@ class FusedAdam(torch.optim.Optimizer):
     def zero_grad(self, set_to_none: bool = False):
         # keep the arena views attached (set_to_none would detach them); one memset for everything
         hb.flush_param_grads()  # (a backward that was never followed by step(): its queued kernels must not land after the memset)
-        hb.join_side_stream()
         if self._zeroed_by_step:
             self._zeroed_by_step = False  # (a backward follows: the arena will not be zero the next time)
         else:
@@ -110,13 +109,11 @@ class FusedAdam(torch.optim.Optimizer):
 
     def flat_grad(self) -> torch.Tensor:
         hb.flush_param_grads()  # the nets' deferred weight-gradient contractions: one grouped launch
-        hb.join_side_stream()  # weight-gradient GEMMs may still be running on the side stream
         return self.g_arena.flat
 
     @torch.no_grad()
     def step(self, closure=None):
         hb.flush_param_grads()
-        hb.join_side_stream()
         for p, gv in zip(self._params, self.g_arena.views):
             if p.grad is not None and p.grad.data_ptr() != gv.data_ptr():
                 gv.copy_(p.grad)  # a gradient produced outside the arena (first backward after set_to_none)
