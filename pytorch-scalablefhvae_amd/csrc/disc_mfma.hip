@@ -8,7 +8,8 @@
 // The VALU kernels in loss.hip spend 2*D lane-instructions per (query,row) pair on the distance alone.
 //
 // One kernel template, three uses.  A workgroup keeps 256 STATIONARY vectors X (64 per wave, as MFMA B-operand
-// fragments in registers) and streams the other set Y through LDS in tiles of 64:
+// fragments in registers) and streams the other set Y through LDS in tiles of 64 (the pieces of allpairs_f32.h, in a loop of
+// its own: two barriers per tile with the norms taken from the LDS image in between, and a software pipeline over the tiles):
 //   MODE 0  forward   X = queries,    Y = table rows : per-query online (max, sumexp) partials per row chunk
 //   MODE 1  dq        X = queries,    Y = table rows : G_x = sum_y w[y,x] Y_y  on MFMA again -> dq = 2c (G - q W)
 //   MODE 1  dtable    X = table rows, Y = queries    : same formula gives dt = 2c (G - t W)
@@ -17,6 +18,7 @@
 // registers (row = 4*(lane>>4)+r): exactly the B-operand layout of the second product, so w never leaves registers.
 #include <algorithm>
 
+#include "allpairs_f32.h"
 #include "disc_mfma.h"
 
 #include <cstdlib>
@@ -24,12 +26,7 @@
 
 namespace fh {
 
-
-template <int D>
-__device__ __forceinline__ int yoff(int row, int ch) {  // byte offset of 16-byte chunk ch of LDS row `row`
-  constexpr int CHN = D / 4;
-  return row * (D * 4) + ((ch ^ (row & (CHN >= 8 ? 7 : CHN - 1))) << 4);
-}
+using ap::yoff;
 
 // The (query, own table row) pairs are NOT computed here.  The expanded form's absolute error ~1e-7 * 2c (|q|^2 + |t|^2) is
 // harmless on far rows (their softmax weight is 0 either way) but it is the whole signal on the pair training drives together
@@ -41,7 +38,7 @@ template <int D, int MODE>
 __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   constexpr int CHN = D / 4;   // 16-byte chunks per vector
   constexpr int NJ = D / 16;   // 16-k groups (also 16-wide d blocks)
-  constexpr int YT = 64;       // streamed vectors per LDS tile
+  constexpr int YT = ap::kYT;  // streamed vectors per LDS tile
   __shared__ __attribute__((aligned(16))) char ytile[YT * D * 4];
   __shared__ __attribute__((aligned(16))) float yn[YT];
   __shared__ float ymax[YT], yinv[YT];
@@ -70,7 +67,8 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   const int y_end = min(a.NY, y_begin + a.chunk);
   const float gscale = BW ? (*a.gsc) * a.gmul : 0.f;
 
-  // ---- stationary fragments: lane (g,i) of tile t holds X[x0+16t+i][4g+16jj .. +3]
+  // ---- stationary fragments, as ap::load_stationary lays them out, with the norm summed next to the load (the shared load and
+  // a norm loop after it cost disc_mfma_kernel<32, 2> one more spilled register)
   uint4 xf[4][NJ];
   float xn[4], xmax[4], xinv[4];
   int xtgt[4];
@@ -118,26 +116,12 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   }
 
   // ---- stream Y in tiles of 64 vectors
-  constexpr int LOADS = YT * CHN / 256;  // 16-byte chunks per thread per tile (2 for D=32)
-  uint4 st[LOADS];
-  auto issue = [&](int y0) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      const int row = id / CHN, ch = id % CHN;
-      const int y = y0 + row;
-      st[p] = (y < y_end) ? *(const uint4*)(a.Y + (int64_t)y * D + ch * 4) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  if (y_begin < y_end) issue(y_begin);
+  ap::TileMover<D> mv(a.Y, D, y_end, ytile);
+  if (y_begin < y_end) mv.issue(y_begin);
   for (int y0 = y_begin; y0 < y_end; y0 += YT) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      *(uint4*)(ytile + yoff<D>(id / CHN, id % CHN)) = st[p];
-    }
+    mv.commit();
     __syncthreads();
-    if (y0 + YT < y_end) issue(y0 + YT);
+    if (y0 + YT < y_end) mv.issue(y0 + YT);
     // per-y scalars: norm (4 lanes per vector), and for streamed queries their (max, 1/sum, target)
     {
       const int row = tid >> 2, part = tid & 3;  // 64 rows x 4 lanes
@@ -179,8 +163,7 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
       if (y0 + yb * 16 >= y_end) break;
       // A fragments of the logit product: Y[yb*16+i][4g+16jj .. +3]
       uint4 af[NJ];
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) af[jj] = *(const uint4*)(ytile + yoff<D>(yb * 16 + i, g + 4 * jj));
+      ap::read_a<D>(ytile, yb, af);
       const float4 ynv = *(const float4*)(yn + yb * 16 + 4 * g);
       const float ynr[4] = {ynv.x, ynv.y, ynv.z, ynv.w};
       float ymx[4], yiv[4];
@@ -205,18 +188,7 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
         for (int dj = 0; dj < NJ; ++dj) oacc[dj] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       // the logit product of tile t: 8 dependent MFMAs
-      auto logits = [&](int t) __attribute__((always_inline)) -> f32x4 {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-          const uint4 ua = af[jj], ub = xf[t][jj];
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.x), __uint_as_float(ub.x), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.y), __uint_as_float(ub.y), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.z), __uint_as_float(ub.z), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.w), __uint_as_float(ub.w), acc, 0, 0, 0);
-        }
-        return acc;
-      };
+      auto logits = [&](int t) __attribute__((always_inline)) -> f32x4 { return ap::dot<D>(af, xf[t]); };
       auto tile = [&](int t, auto masked_c, const f32x4& acc) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_c)::value;
         // MODE 2: B operands of the streamed side's product, xb[q][dj] = X[x0 + 16t + 4g + q][16dj + i], fetched per tile (L1 /
@@ -425,10 +397,7 @@ __global__ void disc_dq_reduce_kernel(float* __restrict__ dx, const float* __res
 // step with 512; 384 and fewer lose on the large tables: S = 1M backward 6.4 ms with 512, 7.5 ms with 384)
 int mfma_chunk(int64_t nx, int64_t ny, int target) {
   const int64_t xt = fh_cdiv(nx, 256);
-  int64_t want = fh_cdiv(target, xt);
-  int64_t chunk = fh_cdiv(fh_cdiv(ny, want), 64) * 64;
-  if (chunk < 64) chunk = 64;
-  return (int)chunk;
+  return (int)fh_allpairs_chunk(ny, fh_cdiv(target, xt), 64);
 }
 
 // host-side entry points used by loss.hip

@@ -4,26 +4,23 @@
 //   score(i, j) = (e_i . e_j) / (n_i n_j),  n = max(|e|, 1e-30),  for every i < j with label[i] >= 0 and label[j] >= 0
 //   hist[label[i] == label[j] ? 0 : 1][clamp(floor((score + 1) NB / 2), 0, NB - 1)] += 1
 //
-// The contraction is disc_mfma.hip's MODE 0: a workgroup keeps 256 STATIONARY rows (64 per wave, as MFMA B-operand fragments
-// in registers) and streams a chunk of the same matrix through LDS in tiles of 64 (same swizzle), exact-f32 MFMA
-// (v_mfma_f32_16x16x4_f32), epilogue on the VALU.  The epilogue here is a count: every lane turns its four dots into bins and
-// adds 1 to a per-workgroup LDS histogram (ds_add_u32: the LDS serialises lanes that meet in a bin, and an integer count
-// has no order); at the end the workgroup adds its non-zero bins to the (2, NB) uint64 result with vector 64-bit global
-// atomic adds.  Counts are integers: the result does not depend on the grid or on the order of arrival.
+// The contraction is allpairs_f32.h's pass over the upper triangle, the epilogue a count: every lane turns its four dots of a
+// tile into bins and adds 1 to a per-workgroup LDS histogram (ds_add_u32: the LDS serialises lanes that meet in a bin, and
+// an integer count has no order); at the end the workgroup adds its non-zero bins to the (2, NB) uint64 result with vector
+// 64-bit global atomic adds.  Counts are integers: the result does not depend on the grid or on the order of arrival.
 //
-// Symmetry, bit for bit: the k order of the MFMA chain is the same whichever row is stationary (both operands use the
-// lane (g, i) <-> d = 16 jj + 4 g + c layout) and a product of two floats commutes; the norms come from ONE kernel
-// (sv_norm_kernel, a fixed fma chain per row) and enter as the commutative product n_i n_j.  score(i, j) == score(j, i).
+// Symmetry, bit for bit: the dot is symmetric (allpairs_f32.h, THE ORDER); the norms come from ONE kernel (sv_norm_kernel, a
+// fixed fma chain per row) and enter as the commutative product n_i n_j.  score(i, j) == score(j, i).
 #include <algorithm>
 #include <cfloat>
 
-#include "common.h"
+#include "allpairs_f32.h"
 
 namespace fh {
 
 namespace {
 
-constexpr int kSvYT = 64;         // streamed rows per LDS tile
+constexpr int kSvYT = ap::kYT;
 constexpr int kSvMinChunk = 512;  // streamed rows per workgroup, at least (a workgroup zeroes and flushes 2 NB bins)
 constexpr int kSvWorkgroups = 8192;  // launched workgroups aimed at (about half of them lie below the diagonal and return)
 
@@ -35,12 +32,6 @@ struct SvArgs {
   int64_t ld;
   int S, NB, chunk;
 };
-
-template <int D>
-__device__ __forceinline__ int sv_yoff(int row, int ch) {  // byte offset of 16-byte chunk ch of LDS row `row` (disc_mfma.hip's swizzle)
-  constexpr int CHN = D / 4;
-  return row * (D * 4) + ((ch ^ (row & (CHN % 8 == 0 ? 7 : 3))) << 4);  // (stays inside an aligned group of 8 / 4 chunks: any D % 16 == 0)
-}
 
 // n[s] = max(sqrt(sum_d e[s][d]^2), 1e-30): one thread per row, one fma chain in d order
 __global__ void sv_norm_kernel(const float* __restrict__ emb, int64_t ld, int S, int D, float* __restrict__ nrm) {
@@ -61,8 +52,6 @@ __global__ void sv_norm_kernel(const float* __restrict__ emb, int64_t ld, int S,
 // (D > 96: 128 and more registers of stationary fragments; two workgroups per CU would spill)
 template <int D>
 __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void sv_hist_kernel(SvArgs a) {
-  constexpr int CHN = D / 4;  // 16-byte chunks per row
-  constexpr int NJ = D / 16;  // 16-k groups
   constexpr int YT = kSvYT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ytile = smem;                               // [YT][D] f32, swizzled
@@ -83,93 +72,49 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void sv_hist_kernel(SvArgs a) 
 
   for (int e = tid; e < 2 * NB; e += 256) h[e] = 0u;
 
-  // ---- stationary fragments: lane (g,i) of tile t holds X[x0+16t+i][4g+16jj .. +3]; rows past S carry label -1
-  uint4 xf[4][NJ];
+  uint4 xf[4][D / 16];
+  ap::load_stationary<D>(a.emb, a.ld, a.S, x0, xf);
   float xn[4];
-  int xl[4];
+  int xl[4];  // (tails on both sides carry label -1)
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int x = x0 + t * 16 + i;
-    const bool ok = x < a.S;
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-      uint4 u = make_uint4(0, 0, 0, 0);
-      if (ok) u = *(const uint4*)(a.emb + (int64_t)x * a.ld + 4 * g + 16 * jj);
-      xf[t][jj] = u;
-    }
-    xn[t] = ok ? a.nrm[x] : 1.f;
-    xl[t] = ok ? a.label[x] : -1;
+    xn[t] = x < a.S ? a.nrm[x] : 1.f;
+    xl[t] = x < a.S ? a.label[x] : -1;
   }
 
-  // ---- stream the chunk in tiles of 64 rows
-  constexpr int LOADS = YT * CHN / 256;  // 16-byte chunks per thread per tile
-  uint4 st[LOADS];
-  auto issue = [&](int y0) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      const int row = id / CHN, ch = id % CHN;
-      const int y = y0 + row;
-      st[p] = (y < y_end) ? *(const uint4*)(a.emb + (int64_t)y * a.ld + ch * 4) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  issue(y_begin);
-  for (int y0 = y_begin; y0 < y_end; y0 += YT) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      *(uint4*)(ytile + sv_yoff<D>(id / CHN, id % CHN)) = st[p];
-    }
-    if (tid < YT) {
-      const int y = y0 + tid;
-      const bool ok = y < y_end;
-      yn[tid] = ok ? a.nrm[y] : 1.f;
-      yl[tid] = ok ? a.label[y] : -1;
-    }
-    __syncthreads();
-    if (y0 + YT < y_end) issue(y0 + YT);
-
-#pragma unroll 1
-    for (int yb = 0; yb < YT / 16; ++yb) {
-      const int ybase = y0 + yb * 16;
-      if (ybase >= y_end) break;
-      if (ybase + 15 <= x0) continue;  // every j of this block <= every i of this wave
-      // A fragments: Y[yb*16+i][4g+16jj .. +3]
-      uint4 af[NJ];
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) af[jj] = *(const uint4*)(ytile + sv_yoff<D>(yb * 16 + i, g + 4 * jj));
-      const float4 ynv = *(const float4*)(yn + yb * 16 + 4 * g);
-      const int4 ylv = *(const int4*)(yl + yb * 16 + 4 * g);
-      const float ynr[4] = {ynv.x, ynv.y, ynv.z, ynv.w};
-      const int ylr[4] = {ylv.x, ylv.y, ylv.z, ylv.w};
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (ybase + 15 <= x0 + 16 * t) continue;  // (uniform over the wave)
-        // dot tile: col = lane & 15 -> stationary row x0+16t+i, accumulator r -> streamed row ybase+4g+r
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-          const uint4 ua = af[jj], ub = xf[t][jj];
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.x), __uint_as_float(ub.x), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.y), __uint_as_float(ub.y), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.z), __uint_as_float(ub.z), acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.w), __uint_as_float(ub.w), acc, 0, 0, 0);
+  ap::stream<D>(
+      a.emb, a.ld, y_begin, y_end, ytile, xf,
+      [&](int y0) {
+        if (tid < YT) {
+          const int y = y0 + tid;
+          yn[tid] = y < y_end ? a.nrm[y] : 1.f;
+          yl[tid] = y < y_end ? a.label[y] : -1;
         }
-        const int x = x0 + t * 16 + i;
+      },
+      // a block whose every j <= every i of this wave is skipped; the few blocks that straddle the diagonal are computed whole
+      // and lose their tiles below it to the x < y test
+      [&](int ybase) { return ybase + 15 > x0; },
+      [&](int y0, int yb, const f32x4(&acc)[4]) {
+        const float4 ynv = *(const float4*)(yn + yb * 16 + 4 * g);
+        const int4 ylv = *(const int4*)(yl + yb * 16 + 4 * g);
+        const float ynr[4] = {ynv.x, ynv.y, ynv.z, ynv.w};
+        const int ylr[4] = {ylv.x, ylv.y, ylv.z, ylv.w};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int y = ybase + 4 * g + r;
-          if (xl[t] >= 0 && ylr[r] >= 0 && x < y) {  // (tails on both sides carry label -1)
-            // two clamped norms can underflow as a product only when both rows are below 1e-19: the dot is 0 there
-            const float score = acc[r] / fmaxf(xn[t] * ynr[r], FLT_MIN);
-            const float b = fminf(fmaxf(floorf((score + 1.f) * half), 0.f), top);
-            atomicAdd(&h[(xl[t] == ylr[r] ? 0 : NB) + (int)b], 1u);
+        for (int t = 0; t < 4; ++t) {
+          const int x = x0 + t * 16 + i;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int y = y0 + yb * 16 + 4 * g + r;
+            if (xl[t] >= 0 && ylr[r] >= 0 && x < y) {
+              // two clamped norms can underflow as a product only when both rows are below 1e-19: the dot is 0 there
+              const float score = acc[t][r] / fmaxf(xn[t] * ynr[r], FLT_MIN);
+              const float b = fminf(fmaxf(floorf((score + 1.f) * half), 0.f), top);
+              atomicAdd(&h[(xl[t] == ylr[r] ? 0 : NB) + (int)b], 1u);
+            }
           }
         }
-      }
-    }
-    __syncthreads();
-  }
+      });
 
   // ---- flush: a workgroup's count of a bin is below 2^32 (256 * chunk trials); the sum over workgroups is 64-bit
   for (int e = tid; e < 2 * NB; e += 256) {
@@ -204,10 +149,10 @@ extern "C" int fhvae_sv_hist(const float* emb, int64_t ld, const int32_t* label,
   FH_CHECK_PTR(hist);
   FH_CHECK_PTR(ws);
   FH_CHECK_POS(S);
-  if (D < 16 || D > 128 || D % 16 != 0) return FHVAE_ERR_SHAPE;
   if (n_bins < 64 || n_bins > 8192 || (n_bins & (n_bins - 1)) != 0) return FHVAE_ERR_SHAPE;
-  if (ld < D) return FHVAE_ERR_SHAPE;
-  if (ld % 4 != 0 || ((uintptr_t)emb & 15) != 0 || ((uintptr_t)ws & 3) != 0 || ((uintptr_t)hist & 7) != 0) return FHVAE_ERR_ALIGN;
+  int rc = fh_allpairs_check(emb, ld, D);
+  if (rc != FHVAE_OK) return rc;
+  if (((uintptr_t)ws & 3) != 0 || ((uintptr_t)hist & 7) != 0) return FHVAE_ERR_ALIGN;
   if (S > ((int64_t)1 << 24)) return FHVAE_ERR_LIMIT;  // (65536 stationary blocks in the grid's y)
   if (ws_bytes < fhvae_sv_hist_ws_bytes(S)) return FHVAE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
@@ -217,7 +162,7 @@ extern "C" int fhvae_sv_hist(const float* emb, int64_t ld, const int32_t* label,
 
   float* nrm = (float*)ws;
   hipLaunchKernelGGL(sv_norm_kernel, dim3((unsigned)fh_cdiv(S, 256)), dim3(256), 0, st, emb, ld, (int)S, (int)D, nrm);
-  int rc = fh_launch_status();
+  rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
 
   SvArgs a = {};
@@ -229,17 +174,7 @@ extern "C" int fhvae_sv_hist(const float* emb, int64_t ld, const int32_t* label,
   a.S = (int)S;
   a.NB = (int)n_bins;
   const int64_t nxb = fh_cdiv(S, 256);
-  const int64_t want = std::max<int64_t>(1, kSvWorkgroups / nxb);
-  a.chunk = (int)std::max<int64_t>(kSvMinChunk, fh_cdiv(fh_cdiv(S, want), kSvYT) * kSvYT);
+  a.chunk = (int)fh_allpairs_chunk(S, std::max<int64_t>(1, kSvWorkgroups / nxb), kSvMinChunk);
   dim3 grid((unsigned)fh_cdiv(S, a.chunk), (unsigned)nxb);
-  switch (D) {
-    case 16: return sv_launch<16>(a, grid, st);
-    case 32: return sv_launch<32>(a, grid, st);
-    case 48: return sv_launch<48>(a, grid, st);
-    case 64: return sv_launch<64>(a, grid, st);
-    case 80: return sv_launch<80>(a, grid, st);
-    case 96: return sv_launch<96>(a, grid, st);
-    case 112: return sv_launch<112>(a, grid, st);
-    default: return sv_launch<128>(a, grid, st);
-  }
+  return fh_allpairs_dispatch(D, [&](auto d) { return sv_launch<decltype(d)::value>(a, grid, st); });
 }

@@ -12,11 +12,8 @@
 //   update (scikit-learn's _gradient_descent): inc = V grad < 0; G = inc ? G + 0.2 : 0.8 G; G = max(G, 0.01);
 //     V = momentum V - lr G grad; Y += V.
 //
-// The contraction is sv.hip's: a workgroup keeps 256 STATIONARY rows (64 per wave, MFMA B-operand fragments in registers) and
-// streams rows of the same matrix through swizzled LDS in tiles of 64, exact-f32 MFMA (v_mfma_f32_16x16x4_f32), epilogue on
-// the VALU.  The pass is the full N x N one: a stationary row sums over every j, nothing is scattered to the streamed side.
-// Lane (g, i) of a wave sees, for its four stationary rows, the streamed rows 4 g .. 4 g + 3 of every group of 16; the four
-// lanes of a row are added by two xor shuffles (commutative adds: the four lanes end with equal bits).
+// The contraction is allpairs_f32.h's pass over the full N x N: a stationary row sums over every j != i, nothing is scattered to
+// the streamed side.
 //
 //   tsne_affinity_kernel: one workgroup per stationary block, every pass (1 for m, kTsneSteps of the bisection, 1 for Z)
 //     inside the launch; a wave owns its 64 rows over all j, so a pass ends in the wave's registers.
@@ -27,21 +24,21 @@
 //     then adds its rows' chunks in index order and does the update.
 // No floating-point atomic anywhere: two calls give equal bits.
 //
-// Symmetry, bit for bit: the MFMA chain's k order does not depend on which row is stationary (sv.hip's argument), the norms
-// come from one kernel and enter as the commutative sum n_i + n_j, and the same expression fma(-2, dot, n_i + n_j) is used by
-// all three kernels: d2(i, j) == d2(j, i), and d2(i, j) - m_i >= 0 holds exactly in every later pass.  The norm's fma chain
-// runs in the MFMA chain's k order, so two equal rows are at distance exactly 0.
+// Symmetry, bit for bit: the dot is symmetric (allpairs_f32.h, THE ORDER), the norms come from one kernel and enter as the
+// commutative sum n_i + n_j, and the same expression fma(-2, dot, n_i + n_j) is used by all three kernels: d2(i, j) ==
+// d2(j, i), and d2(i, j) - m_i >= 0 holds exactly in every later pass.  The norm's fma chain runs in the MFMA chain's k
+// order, so two equal rows are at distance exactly 0.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
-#include "common.h"
+#include "allpairs_f32.h"
 
 namespace fh {
 
 namespace {
 
-constexpr int kTsneYT = 64;              // streamed rows per LDS tile
+constexpr int kTsneYT = ap::kYT;
 constexpr int kTsneMinChunk = 512;       // streamed rows per workgroup of the gradient pass, at least
 constexpr int kTsneWorkgroups = 2048;    // workgroups the gradient pass aims at
 constexpr float kTsneLo = -60.f, kTsneHi = 60.f;  // the interval of log2 beta
@@ -50,14 +47,8 @@ constexpr int kTsneParts = 7;            // per-row partials of a chunk: Fx, Fy,
 constexpr int64_t kTsneMaxN = (int64_t)1 << 22;
 constexpr float kLog2e = 1.44269504088896340736f;
 
-template <int D>
-__device__ __forceinline__ int ts_yoff(int row, int ch) {  // byte offset of 16-byte chunk ch of LDS row `row` (sv.hip's swizzle)
-  constexpr int CHN = D / 4;
-  return row * (D * 4) + ((ch ^ (row & (CHN % 8 == 0 ? 7 : 3))) << 4);
-}
-
 // n[s] = sum_d x[s][d]^2: one thread per row, one fma chain in the k order of the MFMA chain (16 jj + 4 g + c: c inside g
-// inside jj is the order in which the chain below meets the columns)
+// inside jj is the order in which allpairs_f32.h's chain meets the columns)
 __global__ void tsne_norm_kernel(const float* __restrict__ x, int64_t ld, int N, int D, float* __restrict__ nrm) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N) return;
@@ -78,86 +69,6 @@ __global__ void tsne_norm_kernel(const float* __restrict__ x, int64_t ld, int N,
   nrm[s] = ss;
 }
 
-// the stationary fragments of a wave: lane (g, i) of tile t holds X[x0 + 16 t + i][4 g + 16 jj .. + 3]; rows past N are zero
-template <int D>
-__device__ __forceinline__ void ts_load_stationary(const float* __restrict__ x, int64_t ld, int N, int x0, uint4 (&xf)[4][D / 16]) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, i = lane & 15;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int r = x0 + t * 16 + i;
-#pragma unroll
-    for (int jj = 0; jj < D / 16; ++jj) {
-      uint4 u = make_uint4(0, 0, 0, 0);
-      if (r < N) u = *(const uint4*)(x + (int64_t)r * ld + 4 * g + 16 * jj);
-      xf[t][jj] = u;
-    }
-  }
-}
-
-// Stream rows y_begin .. y_end - 1 in tiles of 64.  side(y0) fills the tile's per-row LDS arrays (called by every thread before
-// the barrier); pair(yb, acc) gets, for the 16 streamed rows y0 + 16 yb .. + 15, acc[t][r] = X[x0 + 16 t + i] . X[y0 + 16 yb + 4 g + r].
-template <int D, class Side, class Pair>
-__device__ __forceinline__ void ts_stream(const float* __restrict__ x, int64_t ld, int y_begin, int y_end, char* ytile,
-                                          const uint4 (&xf)[4][D / 16], Side side, Pair pair) {
-  constexpr int CHN = D / 4, NJ = D / 16, YT = kTsneYT;
-  constexpr int LOADS = YT * CHN / 256;  // 16-byte chunks per thread per tile
-  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, i = lane & 15;
-  uint4 st[LOADS];
-  auto issue = [&](int y0) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      const int row = id / CHN, ch = id % CHN;
-      const int y = y0 + row;
-      st[p] = (y < y_end) ? *(const uint4*)(x + (int64_t)y * ld + ch * 4) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  issue(y_begin);
-  for (int y0 = y_begin; y0 < y_end; y0 += YT) {
-#pragma unroll
-    for (int p = 0; p < LOADS; ++p) {
-      const int id = tid + p * 256;
-      *(uint4*)(ytile + ts_yoff<D>(id / CHN, id % CHN)) = st[p];
-    }
-    side(y0);
-    __syncthreads();
-    if (y0 + YT < y_end) issue(y0 + YT);
-#pragma unroll 1
-    for (int yb = 0; yb < YT / 16; ++yb) {
-      if (y0 + yb * 16 >= y_end) break;
-      uint4 af[NJ];
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) af[jj] = *(const uint4*)(ytile + ts_yoff<D>(yb * 16 + i, g + 4 * jj));
-      f32x4 acc[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) {  // four independent chains: the 16x16x4 form needs two to reach its issue rate
-        const uint4 ua = af[jj];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.x), __uint_as_float(xf[t][jj].x), acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.y), __uint_as_float(xf[t][jj].y), acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.z), __uint_as_float(xf[t][jj].z), acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ua.w), __uint_as_float(xf[t][jj].w), acc[t], 0, 0, 0);
-      }
-      pair(y0, yb, acc);
-    }
-    __syncthreads();
-  }
-}
-
-__device__ __forceinline__ float ts_quad_sum(float v) {  // over the four lanes (g = 0..3) of a stationary row
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-__device__ __forceinline__ float ts_quad_min(float v) {
-  v = fminf(v, __shfl_xor(v, 16, 64));
-  return fminf(v, __shfl_xor(v, 32, 64));
-}
 __device__ __forceinline__ float ts_d2(float dot, float nx, float ny) { return fmaxf(__builtin_fmaf(-2.f, dot, nx + ny), 0.f); }
 
 struct TsneAffArgs {
@@ -182,7 +93,7 @@ __global__ __launch_bounds__(256, D > 80 ? 1 : 2) void tsne_affinity_kernel(Tsne
   const int N = a.N;
 
   uint4 xf[4][D / 16];
-  ts_load_stationary<D>(a.x, a.ld, N, x0, xf);
+  ap::load_stationary<D>(a.x, a.ld, N, x0, xf);
   float xn[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) xn[t] = (x0 + t * 16 + i < N) ? a.nrm[x0 + t * 16 + i] : 0.f;
@@ -193,7 +104,7 @@ __global__ __launch_bounds__(256, D > 80 ? 1 : 2) void tsne_affinity_kernel(Tsne
 
   // ---- m = the smallest distance to another row
   float mn[4] = {FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX};
-  ts_stream<D>(a.x, a.ld, 0, N, ytile, xf, side, [&](int y0, int yb, const f32x4(&acc)[4]) {
+  ap::stream<D>(a.x, a.ld, 0, N, ytile, xf, side, ap::EveryBlock(), [&](int y0, int yb, const f32x4(&acc)[4]) {
     const float4 ynv = *(const float4*)(yn + yb * 16 + 4 * g);
     const float ynr[4] = {ynv.x, ynv.y, ynv.z, ynv.w};
 #pragma unroll
@@ -206,7 +117,7 @@ __global__ __launch_bounds__(256, D > 80 ? 1 : 2) void tsne_affinity_kernel(Tsne
       }
   });
 #pragma unroll
-  for (int t = 0; t < 4; ++t) mn[t] = ts_quad_min(mn[t]);
+  for (int t = 0; t < 4; ++t) mn[t] = ap::quad_min(mn[t]);
 
   // ---- the bisection; the pass after its last step sums Z at the final beta
   float lo[4], hi[4], mid[4], s0[4], s1[4], nbl[4];
@@ -220,7 +131,7 @@ __global__ __launch_bounds__(256, D > 80 ? 1 : 2) void tsne_affinity_kernel(Tsne
       nbl[t] = -(exp2f(mid[t]) * kLog2e);  // exp(-beta u) = 2^(nbl u)
       s0[t] = 0.f, s1[t] = 0.f;
     }
-    ts_stream<D>(a.x, a.ld, 0, N, ytile, xf, side, [&](int y0, int yb, const f32x4(&acc)[4]) {
+    ap::stream<D>(a.x, a.ld, 0, N, ytile, xf, side, ap::EveryBlock(), [&](int y0, int yb, const f32x4(&acc)[4]) {
       const float4 ynv = *(const float4*)(yn + yb * 16 + 4 * g);
       const float ynr[4] = {ynv.x, ynv.y, ynv.z, ynv.w};
 #pragma unroll
@@ -236,8 +147,8 @@ __global__ __launch_bounds__(256, D > 80 ? 1 : 2) void tsne_affinity_kernel(Tsne
     });
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      s0[t] = ts_quad_sum(s0[t]);
-      s1[t] = ts_quad_sum(s1[t]);
+      s0[t] = ap::quad_sum(s0[t]);
+      s1[t] = ap::quad_sum(s1[t]);
       if (step < kTsneSteps) {  // (s0 >= 1: the nearest row's term is exactly 1)
         const float h = logf(s0[t]) + exp2f(mid[t]) * s1[t] / s0[t];
         const bool up = h > a.log_perp;
@@ -286,7 +197,7 @@ __global__ __launch_bounds__(256, D > 48 ? 1 : 2) void tsne_grad_kernel(TsneGrad
   const int y_begin = blockIdx.y * a.chunk, y_end = min(N, y_begin + a.chunk);  // (the host's grid leaves no empty chunk)
 
   uint4 xf[4][D / 16];
-  ts_load_stationary<D>(a.x, a.ld, N, x0, xf);
+  ap::load_stationary<D>(a.x, a.ld, N, x0, xf);
   float xn[4], xb[4], xm[4], xz[4], xy0[4], xy1[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -318,7 +229,7 @@ __global__ __launch_bounds__(256, D > 48 ? 1 : 2) void tsne_grad_kernel(TsneGrad
       sy[5 * YT + tid - YT] = v.y;
     }
   };
-  ts_stream<D>(a.x, a.ld, y_begin, y_end, ytile, xf, side, [&](int y0, int yb, const f32x4(&acc)[4]) {
+  ap::stream<D>(a.x, a.ld, y_begin, y_end, ytile, xf, side, ap::EveryBlock(), [&](int y0, int yb, const f32x4(&acc)[4]) {
     float sv[6][4];
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -358,8 +269,8 @@ __global__ __launch_bounds__(256, D > 48 ? 1 : 2) void tsne_grad_kernel(TsneGrad
   float* part = a.part + (int64_t)blockIdx.y * kTsneParts * a.npad;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    const float v[kTsneParts] = {ts_quad_sum(f0[t]), ts_quad_sum(f1[t]), ts_quad_sum(r0[t]), ts_quad_sum(r1[t]),
-                                 ts_quad_sum(ws[t]), ts_quad_sum(ka[t]), ts_quad_sum(kb[t])};
+    const float v[kTsneParts] = {ap::quad_sum(f0[t]), ap::quad_sum(f1[t]), ap::quad_sum(r0[t]), ap::quad_sum(r1[t]),
+                                 ap::quad_sum(ws[t]), ap::quad_sum(ka[t]), ap::quad_sum(kb[t])};
     const int r = x0 + t * 16 + i;
     if (g == 0 && r < N) {
 #pragma unroll
@@ -454,8 +365,7 @@ struct TsnePlan {
 TsnePlan tsne_plan(int64_t N) {
   TsnePlan p;
   p.nxb = fh_cdiv(N, 256);
-  const int64_t want = std::max<int64_t>(1, kTsneWorkgroups / p.nxb);
-  p.chunk = std::max<int64_t>(kTsneMinChunk, fh_cdiv(fh_cdiv(N, want), kTsneYT) * kTsneYT);
+  p.chunk = fh_allpairs_chunk(N, std::max<int64_t>(1, kTsneWorkgroups / p.nxb), kTsneMinChunk);
   p.nchunks = fh_cdiv(N, p.chunk);
   p.npad = fh_cdiv(N, 64) * 64;
   p.part_off = p.npad;
@@ -466,9 +376,9 @@ TsnePlan tsne_plan(int64_t N) {
 
 int tsne_check(const float* x, int64_t ld, int64_t N, int64_t D, const void* ws, int64_t ws_bytes) {
   if (N < 8) return FHVAE_ERR_SHAPE;
-  if (D < 16 || D > 128 || D % 16 != 0) return FHVAE_ERR_SHAPE;
-  if (ld < D) return FHVAE_ERR_SHAPE;
-  if (ld % 4 != 0 || ((uintptr_t)x & 15) != 0 || ((uintptr_t)ws & 15) != 0) return FHVAE_ERR_ALIGN;
+  const int rc = fh_allpairs_check(x, ld, D);
+  if (rc != FHVAE_OK) return rc;
+  if (((uintptr_t)ws & 15) != 0) return FHVAE_ERR_ALIGN;
   if (N > kTsneMaxN) return FHVAE_ERR_LIMIT;
   if (ws_bytes < fhvae_tsne_ws_bytes(N, D)) return FHVAE_ERR_SHAPE;
   return FHVAE_OK;
@@ -479,34 +389,21 @@ int tsne_norms(const float* x, int64_t ld, int64_t N, int64_t D, float* nrm, hip
   return fh_launch_status();
 }
 
-template <int D>
-int tsne_aff_launch(const TsneAffArgs& a, dim3 grid, hipStream_t st) {
-  const int smem = kTsneYT * D * 4 + kTsneYT * 4;
-  hipLaunchKernelGGL(tsne_affinity_kernel<D>, grid, dim3(256), (size_t)smem, st, a);
-  return fh_launch_status();
+int tsne_aff_launch(int64_t D, const TsneAffArgs& a, dim3 grid, hipStream_t st) {
+  return fh_allpairs_dispatch(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    hipLaunchKernelGGL(tsne_affinity_kernel<DD>, grid, dim3(256), (size_t)(kTsneYT * DD * 4 + kTsneYT * 4), st, a);
+    return fh_launch_status();
+  });
 }
 
-template <int D>
-int tsne_grad_launch(const TsneGradArgs& a, dim3 grid, hipStream_t st) {
-  const int smem = kTsneYT * D * 4 + 6 * kTsneYT * 4 + 16 * 4;
-  hipLaunchKernelGGL(tsne_grad_kernel<D>, grid, dim3(256), (size_t)smem, st, a);
-  return fh_launch_status();
+int tsne_grad_launch(int64_t D, const TsneGradArgs& a, dim3 grid, hipStream_t st) {
+  return fh_allpairs_dispatch(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    hipLaunchKernelGGL(tsne_grad_kernel<DD>, grid, dim3(256), (size_t)(kTsneYT * DD * 4 + 6 * kTsneYT * 4 + 16 * 4), st, a);
+    return fh_launch_status();
+  });
 }
-
-#define TSNE_DISPATCH(fn, ...)                       \
-  switch (D) {                                       \
-    case 16: return fn<16>(__VA_ARGS__);             \
-    case 32: return fn<32>(__VA_ARGS__);             \
-    case 48: return fn<48>(__VA_ARGS__);             \
-    case 64: return fn<64>(__VA_ARGS__);             \
-    case 80: return fn<80>(__VA_ARGS__);             \
-    case 96: return fn<96>(__VA_ARGS__);             \
-    case 112: return fn<112>(__VA_ARGS__);           \
-    default: return fn<128>(__VA_ARGS__);            \
-  }
-
-int tsne_grad_dispatch(int64_t D, const TsneGradArgs& a, dim3 grid, hipStream_t st) { TSNE_DISPATCH(tsne_grad_launch, a, grid, st) }
-int tsne_aff_dispatch(int64_t D, const TsneAffArgs& a, dim3 grid, hipStream_t st) { TSNE_DISPATCH(tsne_aff_launch, a, grid, st) }
 
 // the norms, the gradient pass and the reduction / update: what fhvae_tsne_step and fhvae_tsne_grad share
 int tsne_pass(const float* x, int64_t ld, int64_t N, int64_t D, const float* beta, const float* m, const float* z, float* y, float* v,
@@ -522,7 +419,7 @@ int tsne_pass(const float* x, int64_t ld, int64_t N, int64_t D, const float* bet
   a.ld = ld, a.N = (int)N, a.npad = (int)p.npad, a.chunk = (int)p.chunk, a.kl = want_kl;
   a.inv2n = (float)(0.5 / (double)N);
   a.nn = (float)((double)N * (double)N);
-  rc = tsne_grad_dispatch(D, a, dim3((unsigned)p.nxb, (unsigned)p.nchunks), st);
+  rc = tsne_grad_launch(D, a, dim3((unsigned)p.nxb, (unsigned)p.nchunks), st);
   if (rc != FHVAE_OK) return rc;
   TsneUpdArgs u = {};
   u.part = a.part, u.wg = a.wg, u.y = y, u.v = v, u.g = g, u.out = out, u.scal = scal, u.kl = kl;
@@ -559,7 +456,7 @@ extern "C" int fhvae_tsne_affinity(const float* x, int64_t ld, int64_t N, int64_
   TsneAffArgs a = {};
   a.x = x, a.nrm = (const float*)ws, a.beta = beta, a.m = m, a.z = z;
   a.ld = ld, a.N = (int)N, a.log_perp = (float)std::log((double)perplexity);
-  return tsne_aff_dispatch(D, a, dim3((unsigned)fh_cdiv(N, 256)), st);
+  return tsne_aff_launch(D, a, dim3((unsigned)fh_cdiv(N, 256)), st);
 }
 
 extern "C" int fhvae_tsne_step(const float* x, int64_t ld, int64_t N, int64_t D, const float* beta, const float* m, const float* z, float* y,

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import disc_compare as DC
+from disc_plan import cdiv as _cdiv, group_bytes as _group_bytes
 from oracle.disc_ref import disc_ref_bwd, disc_ref_fwd
 
 pytestmark = pytest.mark.gpu
@@ -32,22 +33,6 @@ def _form(B, S, D, lp):
     if D in (16, 32) and B * S >= 65536:
         return "split" if lp and D == 32 else "expanded"
     return "direct"
-
-
-def _cdiv(a, b):
-    return -(-a // b)
-
-
-def _mfma_chunk(nx, ny, target):
-    want = _cdiv(target, _cdiv(nx, 256))
-    return max(64, _cdiv(_cdiv(ny, want), 64) * 64)
-
-
-def _group_bytes(tiles, B, S, D):
-    """Workspace of the one-pass backward for query groups of `tiles` 256-query tiles (disc_mfma.hip onepass_group_bytes)."""
-    rows = min(B, tiles * 256)
-    nchunks = _cdiv(S, _mfma_chunk(rows, S, 512))
-    return (nchunks * rows * D + tiles * S * (D + 1)) * 4
 
 
 def _sink(S, D, G0, seed):
