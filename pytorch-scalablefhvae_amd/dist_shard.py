@@ -304,6 +304,29 @@ class DistributedFHVAE:
         # grouped weight-gradient launch stays whole (split in two it costs ~60 us at the bench shape)
         self.overlap = self.sh.world > 1
 
+    # -- what the training loop and the hierarchical trainer ask of a runner (hip_optim.LocalRunner: the same on one GPU) -------
+    load_label, split_times = "merge", True  # a block's log line: estimate and merge printed apart
+    world = property(lambda self: self.sh.world)
+    rank = property(lambda self: self.sh.rank)
+    row0 = property(lambda self: self.sh.row0)
+    optimizers = property(lambda self: [self.opt_nets, self.opt_table])
+
+    def all_reduce_(self, t, op=None):
+        return self.sh.all_reduce_(t, op=op)
+
+    def table_rows(self):
+        """(rows, m_rows, v_rows) of this rank: the shard is the only parameter of opt_table, its moments the arena's first n."""
+        n = self.shard.numel()
+        return self.shard.data, self.opt_table.m[:n], self.opt_table.v[:n]
+
+    def load_block(self, est, packed, ratio):
+        """The merge of a block's estimate: pack -> all-gather -> rank-order sum + load of the own rows (two launches, one
+        collective)."""
+        hb, sh = self.sh.backend.hb, self.sh
+        hb.hs_pack_partials(est.zsum, est.count, packed)
+        parts = sh.all_gather(packed).view(sh.world, *packed.shape)
+        hb.mu2_merge_load_shard(parts, sh.row0, sh.row1, *self.table_rows(), ratio)
+
     def _on_lstm_rec_done(self, sinks):
         """Fired by hip_binding when a net's backward RECURRENCE has been enqueued (with deferred parameter gradients: queued
         behind it).  Nets finish in bucket order.  When the second-to-last net (the z1 encoder) is through, the queued weight

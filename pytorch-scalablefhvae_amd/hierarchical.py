@@ -5,9 +5,11 @@ over only those K rows.  A step's cost and memory depend on K, not on the corpus
 
   plan_epoch            host: the epoch's blocks (numpy Generator seeded from (seed, epoch)), every block K distinct sequences
   HierarchicalTrainer   device: per block select (fhvae_hs_select) -> estimate (encode_z2 + fhvae_mu2_accumulate_sorted)
-                        -> load (fhvae_mu2_load_table into the FusedAdam arena) -> one shuffled pass of training steps
-  DistributedHierarchicalTrainer  the same blocks on W ranks over the row-sharded K-row table (dist_shard): each rank estimates
-                        a range of the block, the partials are all-gathered and summed in rank order (fhvae_mu2_merge_load_shard)
+                        -> load (the runner's load_block) -> one shuffled pass of training steps.  Written for W ranks; what
+                        differs between one GPU and W ranks is behind the runner (hip_optim.LocalRunner: fhvae_mu2_load_table
+                        into the FusedAdam arena; dist_shard.DistributedFHVAE: the row-sharded K-row table, the partials
+                        all-gathered and summed in rank order by fhvae_mu2_merge_load_shard)
+  DistributedHierarchicalTrainer  its constructor for a DistributedFHVAE
   estimate_pool_mu2     every sequence's mu2 of a pool by the same deterministic path (dev evaluation in this mode)
 
 The model's table has K rows; row i holds the mu2 of the current block's i-th sequence, so a table row means nothing across blocks.
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from dist_shard import rank_range, rank_slice
+from utils import mu2_ratio
 
 
 def eligible_sequences(seq_counts) -> np.ndarray:
@@ -48,11 +51,6 @@ def plan_epoch(eligible, K: int, seed: int, epoch: int) -> np.ndarray:
     return perm.reshape(nb, K)
 
 
-def mu2_ratio(model) -> float:
-    """exp(pz2_logvar) / exp(pmu2_logvar), utils.py:58."""
-    return float(np.exp(model.pz2[1]) / np.exp(model.pmu2[1]))
-
-
 @torch.no_grad()
 def estimate_pool_mu2(model, pool, chunk: int = 4096) -> torch.Tensor:
     """(pool.num_seqs, z2_dim) closed-form mu2 of every sequence of a pool grouped by sequence: encode_z2 over the segments in
@@ -71,47 +69,59 @@ def estimate_pool_mu2(model, pool, chunk: int = 4096) -> torch.Tensor:
 
 
 class HierarchicalTrainer:
-    """Runs the blocks of hierarchical sampling on one GPU.
+    """Runs the blocks of hierarchical sampling, on one GPU or on the W ranks of a distributed runner.
 
     model      FHVAE / SimpleFHVAE built with num_seqs=K (its mu2_table lives in `optimizer`'s arena)
     optimizer  hip_optim.FusedAdam over the model's parameters
+    runner     the hip_optim.LocalRunner over both, when the caller has one (train_model); otherwise one is made here
     pool       datasets.ResidentSegmentPool or datasets.SyntheticSegmentPool (`seq_ptr`, `seq_counts`, `seg_seq`, `features`,
                `batch`)
     step_fn    step_fn(local_idx, features, nsegs) -> (loss, lower_bound): one training step with num_seqs = K (train_model's
                eager step or its --hip-graph replay)
     The shuffled pass of a block is torch.randperm(N, generator=self.gen), self.gen a CUDA generator seeded with `seed` once.
     The estimate runs encode_z2 over chunks of `chunk` segments in CSR order.
+
+    On W ranks (DistributedHierarchicalTrainer: the K-row table row-sharded by dist_shard.DistributedFHVAE, rank r owns rows
+    [row0, row1), the nets replicated):
+    select     every rank selects the whole block (the plan and fhvae_hs_select are deterministic: identical on every rank)
+    estimate   rank r encodes the contiguous range rank_range(N, W, r) of the block's CSR list into its own (K, D) sums; a
+               sequence that crosses a range boundary is split over two ranks, which the merge makes whole
+    merge      fhvae_hs_pack_partials -> ONE all-gather of (K, D+1) -> fhvae_mu2_merge_load_shard: the W partials of the own
+               rows summed in rank order (independent of how the transport reduces: identical on every rank for a given W),
+               loaded into the shard, its Adam moment rows zeroed
+    train      the same seeded generator on every rank; each global batch of B is cut to a multiple of W (rank_slice) and rank
+               r steps on its slice
+    The status word is all-reduced (MAX) where it is read, so every rank raises together.
     """
 
     def __init__(self, model, optimizer, pool, K: int, batch_size: int, step_fn: Callable, seed: int = 0, chunk: int = 4096,
-                 log: Optional[Callable] = print):
+                 log: Optional[Callable] = print, runner=None):
         from fhvae_core import LocalTableOps
-
-        import hip_binding as hb
+        from hip_optim import LocalRunner
 
         if not isinstance(model.table_ops, LocalTableOps):
             raise ValueError("HierarchicalTrainer needs the single-GPU mu2 table; a row-sharded table (dist_shard) is trained "
                              "by DistributedHierarchicalTrainer")
-        table = model.mu2_table
-        if table is None or table.shape[0] != K:
+        if model.mu2_table is None or model.mu2_table.shape[0] != K:
             raise ValueError("hierarchical sampling with K=%d needs a model built with num_seqs=K" % K)
-        self.hb, self.model, self.opt, self.pool = hb, model, optimizer, pool
-        self.K, self.D, self.B = int(K), int(table.shape[1]), int(batch_size)
+        runner = runner if runner is not None else LocalRunner(model, optimizer)
+        self._setup(runner, pool, K, batch_size, step_fn, seed, chunk, log)
+
+    def _setup(self, runner, pool, K, batch_size, step_fn, seed, chunk, log):
+        import hip_binding as hb
+
+        self.hb, self.runner, self.model, self.pool = hb, runner, runner.model, pool
+        self.world, self.rank = runner.world, runner.rank
+        self.K, self.B = int(K), int(batch_size)
+        if self.B % self.world:
+            raise ValueError("the batch size %d is not a multiple of the %d ranks" % (self.B, self.world))
         self.step_fn, self.chunk, self.log = step_fn, int(chunk), log
         self.seed = int(seed)
-        self.dev = table.device
         self.eligible = eligible_sequences(pool.seq_counts)
         if self.K > len(self.eligible):
             raise ValueError("K=%d exceeds the %d sequences that have segments" % (self.K, len(self.eligible)))
-        # the table's slice of the Adam moments: FusedAdam packs parameters into one arena in order
-        slot = [i for i, p in enumerate(optimizer._params) if p is table]
-        if len(slot) != 1:
-            raise ValueError("the optimizer does not hold the model's mu2 table")
-        off = optimizer.p_arena.offsets[slot[0]]
-        n = self.K * self.D
-        if optimizer.p_arena.flat[off:off + n].data_ptr() != table.data_ptr():
-            raise RuntimeError("the mu2 table is not the optimizer arena's view")
-        self.m_rows, self.v_rows = optimizer.m[off:off + n], optimizer.v[off:off + n]
+        rows = runner.table_rows()[0]  # the table rows this rank owns (one GPU: all K)
+        self.D, self.dev = int(rows.shape[1]), rows.device
         # capacity: the K longest sequences (no block can hold more segments)
         cap = int(np.sort(np.asarray(pool.seq_counts, dtype=np.int64))[::-1][:self.K].sum())
         self.seg_ids = torch.zeros(cap, dtype=torch.int64, device=self.dev)
@@ -120,12 +130,18 @@ class HierarchicalTrainer:
         self.words = torch.zeros(2, dtype=torch.int64, device=self.dev)
         self.n_out, self.status = self.words[0:1], self.words[1:2].view(torch.int32)[0:1]
         self.est = hb.SortedMu2Estimator(self.K, self.D, self.dev, status=self.status)
-        self.ratio = mu2_ratio(model)
+        # W ranks: this rank's partial sums and counts, packed for the one all-gather of the merge
+        self.packed = torch.zeros(self.K, self.D + 1, device=self.dev, dtype=torch.float32) if self.world > 1 else None
+        self.ratio = mu2_ratio(self.model)
         self.gen = torch.Generator(device=self.dev)
         self.gen.manual_seed(self.seed)
-        self.times = {}  # the last block's select / estimate / load times (ms, device events)
+        self.times = {}  # the last block's select / estimate / load (W ranks: merge) times (ms, device events)
+        self.skipped = 0  # segments of ragged last batches nobody trained (at most W - 1 per block; one GPU: none)
 
     def _read_words(self):
+        if self.world > 1:
+            # words[0] (the block's segment count) is the same on every rank; MAX over the status half raises on every rank at once
+            self.runner.all_reduce_(self.words, op=torch.distributed.ReduceOp.MAX)
         h = self.words.cpu()
         st = int(h[1]) & 0xFFFFFFFF
         if st:
@@ -142,9 +158,11 @@ class HierarchicalTrainer:
 
     @torch.no_grad()
     def estimate(self, N: int):
-        """3b: encode_z2 over the block's segments in fixed chunks, summed per local index without float atomics."""
-        for c0 in range(0, N, self.chunk):
-            c1 = min(N, c0 + self.chunk)
+        """3b: encode_z2 over this rank's range of the block's segments in fixed chunks, summed per local index without float
+        atomics."""
+        a, b = rank_range(N, self.world, self.rank)
+        for c0 in range(a, b, self.chunk):
+            c1 = min(b, c0 + self.chunk)
             z2 = self.model.encode_z2(self.pool.features(self.seg_ids[c0:c1]))
             self.est.add(z2, self.local_idx[c0:c1])
 
@@ -153,15 +171,22 @@ class HierarchicalTrainer:
         FusedAdam keeps ONE step count, which keeps running: the fresh rows' first updates get the late-step bias correction
         of the nets (m and v warm up from 0 with factors ~1: steps of up to ~lr/sqrt(1-beta2) relative size on their first
         gradients, shrinking over ~1/(1-beta2) steps), as --continue-from from a reference checkpoint does (train_model.py)."""
-        self.est.load_into(self.model.mu2_table.data, self.m_rows, self.v_rows, self.ratio)
+        self.runner.load_block(self.est, self.packed, self.ratio)
 
     def train_pass(self, N: int):
-        """3d: one device-side shuffled pass over the block's segments in batches of B.  Returns (sum of losses (device), steps)."""
+        """3d: one device-side shuffled pass over the block's segments in batches of B, this rank's slice of each.  Returns
+        (sum of losses (device), steps)."""
         perm = torch.randperm(N, device=self.dev, generator=self.gen)
         total = torch.zeros((), device=self.dev)
         nb = 0
         for s in range(0, N, self.B):
             sel = perm[s:s + self.B]
+            a, b, skip = rank_slice(sel.shape[0], self.world, self.rank)
+            self.skipped += skip
+            if b == a:
+                continue
+            if self.world > 1:
+                sel = sel[a:b]
             ids, li = self.seg_ids[sel], self.local_idx[sel]
             _, x, nsegs = self.pool.batch(ids)
             loss, _ = self.step_fn(li, x, nsegs)
@@ -171,6 +196,7 @@ class HierarchicalTrainer:
 
     def run_block(self, block_seqs, j: int = 0, n_blocks: int = 1):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        skipped0 = self.skipped
         ev[0].record()
         N = self.select(block_seqs)
         ev[1].record()
@@ -180,12 +206,17 @@ class HierarchicalTrainer:
         ev[3].record()
         total, nb = self.train_pass(N)
         ev[3].synchronize()  # (the estimate and load only: the block's steps are queued behind them)
+        skip, label = self.skipped - skipped0, self.runner.load_label
         self.times = {"select_ms": ev[0].elapsed_time(ev[1]), "estimate_ms": ev[1].elapsed_time(ev[2]),
-                      "load_ms": ev[2].elapsed_time(ev[3])}
-        if self.log is not None:
-            self.log("hs block %d/%d: %d seqs, %d segments, estimate %.2f ms" % (j + 1, n_blocks, self.K, N,
-                                                                                self.times["estimate_ms"] + self.times["load_ms"]))
-        return total, nb, N
+                      label + "_ms": ev[2].elapsed_time(ev[3])}
+        est_ms, load_ms = self.times["estimate_ms"], self.times[label + "_ms"]
+        if self.log is not None and not self.runner.split_times:
+            self.log("hs block %d/%d: %d seqs, %d segments, estimate %.2f ms" % (j + 1, n_blocks, self.K, N, est_ms + load_ms))
+        elif self.log is not None:
+            self.log("hs block %d/%d: %d seqs, %d segments, estimate %.2f ms, %s %.2f ms%s" % (
+                j + 1, n_blocks, self.K, N, est_ms, label, load_ms,
+                (", %d segments of the last batch skipped (not a multiple of %d ranks)" % (skip, self.world)) if skip else ""))
+        return total, nb, N - skip
 
     def run_epoch(self, epoch: int, check: Optional[Callable] = None):
         """Every block of the epoch's plan.  `check(steps so far)` (optional) runs after each block and may return an exit code
@@ -208,111 +239,14 @@ class HierarchicalTrainer:
 
 
 class DistributedHierarchicalTrainer(HierarchicalTrainer):
-    """The blocks of hierarchical sampling on W ranks: the K-row table is row-sharded by `runner` (dist_shard.DistributedFHVAE,
-    rank r owns rows [row0, row1)), the nets are replicated.
-
-    select     every rank selects the whole block (the plan and fhvae_hs_select are deterministic: identical on every rank)
-    estimate   rank r encodes the contiguous range rank_range(N, W, r) of the block's CSR list into its own (K, D) sums; a
-               sequence that crosses a range boundary is split over two ranks, which the merge makes whole
-    merge      fhvae_hs_pack_partials -> ONE all-gather of (K, D+1) -> fhvae_mu2_merge_load_shard: the W partials of the own
-               rows summed in rank order (independent of how the transport reduces: identical on every rank for a given W),
-               loaded into the shard, its Adam moment rows zeroed
-    train      the block's shuffled pass as on one GPU (the same seeded generator on every rank); each global batch of B is cut
-               to a multiple of W (rank_slice) and rank r steps on its slice: step_fn(local_idx, x, nsegs)
-    The status word is all-reduced (MAX) where it is read, so every rank raises together.
-    """
+    """HierarchicalTrainer over a dist_shard.DistributedFHVAE (its class docstring: what each step does on W ranks)."""
 
     def __init__(self, runner, pool, K: int, batch_size: int, step_fn: Callable, seed: int = 0, chunk: int = 4096,
                  log: Optional[Callable] = print):
-        import hip_binding as hb
-
-        model, sh = runner.model, runner.sh
-        if sh.S != K:
+        if runner.sh.S != K:
             raise ValueError("hierarchical sampling with K=%d needs a model built with num_seqs=K (the runner's table has %d rows)"
-                             % (K, sh.S))
-        self.hb, self.runner, self.sh, self.model, self.opt, self.pool = hb, runner, sh, model, None, pool
-        self.K, self.D, self.B = int(K), int(runner.shard.shape[1]), int(batch_size)
-        if self.B % sh.world:
-            raise ValueError("the batch size %d is not a multiple of the %d ranks" % (self.B, sh.world))
-        self.step_fn, self.chunk, self.log = step_fn, int(chunk), log
-        self.seed = int(seed)
-        self.dev = runner.shard.device
-        self.eligible = eligible_sequences(pool.seq_counts)
-        if self.K > len(self.eligible):
-            raise ValueError("K=%d exceeds the %d sequences that have segments" % (self.K, len(self.eligible)))
-        n = runner.shard.numel()  # the shard is the only parameter of opt_table: its moments are the arena's first n
-        self.m_rows, self.v_rows = runner.opt_table.m[:n], runner.opt_table.v[:n]
-        cap = int(np.sort(np.asarray(pool.seq_counts, dtype=np.int64))[::-1][:self.K].sum())
-        self.seg_ids = torch.zeros(cap, dtype=torch.int64, device=self.dev)
-        self.local_idx = torch.zeros(cap, dtype=torch.int64, device=self.dev)
-        self.words = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        self.n_out, self.status = self.words[0:1], self.words[1:2].view(torch.int32)[0:1]
-        self.est = hb.SortedMu2Estimator(self.K, self.D, self.dev, status=self.status)
-        self.packed = torch.zeros(self.K, self.D + 1, device=self.dev, dtype=torch.float32)
-        self.ratio = mu2_ratio(model)
-        self.gen = torch.Generator(device=self.dev)
-        self.gen.manual_seed(self.seed)
-        self.times = {}
-        self.skipped = 0  # segments of ragged last batches nobody trained (at most W - 1 per block)
-
-    def _read_words(self):
-        # words[0] (the block's segment count) is the same on every rank; MAX over the status half raises on every rank at once
-        self.sh.all_reduce_(self.words, op=torch.distributed.ReduceOp.MAX)
-        return super()._read_words()
-
-    @torch.no_grad()
-    def estimate(self, N: int):
-        a, b = rank_range(N, self.sh.world, self.sh.rank)
-        for c0 in range(a, b, self.chunk):
-            c1 = min(b, c0 + self.chunk)
-            z2 = self.model.encode_z2(self.pool.features(self.seg_ids[c0:c1]))
-            self.est.add(z2, self.local_idx[c0:c1])
-
-    def load(self):
-        """The merge: pack -> all-gather -> rank-order sum + load of the own rows (two launches, one collective)."""
-        self.hb.hs_pack_partials(self.est.zsum, self.est.count, self.packed)
-        parts = self.sh.all_gather(self.packed).view(self.sh.world, self.K, self.D + 1)
-        self.hb.mu2_merge_load_shard(parts, self.sh.row0, self.sh.row1, self.runner.shard.data, self.m_rows, self.v_rows,
-                                     self.ratio)
-
-    def train_pass(self, N: int):
-        perm = torch.randperm(N, device=self.dev, generator=self.gen)
-        total = torch.zeros((), device=self.dev)
-        nb = 0
-        for s in range(0, N, self.B):
-            sel = perm[s:s + self.B]
-            a, b, skip = rank_slice(sel.shape[0], self.sh.world, self.sh.rank)
-            self.skipped += skip
-            if b == a:
-                continue
-            sel = sel[a:b]
-            ids, li = self.seg_ids[sel], self.local_idx[sel]
-            _, x, nsegs = self.pool.batch(ids)
-            loss, _ = self.step_fn(li, x, nsegs)
-            total += loss
-            nb += 1
-        return total, nb
-
-    def run_block(self, block_seqs, j: int = 0, n_blocks: int = 1):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        skipped0 = self.skipped
-        ev[0].record()
-        N = self.select(block_seqs)
-        ev[1].record()
-        self.estimate(N)
-        ev[2].record()
-        self.load()
-        ev[3].record()
-        total, nb = self.train_pass(N)
-        ev[3].synchronize()
-        self.times = {"select_ms": ev[0].elapsed_time(ev[1]), "estimate_ms": ev[1].elapsed_time(ev[2]),
-                      "merge_ms": ev[2].elapsed_time(ev[3])}
-        if self.log is not None:
-            skip = self.skipped - skipped0
-            self.log("hs block %d/%d: %d seqs, %d segments, estimate %.2f ms, merge %.2f ms%s" % (
-                j + 1, n_blocks, self.K, N, self.times["estimate_ms"], self.times["merge_ms"],
-                (", %d segments of the last batch skipped (not a multiple of %d ranks)" % (skip, self.sh.world)) if skip else ""))
-        return total, nb, N - (self.skipped - skipped0)
+                             % (K, runner.sh.S))
+        self._setup(runner, pool, K, batch_size, step_fn, seed, chunk, log)
 
 
 def hs_clamp(K: int, seq_counts, log: Optional[Callable] = print) -> int:

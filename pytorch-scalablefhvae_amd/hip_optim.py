@@ -122,3 +122,55 @@ class FusedAdam(torch.optim.Optimizer):
         hb.adam_step_(self.p_arena.flat, self.g_arena.flat, self.m, self.v, self._step_buf, g["lr"], g["betas"][0],
                       g["betas"][1], g["eps"], self.grad_scale, flags=hb.ADAM_ZERO_GRAD | hb.ADAM_ADVANCE)
         self._zeroed_by_step = True
+
+
+class LocalRunner:
+    """The one-GPU counterpart of dist_shard.DistributedFHVAE: the members the training loop (train_model) and the hierarchical
+    trainer use.  One model, ONE FusedAdam over model.parameters() (the checkpoint layout), the whole mu2 table in its arena."""
+
+    world, rank, row0 = 1, 0, 0
+    load_label, split_times = "load", False  # a block's log line: estimate and load printed as one sum
+
+    def __init__(self, model, optimizer: FusedAdam, loss_function=None):
+        """`loss_function(lower_bound, log_qy, alpha)` (train_model's) is what train_step minimises; a runner that only serves a
+        HierarchicalTrainer with a step function of its own needs none."""
+        self.model, self.optimizer, self.optimizers, self._loss = model, optimizer, [optimizer], loss_function
+        self.num_seqs = int(model.mu2_table.shape[0])  # the table's rows: forward()'s num_seqs
+        self.lstm_status = 0  # what check_status() last read from the recurrence's status word
+        self._rows = None
+
+    def train_step(self, x, idx, nsegs, alpha=10.0):
+        """One iteration of the reference loop body, train_model.py:446-454."""
+        self.optimizer.zero_grad()
+        out = self.model(x, idx, self.num_seqs, nsegs)
+        loss = self._loss(out[0], out[1], alpha)
+        hb.backward(loss)  # (loss.backward() with a cached seed)
+        self.optimizer.step()
+        return loss.detach(), out[0].detach()
+
+    def check_status(self) -> int:
+        """One host sync, no collective: 0 = healthy; 2 = a NaN lower bound was seen; 3 = a persistent LSTM launch gave up."""
+        if hb.diverged(self.model.mu2_table.device):
+            return 2  # sys.exit(2), train_model.py:464-466
+        self.lstm_status = hb.lstm_sync_status()
+        return 3 if self.lstm_status != 0 else 0
+
+    def all_reduce_(self, t, op=None):
+        return None
+
+    def table_rows(self):
+        """(rows, m_rows, v_rows): the table and its slice of the Adam moments (FusedAdam packs parameters into one arena)."""
+        if self._rows is None:
+            table, opt = self.model.mu2_table, self.optimizer
+            slot = [i for i, p in enumerate(opt._params) if p is table]
+            if len(slot) != 1:
+                raise ValueError("the optimizer does not hold the model's mu2 table")
+            off, n = opt.p_arena.offsets[slot[0]], table.numel()
+            if opt.p_arena.flat[off:off + n].data_ptr() != table.data_ptr():
+                raise RuntimeError("the mu2 table is not the optimizer arena's view")
+            self._rows = (table.data, opt.m[off:off + n], opt.v[off:off + n])
+        return self._rows
+
+    def load_block(self, est, packed, ratio):
+        """A finished block estimate into the table: rows = zsum / (count + r) in place in the arena, their m and v zeroed."""
+        est.load_into(*self.table_rows(), ratio)

@@ -21,6 +21,11 @@ def check_best(val_lower_bound, best_val_lb) -> bool:
     return bool(torch.mean(val_lower_bound) > best_val_lb)
 
 
+def mu2_ratio(model) -> float:
+    """exp(pz2_logvar) / exp(pmu2_logvar), utils.py:58."""
+    return float(np.exp(model.pz2[1]) / np.exp(model.pmu2[1]))
+
+
 def estimate_mu2_dict(model, loader, num_seqs):
     """Estimate mu2 for sequences (utils.py:45-60): mu2[y] = sum z2_mu / (n_y + exp(pz2_logvar)/exp(pmu2_logvar)).
     `loader` yields (idxs, features, nsegs) like the reference's DataLoader (or ResidentSegmentPool.epoch).
@@ -36,8 +41,7 @@ def estimate_mu2_dict(model, loader, num_seqs):
             if est is None:
                 est = hb.Mu2Estimator(num_seqs, z2_mu.shape[1], z2_mu.device)
             est.add(z2_mu, torch.as_tensor(idxs).to(device=z2_mu.device, dtype=torch.int64))
-    r = float(np.exp(model.pz2[1]) / np.exp(model.pmu2[1]))  # utils.py:58
-    mu2, count = est.result(r)
+    mu2, count = est.result(mu2_ratio(model))
     seen = torch.nonzero(count > 0).flatten().tolist()
     return {y: mu2[y] for y in seen}
 
@@ -115,8 +119,12 @@ def save_checkpoint(model, optimizer, summary_list, values_dict, run_info: str, 
 def load_checkpoint_file(checkpoint_file, finetune, input_size=None):
     """utils.py:63-102.  Accepts the reference's 5-value `model_params` (then `input_size` must be given) and this
     build's 6-value form; a reference checkpoint has no `mu2_table` (the reference never kept one)."""
+    return load_checkpoint(torch.load(checkpoint_file, map_location="cpu", weights_only=False), finetune, input_size)
+
+
+def load_checkpoint(checkpoint: dict, finetune, input_size=None):
+    """load_checkpoint_file on a checkpoint that is already in memory."""
     optim_state = start_epoch = best_val_lb = summary_list = values = None
-    checkpoint = torch.load(checkpoint_file, map_location="cpu", weights_only=False)
     model_type = checkpoint["model_type"]
     params = tuple(checkpoint["model_params"])
     if len(params) == 5:
