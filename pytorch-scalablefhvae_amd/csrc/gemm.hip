@@ -89,7 +89,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int bx, int by, i
   zero_acc(acc);
   RowIdent arm{p.M}, brm{p.N};
   bool dma = false;
-  if constexpr (kDma)
+  if constexpr (kDma)  // (mirrored by gemm_plan's dma_tiles in tests/gemm_plan.py)
     dma = p.splitk == 1 && m0 + BM <= p.M && n0 + BN <= p.N && seg_glds_ok<T>(p.seg[0], TL::BK) && seg_glds_ok<T>(p.seg[1], TL::BK);
   if (dma) {
     if constexpr (kDma) mainloop_glds<T, BM, BN, WM, WN, CH, NBUF, SWAP>(acc, p.seg, m0, n0, arm, brm, smem);
@@ -220,6 +220,7 @@ __global__ void gemm_slow_kernel(GemmParams p) {
 
 template <typename T, int BM, int BN, int CH>
 static void launch_fast(const GemmParams& p, dim3 grid, hipStream_t st) {
+  // (mirrored by gemm_plan's `kernel` in tests/gemm_plan.py: change both)
   const int akc = p.seg[0].K > 0 ? p.seg[0].a_kc : p.seg[1].a_kc;
   const int bkc = p.seg[0].K > 0 ? p.seg[0].b_kc : p.seg[1].b_kc;
   if (akc && bkc) {
@@ -241,7 +242,7 @@ static void launch_fast(const GemmParams& p, dim3 grid, hipStream_t st) {
 }
 
 // splitk == 0 on entry means "choose": only legal with mode 1 (accumulate), switched to atomics when split
-static int auto_splitk(int64_t tiles, int64_t panels) {
+static int auto_splitk(int64_t tiles, int64_t panels) {  // (mirrored by auto_splitk in tests/gemm_plan.py)
   if (tiles >= 192 || panels < 4) return 1;
   int64_t s = fh_cdiv(512, tiles);
   if (s > panels / 2) s = panels / 2;
@@ -251,7 +252,7 @@ static int auto_splitk(int64_t tiles, int64_t panels) {
 }
 
 int launch_gemm(const GemmParams& p_in, int dtype, hipStream_t st) {
-  GemmParams p = p_in;
+  GemmParams p = p_in;  // (the decisions below are mirrored by gemm_plan in tests/gemm_plan.py: change both)
   if (p.M <= 0 || p.N <= 0) return FHVAE_ERR_SHAPE;
   if (dtype != FHVAE_F32 && dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
   const bool want_auto = p.splitk == 0;

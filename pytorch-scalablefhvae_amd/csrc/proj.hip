@@ -195,6 +195,7 @@ int launch_proj(const void* a, int64_t lda, const void* b, int64_t ldb, float* c
   ProjArgs p = {(const u16*)a, (const u16*)b, c, bias, bias2, bias_split, lda, ldb, ldc, (int)M, (int)N, (int)K};
   const int BN = N > 128 ? 256 : 128;
   const int64_t ncol = fh_cdiv(N, BN);
+  // (mirrored by proj_plan in tests/gemm_plan.py: change both)
   // the row tile that fills the chip's 256 CUs in the fewest rounds with the least padding: one round if it can
   int best = 256;
   double best_t = 1e30;

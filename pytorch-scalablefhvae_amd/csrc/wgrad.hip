@@ -275,7 +275,7 @@ template __global__ void wgrad_kernel<WgF32, 128>(WgGroupT<WgF32>);
 template <class T>
 bool wgrad_eligible(const WgProblemT<T>& p) {
   using E = WgElem<T>;
-  constexpr int64_t ES = sizeof(T);
+  constexpr int64_t ES = sizeof(T);  // (mirrored by wgrad_desc_ok in tests/gemm_plan.py)
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.A || !p.B || !p.C) return false;
   if ((((uintptr_t)p.A) | ((uintptr_t)p.B)) & 15) return false;
   if ((p.lda % (16 / ES)) || (p.ldb % (16 / ES)) || p.lda < p.a_col0 + p.M || p.ldb < p.N || p.a_col0 < 0) return false;
@@ -287,6 +287,7 @@ bool wgrad_eligible(const WgProblemT<T>& p) {
 template <class T, int BN>
 static int launch_class(const WgProblemT<T>* ps, const int* which, int n, hipStream_t st) {
   using E = WgElem<T>;
+  // (mirrored, cost model included, by wgrad_class_plan in tests/gemm_plan.py: change both)
   // one launch of about one workgroup per CU: the K slices are what is left after the tiles
   for (int at = 0; at < n; at += kMaxWgProblems) {
     const int cnt = n - at < kMaxWgProblems ? n - at : kMaxWgProblems;
@@ -338,7 +339,7 @@ static int launch_class(const WgProblemT<T>* ps, const int* which, int n, hipStr
 template <class T>
 int launch_wgrad(const WgProblemT<T>* ps, int n, hipStream_t st) {
   if (n <= 0) return FHVAE_OK;
-  int wide[256], narrow[256], nw = 0, nn = 0;
+  int wide[256], narrow[256], nw = 0, nn = 0;  // (mirrored by wgrad_plan in tests/gemm_plan.py)
   if (n > 256) return FHVAE_ERR_LIMIT;
   for (int k = 0; k < n; ++k) {
     if (!wgrad_eligible(ps[k])) return FHVAE_ERR_ALIGN;
