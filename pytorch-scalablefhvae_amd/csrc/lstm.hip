@@ -21,6 +21,7 @@
 #include <vector>
 #include "trace.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace fh {
 
@@ -497,15 +498,6 @@ static int cast_operands(const fhvae_lstm_desc* d, hipStream_t st) {
   return fh_launch_status();
 }
 
-// the large-tile cells (lstm_cell.hip) take a wavefront step once it offers them about a workgroup per CU (f32, whose
-// generic cells are further from their roofline: from 256 tiles per launch); FHVAE_BIG_CELLS=0/1 overrides
-static bool big_cells(int64_t B, int64_t H, int dtype = FHVAE_BF16) {
-  const char* ev = getenv("FHVAE_BIG_CELLS");  // read per call: the tests flip it
-  const int env = ev ? atoi(ev) : -1;
-  if (env >= 0) return env != 0;
-  return (B / 128) * (H / 64) >= (dtype == FHVAE_F32 ? 64 : 96);
-}
-
 // the forward jobs of wavefront step w; `big`: for the large-tile cells, which multiply layer 0's input themselves (no `pre`)
 template <typename T>
 static FwdJobs<T> fwd_jobs(const fhvae_lstm_desc* d, const Ops<T>& op, int64_t w, bool big, int& nj) {
@@ -566,38 +558,25 @@ static bool cell_fwd_plan_ok(const fhvae_lstm_desc* d, const Ops<T>& op) {
   return true;
 }
 
-// the shape part of the large-tile cells' preconditions (what remains is 16-byte alignment of the caller's buffers)
-static bool big_shape_ok(const fhvae_lstm_desc* d) {
-  const int es = d->dtype == FHVAE_BF16 ? 2 : 4, epc = 16 / es;
-  if (d->B % 128 || d->H % 64 || d->I % epc || d->Ic % epc) return false;
-  if (d->B * 4 * d->H * 4 >= (1LL << 31) || (int64_t)d->L * d->H * d->B * 4 >= (1LL << 31)) return false;
-  return 4 * d->H * (d->I + d->Ic > d->H ? d->I + d->Ic : d->H) * es < (1LL << 30);
-}
-
 template <typename T>
-static int lstm_fwd_impl(const fhvae_lstm_desc* d, const Ops<T>& op, hipStream_t st) {
+static int lstm_fwd_impl(const fhvae_lstm_desc* d, const LstmPlan& pl, const Ops<T>& op, hipStream_t st) {
   const int64_t B = d->B, T_ = d->T, I = d->I, Ic = d->Ic, H = d->H;
   const int L = d->L;
   const int64_t K0 = I + Ic;
   const T* w0 = op.w_ih[0];
+  // large-tile step cells (lstm_cell.hip; all steps of the sequence or none): they multiply layer 0's input themselves
+  const bool cell_big = pl.big && cell_fwd_plan_ok(d, op);
+  // fhvae_lstm_pre_elems has promised the caller that `pre` is not needed for this shape
+  if (pl.big && pl.big_shape && !cell_big) return FHVAE_ERR_ALIGN;
   // ---- layer-0 input projection (+ both biases): pre = [x_t || xc] . W_ih0^T + b_ih0 + b_hh0.  The persistent kernels
   //      multiply x_t themselves when they can (fold): then only the time-constant part is left for this GEMM
-  bool cluster = false, fold = false, xc_in = false;
-  if constexpr (sizeof(T) == 2) {
-    cluster = cluster_eligible(d);
-    fold = cluster && cluster_can_fold(d);
-    xc_in = cluster && cluster_xc_in_kernel(d);
-  }
-  // large-tile step cells (lstm_cell.hip; all steps of the sequence or none): they multiply layer 0's input themselves
-  const bool cell_big = !cluster && big_cells(B, H, d->dtype) && cell_fwd_plan_ok(d, op);
-  // fhvae_lstm_pre_elems has promised the caller that `pre` is not needed for this shape
-  if (!cluster && !cell_big && big_cells(B, H, d->dtype) && big_shape_ok(d)) return FHVAE_ERR_ALIGN;
-  if (!cell_big && !(fold && Ic == 0) && !xc_in) {
+  const bool xt = I > 0 && !pl.fold;  // x_t is part of it: T*B rows
+  if (!cell_big && !(pl.fold && Ic == 0) && !pl.xc_in) {
     GemmParams p = {};
     int s = 0;
-    if (I > 0 && !fold) p.seg[s++] = Seg{op.x, I, 1, w0, K0, 1, (int)I, 0};
-    if (Ic > 0) p.seg[s++] = Seg{op.xc, Ic, 1, w0 + I, K0, 1, (int)Ic, (I > 0 && !fold) ? (int)B : 0};
-    p.M = (int)((I > 0 && !fold) ? T_ * B : B);
+    if (xt) p.seg[s++] = Seg{op.x, I, 1, w0, K0, 1, (int)I, 0};
+    if (Ic > 0) p.seg[s++] = Seg{op.xc, Ic, 1, w0 + I, K0, 1, (int)Ic, xt ? (int)B : 0};
+    p.M = (int)(xt ? T_ * B : B);
     p.N = (int)(4 * H);
     p.C = d->pre;
     p.ldc = 4 * H;
@@ -608,99 +587,75 @@ static int lstm_fwd_impl(const fhvae_lstm_desc* d, const Ops<T>& op, hipStream_t
     if (e) return e;
   }
   if constexpr (sizeof(T) == 2) {
-    if (cluster) {  // persistent form: the whole recurrence in one launch (lstm_cluster.hip)
+    if (pl.form) {  // persistent form: the whole recurrence in one launch (lstm_cluster.hip)
       ClusterWeights cw = {};
       for (int l = 0; l < L; ++l) cw.w_ih[l] = op.w_ih[l], cw.w_hh[l] = op.w_hh[l], cw.w_ih_t[l] = op.w_ih_t[l], cw.w_hh_t[l] = op.w_hh_t[l];
       cw.xch = (u16*)d->lp + lp_layout(d).xch;
-      cw.x_fold = fold ? (const u16*)op.x : nullptr;
-      cw.xc_fold = xc_in ? (const u16*)op.xc : nullptr;
-      return cluster_fwd(d, cw, st);
+      cw.x_fold = pl.fold ? (const u16*)op.x : nullptr;
+      cw.xc_fold = pl.xc_in ? (const u16*)op.xc : nullptr;
+      return cluster_fwd(d, pl, cw, st);
     }
   }
-  if constexpr (sizeof(T) == 2) {
-  }
-  {
-    if (cell_big) {  // large-tile cells (lstm_cell.hip)
-      for (int64_t w = 0; w < T_ + L - 1; ++w) {
-        int nj = 0;
-        const FwdJobs<T> jobs = fwd_jobs(d, op, w, true, nj);
-        double fl = 0;
-        for (int j = 0; j < nj; ++j)
-          fl += 2.0 * B * 4 * H * (jobs.job[j].seg[0].K + jobs.job[j].seg[1].K + jobs.job[j].xseg[0].K + jobs.job[j].xseg[1].K);
-        const int ts = trace_begin(st, kTraceFwdCell, fl);
-        const int e = launch_cell_fwd_big(jobs, nj, st);
-        trace_end(st, ts);
-        if (e) return e;
-      }
-      return FHVAE_OK;
-    }
-  }
-  // ---- wavefront over (layer, time)
+  // ---- wavefront over (layer, time): the large-tile cells, or the step cells in one of three tile classes.
+  // 128x128 tiles (half the L2 -> LDS operand bytes per FLOP) only pay once they still give >= 2 workgroups per CU (see
+  // gemm.hip): B >= 16384 at H = 256, B >= 2048 at H = 512 (configs[3]: 2048 workgroups of 64x64 pulled 14 TB/s from L2)
+  // (measured at B = 2048, H = 512, bf16: 128x128 tiles 1.3-1.8 ms per net forward against 1.0-1.3 ms with 64x64: the
+  //  heuristic stays "B >= 16384").  64x64 tiles from B = 1024, many workgroups per CU: 256-byte panels (32 KB LDS) so 2
+  // workgroups per CU keep twice the bytes in flight; below, 512-byte panels.
+  const bool big_fwd = B >= 16384;
+  auto step_kernel = [&](auto save) -> void (*)(FwdJobs<T>) {  // (save false: fhvae_lstm_seq_infer)
+    constexpr bool kSave = decltype(save)::value;
+    return big_fwd     ? lstm_fwd_step_kernel<T, 128, 128, 2, 2, 16, kSave>
+           : B >= 1024 ? lstm_fwd_step_kernel<T, 64, 64, 4, 1, 16, kSave>
+                       : lstm_fwd_step_kernel<T, 64, 64, 4, 1, kCH, kSave>;
+  };
+  const auto kernel = d->gates ? step_kernel(std::true_type{}) : step_kernel(std::false_type{});
   for (int64_t w = 0; w < T_ + L - 1; ++w) {
     int nj = 0;
-    const FwdJobs<T> jobs = fwd_jobs(d, op, w, false, nj);
+    const FwdJobs<T> jobs = fwd_jobs(d, op, w, cell_big, nj);
     double fl = 0;
-    for (int j = 0; j < nj; ++j) fl += 2.0 * B * 4 * H * (jobs.job[j].seg[0].K + jobs.job[j].seg[1].K);
+    for (int j = 0; j < nj; ++j)
+      fl += 2.0 * B * 4 * H * (jobs.job[j].seg[0].K + jobs.job[j].seg[1].K + jobs.job[j].xseg[0].K + jobs.job[j].xseg[1].K);
     const int ts = trace_begin(st, kTraceFwdCell, fl);
-    // large tiles (half the L2 -> LDS operand bytes per FLOP) only pay once they still give >= 2 workgroups per CU (see
-    // gemm.hip): B >= 16384 at H = 256, B >= 2048 at H = 512 (configs[3]: 2048 workgroups of 64x64 pulled 14 TB/s from L2)
-    // (measured at B = 2048, H = 512, bf16: 128x128 tiles 1.3-1.8 ms per net forward against 1.0-1.3 ms with 64x64: the
-    //  heuristic stays "B >= 16384")
-    const bool big_fwd = B >= 16384;
-    const bool save = d->gates != nullptr;  // (NULL: fhvae_lstm_seq_infer, kSave = false)
-    if (big_fwd) {
-      dim3 grid((unsigned)fh_cdiv(B, 128), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
-      if (save)
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 128, 128, 2, 2, 16, true>), grid, dim3(kThreads), 0, st, jobs);
-      else
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 128, 128, 2, 2, 16, false>), grid, dim3(kThreads), 0, st, jobs);
-    } else if (B >= 1024) {
-      // many workgroups per CU: 256-byte panels (32 KB LDS) so 2 workgroups per CU keep twice the bytes in flight
-      dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 16), (unsigned)nj);
-      if (save)
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, 16, true>), grid, dim3(kThreads), 0, st, jobs);
-      else
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, 16, false>), grid, dim3(kThreads), 0, st, jobs);
+    int e;
+    if (cell_big) {
+      e = launch_cell_fwd_big(jobs, nj, st);
     } else {
-      dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 16), (unsigned)nj);
-      if (save)
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, kCH, true>), grid, dim3(kThreads), 0, st, jobs);
-      else
-        hipLaunchKernelGGL((lstm_fwd_step_kernel<T, 64, 64, 4, 1, kCH, false>), grid, dim3(kThreads), 0, st, jobs);
+      const dim3 grid((unsigned)fh_cdiv(B, big_fwd ? 128 : 64), (unsigned)fh_cdiv(H, big_fwd ? 32 : 16), (unsigned)nj);
+      hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, jobs);
+      e = fh_launch_status();
     }
     trace_end(st, ts);
-    int e = fh_launch_status();
     if (e) return e;
   }
   return FHVAE_OK;
 }
 
 extern "C" int fhvae_lstm_form(const fhvae_lstm_desc* d) {
-  if (!d || check_desc(d, kCheckShape) != FHVAE_OK || !cluster_eligible(d)) return 0;
-  return cluster_form(d);
+  return d && check_desc(d, kCheckShape) == FHVAE_OK ? lstm_plan(d).form : 0;
 }
 
-// What decides the layouts of the tensors a forward saves for its backward (gates, the schedule-specific workspaces): the schedule
-// (per-step cells, large-tile cells, persistent rows / contraction-split form) and its variants (register-stationary forward:
-// unit-major gates).  The schedule is re-derived per call from the descriptor and the environment: a caller keeps the forward's
-// value and compares it before the backward (hip_binding does; a mismatch would otherwise be silently wrong gradients).
+// What decides the layouts of the tensors a forward saves for its backward (gates, the schedule-specific workspaces): the plan's
+// schedule (per-step cells, large-tile cells, persistent rows / contraction-split form) and its register-stationary forward
+// (unit-major gates).  Forward and backward each make their plan from the descriptor and the environment of their own call: a
+// caller keeps the forward's value and compares it before the backward (hip_binding does; a switch flipped in between would
+// otherwise be silently wrong gradients).
 extern "C" int fhvae_lstm_layout_id(const fhvae_lstm_desc* d) {
   if (!d || check_desc(d, kCheckShape) != FHVAE_OK) return -1;
-  if (d->dtype == FHVAE_BF16 && cluster_eligible(d)) return 16 + cluster_form(d) * 2 + (cluster_fwd_wr_ok(d) ? 1 : 0);
-  return big_cells(d->B, d->H, d->dtype) && big_shape_ok(d) ? 1 : 0;
+  const LstmPlan pl = lstm_plan(d);
+  return pl.form ? 16 + pl.form * 2 + pl.fwd_wr : pl.big && pl.big_shape;
 }
 
 extern "C" int64_t fhvae_lstm_pre_elems(const fhvae_lstm_desc* d) {
   if (!d || d->L < 1 || d->L > FHVAE_MAX_LAYERS || d->B <= 0 || d->T <= 0 || d->H <= 0) return 0;
-  const int64_t full = (d->I > 0 ? d->T : 1) * d->B * 4 * d->H;
-  if (d->dtype == FHVAE_BF16 && cluster_eligible(d)) return (d->I == 0 || cluster_can_fold(d)) ? d->B * 4 * d->H : full;
-  if (big_cells(d->B, d->H, d->dtype) && big_shape_ok(d)) return 1;  // the cells multiply layer 0's input themselves
-  return full;
+  const LstmPlan pl = lstm_plan(d);
+  if (pl.big && pl.big_shape) return 1;  // the cells multiply layer 0's input themselves
+  // (B,4H) is asked for even where xc_in, or fold without a time-constant input, leaves nothing to project: callers size by it
+  return (d->I > 0 && !pl.fold ? d->T : 1) * d->B * 4 * d->H;
 }
 
 extern "C" int64_t fhvae_lstm_ws_below_elems(const fhvae_lstm_desc* d) {
-  if (!d || d->dtype != FHVAE_BF16 || d->L < 2) return 0;
-  return cluster_needs_ws_below(d) ? d->T * d->B * d->H : 0;
+  return d && lstm_plan(d).needs_ws_below ? d->T * d->B * d->H : 0;
 }
 
 __global__ void cast_hn_kernel(const float* __restrict__ s, u16* __restrict__ d, int64_t n) {
@@ -709,7 +664,7 @@ __global__ void cast_hn_kernel(const float* __restrict__ s, u16* __restrict__ d,
 }
 
 // the forward of a checked descriptor; gates == NULL: the inference forward (fhvae_lstm_seq_infer)
-static int lstm_seq_fwd_checked(const fhvae_lstm_desc* d, void* stream) {
+static int lstm_seq_fwd_checked(const fhvae_lstm_desc* d, const LstmPlan& pl, void* stream) {
   int e;
   hipStream_t st = (hipStream_t)stream;
   if (d->dtype == FHVAE_F32) {
@@ -725,14 +680,14 @@ static int lstm_seq_fwd_checked(const fhvae_lstm_desc* d, void* stream) {
       e = fh_launch_status();
       if (e) return e;
     }
-    return lstm_fwd_impl<float>(d, ops_f32(d), st);
+    return lstm_fwd_impl<float>(d, pl, ops_f32(d), st);
   }
   e = cast_operands(d, st);
   if (e) return e;
-  e = lstm_fwd_impl<u16>(d, ops_bf16(d), st);
+  e = lstm_fwd_impl<u16>(d, pl, ops_bf16(d), st);
   if (e || !d->hn_lp) return e;
   if (!d->hn) return FHVAE_ERR_NULL;
-  if (cluster_eligible(d)) return FHVAE_OK;  // the persistent forward kernels stored the bf16 copy beside hn
+  if (pl.form) return FHVAE_OK;  // the persistent forward kernels stored the bf16 copy beside hn
   const int64_t n = d->B * d->L * d->H;
   hipLaunchKernelGGL(cast_hn_kernel, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, st, d->hn, (u16*)d->hn_lp, n);
   return fh_launch_status();
@@ -740,21 +695,20 @@ static int lstm_seq_fwd_checked(const fhvae_lstm_desc* d, void* stream) {
 
 extern "C" int fhvae_lstm_seq_fwd(const fhvae_lstm_desc* d, void* stream) {
   const int e = check_desc(d);
-  return e ? e : lstm_seq_fwd_checked(d, stream);
+  return e ? e : lstm_seq_fwd_checked(d, lstm_plan(d), stream);
 }
 
 // the persistent schedules keep c in registers / LDS; the per-step cells need c_{t-1} of every layer: a two-slot ring (L,2,B,H)
 extern "C" int64_t fhvae_lstm_infer_cs_elems(const fhvae_lstm_desc* d) {
-  if (!d || check_desc(d, kCheckShape) != FHVAE_OK) return 0;
-  if (d->dtype == FHVAE_BF16 && cluster_eligible(d)) return 0;
-  return 2 * (int64_t)d->L * d->B * d->H;
+  return d && check_desc(d, kCheckShape) == FHVAE_OK && !lstm_plan(d).form ? 2 * (int64_t)d->L * d->B * d->H : 0;
 }
 
 extern "C" int fhvae_lstm_seq_infer(const fhvae_lstm_desc* d, void* stream) {
   int e = check_desc(d, kCheckInfer);
   if (e) return e;
-  if (fhvae_lstm_infer_cs_elems(d) > 0 && !d->cs) return FHVAE_ERR_NULL;
-  return lstm_seq_fwd_checked(d, stream);
+  const LstmPlan pl = lstm_plan(d);
+  if (!pl.form && !d->cs) return FHVAE_ERR_NULL;  // (fhvae_lstm_infer_cs_elems)
+  return lstm_seq_fwd_checked(d, pl, stream);
 }
 
 // the backward jobs of wavefront step w (layer l at time T-1-(w-(L-1-l)))
@@ -819,63 +773,55 @@ static bool cell_bwd_plan_ok(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op) {
 }
 
 template <typename T>
-static int lstm_bwd_impl(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hipStream_t st) {
+static int lstm_bwd_impl(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const Ops<T>& op, hipStream_t st) {
   const fhvae_lstm_desc* d = &bd->f;
   const int64_t B = d->B, T_ = d->T, Ic = d->Ic, H = d->H;
   const int L = d->L;
-  constexpr bool kF32 = sizeof(T) == 4;
-  if constexpr (!kF32) {
-    if (cluster_eligible(d)) {  // the forward on this workspace took the persistent form too (same predicate)
+  if constexpr (sizeof(T) == 2) {
+    if (pl.form) {
       ClusterWeights cw = {};
       for (int l = 0; l < L; ++l) cw.w_ih[l] = op.w_ih[l], cw.w_hh[l] = op.w_hh[l], cw.w_ih_t[l] = op.w_ih_t[l], cw.w_hh_t[l] = op.w_hh_t[l];
       cw.xch = (u16*)d->lp + lp_layout(d).xch;
-      return cluster_bwd(bd, cw, st);
+      return cluster_bwd(bd, pl, cw, st);
     }
   }
-  if (big_cells(B, H, d->dtype) && cell_bwd_plan_ok(bd, op)) {
-    // large-tile cells (lstm_cell.hip); they leave the time sum of layer 0's gate gradients to one pass over the saved
-    // dgates.  (Tried: the batch rows as 2 / 4 independent launch chains on side streams, so that one chain's
-    // HBM-bound epilogue would run beside the other's contraction: 348 k / 312 k segments/s against 361 k for one chain.)
-    for (int64_t w = 0; w < T_ + L - 1; ++w) {
-      int nj = 0;
-      const BwdJobs<T> jobs = bwd_jobs<T>(bd, op, w, nj);
-      double fl = 0;
-      for (int j = 0; j < nj; ++j) fl += 2.0 * B * H * (jobs.job[j].seg[0].K + jobs.job[j].seg[1].K);
-      const int ts = trace_begin(st, kTraceBwdCell, fl);
-      const int e = launch_cell_bwd_big(jobs, nj, st);
-      trace_end(st, ts);
-      if (e) return e;
-    }
-    if (Ic > 0) return launch_cell_dgsum((const T*)bd->dgates, bd->dgsum, (int)T_, B * 4 * H, st);
-    return FHVAE_OK;
-  }
+  // large-tile cells (lstm_cell.hip); they leave the time sum of layer 0's gate gradients to one pass over the saved
+  // dgates.  (Tried: the batch rows as 2 / 4 independent launch chains on side streams, so that one chain's
+  // HBM-bound epilogue would run beside the other's contraction: 348 k / 312 k segments/s against 361 k for one chain.)
+  const bool cell_big = pl.big && cell_bwd_plan_ok(bd, op);
   for (int64_t w = 0; w < T_ + L - 1; ++w) {
     int nj = 0;
     const BwdJobs<T> jobs = bwd_jobs<T>(bd, op, w, nj);
     double fl = 0;
     for (int j = 0; j < nj; ++j) fl += 2.0 * B * H * (jobs.job[j].seg[0].K + jobs.job[j].seg[1].K);
     const int ts = trace_begin(st, kTraceBwdCell, fl);
-    // tile by how many workgroups the shape offers (>= 2 per CU wanted): 128x64 from B = 16384 at H = 256, 64x64 from
-    // B = 2048 at H = 512 (32x32 tiles there: 2048 workgroups re-reading 1 GB of operand panels per launch from L2)
-    // (measured at B = 2048, H = 512, bf16: 64x64 tiles 2.4 ms per net backward, 32x32 2.2-2.3 ms: no gain from larger tiles)
-    const int bt = B >= 16384 ? 128 : 32;
-    if (bt == 128) {
-      dim3 grid((unsigned)fh_cdiv(B, 128), (unsigned)fh_cdiv(H, 64), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 128, 64, 4, 1, 16>), grid, dim3(kThreads), 0, st, jobs);
-    } else if (bt == 64) {
-      dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 64), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 64, 64, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
-    } else if (B >= 1024) {
-      dim3 grid((unsigned)fh_cdiv(B, 32), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 32, 32, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
+    int e;
+    if (cell_big) {
+      e = launch_cell_bwd_big(jobs, nj, st);
     } else {
-      dim3 grid((unsigned)fh_cdiv(B, 32), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
-      hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 32, 32, 2, 2, kCH>), grid, dim3(kThreads), 0, st, jobs);
+      // tile by how many workgroups the shape offers (>= 2 per CU wanted): 128x64 from B = 16384 at H = 256, 64x64 from
+      // B = 2048 at H = 512 (32x32 tiles there: 2048 workgroups re-reading 1 GB of operand panels per launch from L2)
+      // (measured at B = 2048, H = 512, bf16: 64x64 tiles 2.4 ms per net backward, 32x32 2.2-2.3 ms: no gain from larger tiles)
+      const int bt = B >= 16384 ? 128 : 32;
+      if (bt == 128) {
+        dim3 grid((unsigned)fh_cdiv(B, 128), (unsigned)fh_cdiv(H, 64), (unsigned)nj);
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 128, 64, 4, 1, 16>), grid, dim3(kThreads), 0, st, jobs);
+      } else if (bt == 64) {
+        dim3 grid((unsigned)fh_cdiv(B, 64), (unsigned)fh_cdiv(H, 64), (unsigned)nj);
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 64, 64, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
+      } else if (B >= 1024) {
+        dim3 grid((unsigned)fh_cdiv(B, 32), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 32, 32, 2, 2, 16>), grid, dim3(kThreads), 0, st, jobs);
+      } else {
+        dim3 grid((unsigned)fh_cdiv(B, 32), (unsigned)fh_cdiv(H, 32), (unsigned)nj);
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<T, 32, 32, 2, 2, kCH>), grid, dim3(kThreads), 0, st, jobs);
+      }
+      e = fh_launch_status();
     }
     trace_end(st, ts);
-    int e = fh_launch_status();
     if (e) return e;
   }
+  if (cell_big && Ic > 0) return launch_cell_dgsum((const T*)bd->dgates, bd->dgsum, (int)T_, B * 4 * H, st);
   return FHVAE_OK;
 }
 
@@ -887,7 +833,7 @@ constexpr int64_t kWgradMinK = 1024;  // shorter contractions stay on the generi
 // `wq`: long contractions that meet wgrad.hip's preconditions are appended to it instead of being launched; the caller launches
 // everything it has collected (possibly from several nets) as one grouped launch (launch_wgrad).
 template <typename T>
-static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hipStream_t st, std::vector<WgProblemT<T>>* wq = nullptr,
+static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const Ops<T>& op, hipStream_t st, std::vector<WgProblemT<T>>* wq,
                             std::vector<GemmParams>* fq = nullptr) {
   const fhvae_lstm_desc* d = &bd->f;
   const int64_t B = d->B, T_ = d->T, I = d->I, Ic = d->Ic, H = d->H;
@@ -901,7 +847,7 @@ static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hip
   int ng = 0;
   // -> true: taken by the dedicated long-K kernel (queued in wq)
   auto wgrad_long = [&](const void* a, int64_t lda, const void* b, int64_t ldb, int64_t Kc, float* c, int64_t ldc, int64_t Ncols) {
-    if (!wq || Kc < kWgradMinK) return false;
+    if (!pl.wgrad || Kc < kWgradMinK) return false;
     WgProblemT<T> w = {};
     w.A = (const T*)a, w.B = (const T*)b, w.C = c;
     w.lda = lda, w.ldb = ldb, w.ldc = ldc;
@@ -951,7 +897,7 @@ static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hip
         }
       }
     }
-    if (!(sizeof(T) == 2 && cluster_eligible(d))) {  // (the persistent backward kernels sum the bias gradients themselves)
+    if (!pl.form) {  // (the persistent backward kernels sum the bias gradients themselves)
       // layer 0 with a time-constant input: the sum over t already exists (dgsum, f32 [B,4H]): B rows instead of T*B
       if (l == 0 && Ic > 0 && bd->dgsum)
         e = launch_colsum(bd->dgsum, FHVAE_F32, G, bd->db_ih[l], bd->db_hh[l], B, G, st);
@@ -964,7 +910,7 @@ static int lstm_param_grads(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, hip
 }
 
 // d_xc[B,Ic] = dgsum[B,4H] . W_ih0[:, I:]   (f32 master weight as KM operand: B(n, k) = W[k*K0 + I + n])
-static int lstm_dxc(const fhvae_lstm_bwd_desc* bd, hipStream_t st, bool zeroed = false) {
+static int lstm_dxc(const fhvae_lstm_bwd_desc* bd, hipStream_t st, bool zeroed) {
   const fhvae_lstm_desc* d = &bd->f;
   if (!bd->d_xc || d->Ic <= 0) return FHVAE_OK;
   const int64_t G = 4 * d->H, K0 = d->I + d->Ic;
@@ -993,17 +939,17 @@ static int lstm_dxc(const fhvae_lstm_bwd_desc* bd, hipStream_t st, bool zeroed =
 
 // the recurrence (+ d_xc) and / or the parameter gradients of one net, its long contractions as one grouped launch
 template <typename T>
-static int lstm_seq_bwd_t(const fhvae_lstm_bwd_desc* bd, const Ops<T>& op, bool rec, bool par, bool dxc_zeroed, hipStream_t st) {
+static int lstm_seq_bwd_t(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const Ops<T>& op, bool rec, bool par, hipStream_t st) {
   int e;
   if (rec) {
-    e = lstm_bwd_impl<T>(bd, op, st);
+    e = lstm_bwd_impl<T>(bd, pl, op, st);
     if (e) return e;
-    e = lstm_dxc(bd, st, dxc_zeroed);
+    e = lstm_dxc(bd, st, pl.bwd_zeroes_dxc);
     if (e) return e;
   }
   if (!par) return FHVAE_OK;
   std::vector<WgProblemT<T>> wq;
-  e = lstm_param_grads<T>(bd, op, st, getenv("FHVAE_NO_WGRAD") ? nullptr : &wq);
+  e = lstm_param_grads<T>(bd, pl, op, st, &wq);
   if (e) return e;
   return launch_wgrad(wq.data(), (int)wq.size(), st);
 }
@@ -1020,9 +966,9 @@ extern "C" int fhvae_lstm_seq_bwd(const fhvae_lstm_bwd_desc* bd, void* stream) {
   const bool rec = bd->phase != 2, par = bd->phase != 1;
   if (rec && !bd->d_hs_top && !bd->d_hn) return FHVAE_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == FHVAE_F32) return lstm_seq_bwd_t<float>(bd, ops_f32(d), rec, par, false, st);
-  // (the operands were filled by the forward)
-  return lstm_seq_bwd_t<u16>(bd, ops_bf16(d), rec, par, rec && cluster_eligible(d) && cluster_bwd_zeroes_dxc(d), st);
+  const LstmPlan pl = lstm_plan(d);
+  if (d->dtype == FHVAE_F32) return lstm_seq_bwd_t<float>(bd, pl, ops_f32(d), rec, par, st);
+  return lstm_seq_bwd_t<u16>(bd, pl, ops_bf16(d), rec, par, st);  // (the operands were filled by the forward)
 }
 
 // Phase 2 (parameter gradients) of n backward passes whose recurrences (phase 1) have run: the long weight-gradient
@@ -1059,7 +1005,6 @@ extern "C" int fhvae_lstm_param_grads_multi(const fhvae_lstm_bwd_desc* const* bd
   }
   std::vector<GemmParams> fq;  // the f32 (B-row) contractions of the time-constant inputs
   std::vector<WgProblem32> wq32;  // f32 mode: the long contractions of every queued net, one grouped launch
-  const bool use_wq = !getenv("FHVAE_NO_WGRAD");
   for (int i = 0; i < n; ++i) {
     const fhvae_lstm_bwd_desc* bd = bds[i];
     FH_CHECK_PTR(bd);
@@ -1069,9 +1014,9 @@ extern "C" int fhvae_lstm_param_grads_multi(const fhvae_lstm_bwd_desc* const* bd
     FH_CHECK_PTR(bd->dgates);
     if (d->Ic > 0) FH_CHECK_PTR(bd->dgsum);
     if (d->dtype == FHVAE_F32) {
-      e = lstm_param_grads<float>(bd, ops_f32(d), st, use_wq ? &wq32 : nullptr);
+      e = lstm_param_grads<float>(bd, lstm_plan(d), ops_f32(d), st, &wq32);
     } else {
-      e = lstm_param_grads<u16>(bd, ops_bf16(d), st, use_wq ? &wq : nullptr, &fq);
+      e = lstm_param_grads<u16>(bd, lstm_plan(d), ops_bf16(d), st, &wq, &fq);
     }
     if (e) return e;
   }

@@ -32,22 +32,35 @@ struct ClusterWeights {  // bf16 operand copies in the workspace
   const u16* xc_fold;                   // (B,Ic) bf16 when the rows-form forward kernel projects the time-constant input itself
 };
 
-// whether this device / shape can run the cluster kernels (gfx950 with 256 CUs, bf16, H in {128, 256}, L <= 2, ...)
-bool cluster_eligible(const fhvae_lstm_desc* d);
-// 1: the waves of a workgroup split the cluster's rows, 2: they split the contraction (<= 32 rows per cluster)
-int cluster_form(const fhvae_lstm_desc* d);
-// the forward kernels can multiply x_t by W_ih[0][:, :I] themselves (I a multiple of 8, at most 128, rows 16-byte aligned)
-bool cluster_can_fold(const fhvae_lstm_desc* d);
-bool cluster_xc_in_kernel(const fhvae_lstm_desc* d);
-// the forward runs with register-stationary weights and saves the gates unit-major (lstm_fwd_wr.hip)
-bool cluster_fwd_wr_ok(const fhvae_lstm_desc* d);
+// The schedule of a recurrence and its variants, decided ONCE per C call from the descriptor's scalar fields, `lp != NULL`, the
+// (cached) device check and the environment: every schedule switch (FHVAE_NO_CLUSTER, _NO_FOLD, _NO_XC_FOLD, _NO_FWD_WR, _NO_RS,
+// _BIG_CELLS, _NO_WGRAD, _CLUSTER_TLOG) is read in lstm_plan and nowhere else, on every call (the tests flip them between calls).
+// Forward, backward and the size queries of the C ABI all read the same fields, so what a forward saves (gates unit-major or not,
+// ws_below, pre) is what the backward of the same descriptor and environment expects.
+struct LstmPlan {
+  int form;  // 0: one launch per wavefront step (lstm.hip); persistent (bf16, gfx950 with 256 CUs, H in {128, 256}, L <= 2, ...):
+             // 1: the waves of a workgroup split the cluster's rows, 2: they split the contraction (<= 32 rows per cluster)
+  bool big, big_shape;  // form 0: the large-tile cells (lstm_cell.hip) are wanted (FHVAE_BIG_CELLS = 0 / 1, else from about a
+                        // workgroup per CU), and the shape meets their preconditions (what remains is 16-byte alignment)
+  bool fold;            // form > 0: the forward kernels multiply x_t by W_ih[0][:, :I] themselves (I a multiple of 8, at most 128)
+  bool xc_in;           // form > 0: ... and project the time-constant input themselves (no GEMM, no (B,4H) f32 round trip)
+  bool bwd_rs;          // rows form at H = 256: the per-layer backward exchanges partial dh (lstm_bwd_rs.hip)
+  bool fwd_wr;          // ... two layers, the inputs folded: the forward with register-stationary weights (lstm_fwd_wr.hip); it
+                        // saves the gates unit-major, which the partial-dh backward then reads (gates_um of ClFwd and ClBwd)
+  bool bwd_zeroes_dxc;  // the backward recurrence leaves bd->d_xc zeroed: lstm.hip's split-K contraction into it needs no zeroing launch
+  bool needs_ws_below;  // rows form, L >= 2: the layer-by-layer backward hands the from-above gradient down through bd->ws_below
+  bool wgrad;           // the long weight-gradient contractions go to wgrad.hip's grouped launch
+  bool tlog;            // the persistent kernels log their phase clocks into the last quarter of the sync block
+  struct Geo {
+    int NU, NC;     // workgroups per cluster, clusters per launch
+    int64_t chunk;  // batch rows per launch (larger batches run as consecutive launches)
+  } fwd, bwd;       // form > 0
+};
+LstmPlan lstm_plan(const fhvae_lstm_desc* d);
+
 // the recurrence of fhvae_lstm_seq_fwd after the layer-0 input projection (d->pre filled): all T steps, all layers
-int cluster_fwd(const fhvae_lstm_desc* d, const ClusterWeights& w, hipStream_t st);
-// the backward needs fhvae_lstm_bwd_desc.ws_below
-bool cluster_needs_ws_below(const fhvae_lstm_desc* d);
-// the backward recurrence leaves bd->d_xc zeroed (lstm_bwd_rs.hip): lstm.hip's split-K contraction into it needs no zeroing launch
-bool cluster_bwd_zeroes_dxc(const fhvae_lstm_desc* d);
+int cluster_fwd(const fhvae_lstm_desc* d, const LstmPlan& pl, const ClusterWeights& w, hipStream_t st);
 // the recurrence of fhvae_lstm_seq_bwd: fills dgates (and dgsum when Ic > 0)
-int cluster_bwd(const fhvae_lstm_bwd_desc* bd, const ClusterWeights& w, hipStream_t st);
+int cluster_bwd(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const ClusterWeights& w, hipStream_t st);
 
 }  // namespace fh

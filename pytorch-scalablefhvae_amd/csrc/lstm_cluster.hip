@@ -18,7 +18,7 @@
 //     the launch's number on the sync block); a workgroup that found its XCD full would hold a ticket of the next launch, wait
 //     for flags nobody raises and end the launch through the bounded spin (status word): it never computes from a stale line;
 //   * every spin is bounded and watches the abort word: a lost workgroup ends the launch, it cannot hang the GPU.
-// Kernels (H in {128, 256}, L <= 2; chosen by rows per cluster, cluster_form):
+// Kernels (H in {128, 256}, L <= 2; chosen by rows per cluster, LstmPlan::form):
 //   lstm_fwd_cluster_kernel   forward, both layers as one wavefront, 16 units per member, 64/128 rows per cluster; every
 //                             wave stages its own rows with LDS-DMA into a private ring (no barrier in the contraction);
 //                             the layer-0 input projection folded in (W_ih[0] fragments in registers)
@@ -1226,56 +1226,6 @@ static bool device_ok() {
   return ok == 1;
 }
 
-bool cluster_eligible(const fhvae_lstm_desc* d) {
-  if (getenv("FHVAE_NO_CLUSTER")) return false;
-  if (d->dtype != FHVAE_BF16 || !d->lp) return false;
-  if (d->H != 256 && d->H != 128) return false;
-  if (d->L > 2 || d->T + d->L >= kSeqEpochs) return false;
-  if (d->B > 131072) return false;  // 32-bit byte offsets into the exchange buffer (buffer loads)
-  return device_ok();
-}
-
-// kSave = false (p.gates == NULL): the inference forward of the two kernels
-template <bool kSave, int H, int L, int RB>
-static int launch_fwd_rb(const ClFwd& p, hipStream_t st) {
-  using CF = ClFwdCfg<H, L, RB>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)lstm_fwd_cluster_kernel<H, L, RB, kSave>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((lstm_fwd_cluster_kernel<H, L, RB, kSave>), dim3(kGrid), dim3(kThreads), CF::SMEM, st, p);
-  return fh_launch_status();
-}
-
-template <bool kSave, int H, int L, int RB>
-static int launch_fwd_ks(const ClFwd& p, hipStream_t st) {
-  constexpr int SMEM = (2 * L - 1) * 64 * (H / 8) * 16 + 4 * L * 4 * 1024 + 16;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)lstm_fwd_ksplit_kernel<H, L, RB, kSave>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((lstm_fwd_ksplit_kernel<H, L, RB, kSave>), dim3(kGrid), dim3(kThreads), SMEM, st, p);
-  return fh_launch_status();
-}
-
-template <bool kSave, int H, int L>
-static int launch_fwd_save(const ClFwd& p, int RB, hipStream_t st) {
-  switch (RB) {
-    case 16: return launch_fwd_ks<kSave, H, L, 16>(p, st);
-    case 32: return launch_fwd_ks<kSave, H, L, 32>(p, st);
-    case 64: return launch_fwd_rb<kSave, H, L, 64>(p, st);
-    default: return launch_fwd_rb<kSave, H, L, 128>(p, st);
-  }
-}
-template <int H, int L>
-static int launch_fwd(const ClFwd& p, int RB, hipStream_t st) {
-  return p.gates ? launch_fwd_save<true, H, L>(p, RB, st) : launch_fwd_save<false, H, L>(p, RB, st);
-}
-
 // rows per cluster and the tile that holds them
 static void cluster_rows(int64_t nrows, int NC, int* Mc, int* RB) {
   int64_t m = (nrows + NC - 1) / NC;
@@ -1284,52 +1234,92 @@ static void cluster_rows(int64_t nrows, int NC, int* Mc, int* RB) {
   *RB = m <= 16 ? 16 : m <= 32 ? 32 : m <= 64 ? 64 : 128;
 }
 
-// the forward kernels project the time-constant input themselves (no GEMM, no (B,4H) f32 round trip)
-bool cluster_xc_in_kernel(const fhvae_lstm_desc* d) {
-  if (!(d->Ic > 0 && d->Ic % 8 == 0 && d->Ic <= 128 && d->I % 8 == 0 && (d->I == 0 || cluster_can_fold(d))) || getenv("FHVAE_NO_XC_FOLD"))
-    return false;
-  return true;
-}
-
-bool cluster_can_fold(const fhvae_lstm_desc* d) {
-  return d->I > 0 && d->I % 8 == 0 && d->I <= 128 && (d->I + d->Ic) % 8 == 0 && !getenv("FHVAE_NO_FOLD");
-}
-
-int cluster_form(const fhvae_lstm_desc* d) {
-  const int NC = kGrid / ((int)d->H / 16);
-  const int64_t chunk = (int64_t)NC * 128;
+LstmPlan lstm_plan(const fhvae_lstm_desc* d) {
+  const int64_t B = d->B, T = d->T, I = d->I, Ic = d->Ic, H = d->H;
+  LstmPlan p = {};
+  p.wgrad = !getenv("FHVAE_NO_WGRAD");
+  const bool persistent = !getenv("FHVAE_NO_CLUSTER") && d->dtype == FHVAE_BF16 && d->lp && (H == 256 || H == 128) && d->L <= 2 &&
+                          T + d->L < kSeqEpochs && B <= 131072 &&  // (B: 32-bit byte offsets into the exchange buffer, buffer loads)
+                          device_ok();
+  if (!persistent) {
+    const char* ev = getenv("FHVAE_BIG_CELLS");
+    const int want = ev ? atoi(ev) : -1, es = d->dtype == FHVAE_BF16 ? 2 : 4, epc = 16 / es;
+    // f32, whose generic cells are further from their roofline: from 256 tiles per launch
+    p.big = want >= 0 ? want != 0 : (B / 128) * (H / 64) >= (d->dtype == FHVAE_F32 ? 64 : 96);
+    p.big_shape = !(B % 128 || H % 64 || I % epc || Ic % epc) && B * 4 * H * 4 < (1LL << 31) && (int64_t)d->L * H * B * 4 < (1LL << 31) &&
+                  4 * H * (I + Ic > H ? I + Ic : H) * es < (1LL << 30);
+    return p;
+  }
+  const int NU = (int)H / 16, NC = kGrid / NU;
   int Mc, RB;
-  cluster_rows(d->B < chunk ? d->B : chunk, NC, &Mc, &RB);
-  return RB <= 32 ? 2 : 1;
+  cluster_rows(B < (int64_t)NC * 128 ? B : (int64_t)NC * 128, NC, &Mc, &RB);
+  p.form = RB <= 32 ? 2 : 1;
+  p.tlog = getenv("FHVAE_CLUSTER_TLOG") != nullptr;
+  p.fold = I > 0 && I % 8 == 0 && I <= 128 && (I + Ic) % 8 == 0 && !getenv("FHVAE_NO_FOLD");
+  p.xc_in = Ic > 0 && Ic % 8 == 0 && Ic <= 128 && I % 8 == 0 && (I == 0 || p.fold) && !getenv("FHVAE_NO_XC_FOLD");
+  p.bwd_rs = p.form == 1 && H == 256 && !getenv("FHVAE_NO_RS");
+  p.fwd_wr = p.bwd_rs && d->L == 2 && !getenv("FHVAE_NO_FWD_WR") && (I == 0 || p.fold) && (Ic == 0 || p.xc_in) &&
+             2 * T * B * H * 2 < (1LL << 31) && T * B * I * 2 < (1LL << 31) && I + Ic > 0;  // (32-bit buffer offsets)
+  p.bwd_zeroes_dxc = p.bwd_rs || p.form == 2;  // their layer-0 epilogue covers every row once
+  p.needs_ws_below = p.form == 1 && d->L >= 2;
+  // fwd_wr: 8 members with up to 64 rows; bwd_rs: 64 units per member, 32 rows; the other rows-form backward: 32 units per member
+  p.fwd = p.fwd_wr ? LstmPlan::Geo{8, kGrid / 8, (int64_t)(kGrid / 8) * 64} : LstmPlan::Geo{NU, NC, (int64_t)NC * 128};
+  const int NUb = (int)H / (p.form == 2 ? 16 : p.bwd_rs ? 64 : 32);
+  p.bwd = LstmPlan::Geo{NUb, kGrid / NUb, (int64_t)(kGrid / NUb) * (p.bwd_rs ? 32 : 128)};
+  return p;
 }
 
-static bool cluster_bwd_rs(const fhvae_lstm_desc* d);
-
-// H = 256, two layers, rows form, the inputs foldable: the forward with register-stationary weights (lstm_fwd_wr.hip).  It saves the
-// activated gates unit-major, which only the partial-dh backward reads (ClBwd::gates_um): both follow from this one predicate.
-bool cluster_fwd_wr_ok(const fhvae_lstm_desc* d) {
-  if (!cluster_bwd_rs(d) || d->L != 2 || getenv("FHVAE_NO_FWD_WR")) return false;
-  if (d->I > 0 && !cluster_can_fold(d)) return false;
-  if (d->Ic > 0 && !cluster_xc_in_kernel(d)) return false;
-  if ((int64_t)2 * d->T * d->B * d->H * 2 >= (1LL << 31) || (int64_t)d->T * d->B * d->I * 2 >= (1LL << 31)) return false;  // 32-bit buffer offsets
-  return d->I > 0 || d->Ic > 0;
+// one persistent launch of `kernel` (a workgroup per CU); its dynamic LDS limit is raised before its first launch
+template <auto kernel, class P>
+static int launch_cl(const P& p, int grid, int threads, int smem, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return (int)e;
+    attr = true;
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), smem, st, p);
+  return fh_launch_status();
 }
 
-int cluster_fwd(const fhvae_lstm_desc* d, const ClusterWeights& w, hipStream_t st) {
+// what ClFwd and ClBwd share, for the launch that starts at batch row row0; -> the tile RB that holds a cluster's rows
+template <class P>
+static int chunk_params(P& p, const fhvae_lstm_desc* d, const LstmPlan& pl, const LstmPlan::Geo& g, const ClusterWeights& w, int64_t row0) {
+  const int64_t nrows = d->B - row0 < g.chunk ? d->B - row0 : g.chunk;
+  int RB;
+  cluster_rows(nrows, g.NC, &p.Mc, &RB);
+  p.B = (int)d->B;
+  p.T = (int)d->T;
+  p.NU = g.NU;
+  p.row0 = (int)row0;
+  p.nrows = (int)nrows;
+  p.sync = (unsigned*)d->lp;
+  p.xch = w.xch;
+  p.tlog = pl.tlog ? (unsigned long long*)((char*)d->lp + FHVAE_LSTM_SYNC_BYTES * 3 / 4) : nullptr;
+  return RB;
+}
+
+// kSave = false (p.gates == NULL): the inference forward of the two kernels
+template <bool kSave, int H, int L>
+static int launch_fwd_save(const ClFwd& p, int RB, hipStream_t st) {
+  constexpr int KS_SMEM = (2 * L - 1) * 64 * (H / 8) * 16 + 4 * L * 4 * 1024 + 16;
+  switch (RB) {
+    case 16: return launch_cl<lstm_fwd_ksplit_kernel<H, L, 16, kSave>>(p, kGrid, kThreads, KS_SMEM, st);
+    case 32: return launch_cl<lstm_fwd_ksplit_kernel<H, L, 32, kSave>>(p, kGrid, kThreads, KS_SMEM, st);
+    case 64: return launch_cl<lstm_fwd_cluster_kernel<H, L, 64, kSave>>(p, kGrid, kThreads, ClFwdCfg<H, L, 64>::SMEM, st);
+    default: return launch_cl<lstm_fwd_cluster_kernel<H, L, 128, kSave>>(p, kGrid, kThreads, ClFwdCfg<H, L, 128>::SMEM, st);
+  }
+}
+template <int H, int L>
+static int launch_fwd(const ClFwd& p, int RB, hipStream_t st) {
+  return p.gates ? launch_fwd_save<true, H, L>(p, RB, st) : launch_fwd_save<false, H, L>(p, RB, st);
+}
+
+int cluster_fwd(const fhvae_lstm_desc* d, const LstmPlan& pl, const ClusterWeights& w, hipStream_t st) {
   const int H = (int)d->H, L = d->L;
-  const bool wr = cluster_fwd_wr_ok(d);
-  const int NU = wr ? 8 : H / 16, NC = kGrid / NU;
-  const int64_t chunk = (int64_t)NC * (wr ? 64 : 128);
-  for (int64_t row0 = 0; row0 < d->B; row0 += chunk) {
-    const int64_t nrows = d->B - row0 < chunk ? d->B - row0 : chunk;
+  for (int64_t row0 = 0; row0 < d->B; row0 += pl.fwd.chunk) {
     ClFwd p = {};
-    int RB;
-    cluster_rows(nrows, NC, &p.Mc, &RB);
-    p.B = (int)d->B;
-    p.T = (int)d->T;
-    p.NU = NU;
-    p.row0 = (int)row0;
-    p.nrows = (int)nrows;
+    const int RB = chunk_params(p, d, pl, pl.fwd, w, row0);
     for (int l = 0; l < L; ++l) {
       p.w_ih[l] = w.w_ih[l];
       p.w_hh[l] = w.w_hh[l];
@@ -1347,7 +1337,7 @@ int cluster_fwd(const fhvae_lstm_desc* d, const ClusterWeights& w, hipStream_t s
       p.pre = d->pre;
       p.pre_tstride = d->I > 0 ? d->B * 4 * d->H : 0;
     }
-    if (w.xc_fold) {  // (cluster_xc_in_kernel) nothing was left in d->pre: the kernel projects xc itself
+    if (w.xc_fold) {  // (LstmPlan::xc_in) nothing was left in d->pre: the kernel projects xc itself
       p.xcv = w.xc_fold;
       p.Ic = (int)d->Ic;
       p.w_ih0 = w.w_ih[0];
@@ -1362,18 +1352,15 @@ int cluster_fwd(const fhvae_lstm_desc* d, const ClusterWeights& w, hipStream_t s
     p.hs_top_f32 = d->hs_top_f32;
     p.hn = d->hn;
     p.hn_lp = (u16*)d->hn_lp;  // every persistent forward stores the bf16 copy beside hn
-    p.sync = (unsigned*)d->lp;
-    p.xch = w.xch;
-    p.tlog = getenv("FHVAE_CLUSTER_TLOG") ? (unsigned long long*)((char*)d->lp + FHVAE_LSTM_SYNC_BYTES * 3 / 4) : nullptr;
     p.il = 1;
+    p.gates_um = pl.fwd_wr;
     double fl = 0;
-    for (int l = 0; l < L; ++l) fl += 2.0 * nrows * 4 * H * ((l > 0 ? d->T * H : 0) + (d->T - 1) * (double)H);
+    for (int l = 0; l < L; ++l) fl += 2.0 * p.nrows * 4 * H * ((l > 0 ? d->T * H : 0) + (d->T - 1) * (double)H);
     const int ts = trace_begin(st, kTraceFwdCell, fl);
     int e;
-    if (wr) {
-      p.gates_um = 1;
+    if (pl.fwd_wr)
       e = cluster_fwd_wr(p, st);
-    } else if (H == 256)
+    else if (H == 256)
       e = L == 1 ? launch_fwd<256, 1>(p, RB, st) : launch_fwd<256, 2>(p, RB, st);
     else
       e = L == 1 ? launch_fwd<128, 1>(p, RB, st) : launch_fwd<128, 2>(p, RB, st);
@@ -1383,42 +1370,18 @@ int cluster_fwd(const fhvae_lstm_desc* d, const ClusterWeights& w, hipStream_t s
   return FHVAE_OK;
 }
 
-template <int H, int L, int RB>
-static int launch_bwd_ks(const ClBwd& p, hipStream_t st) {
-  constexpr int SMEM = (2 * L - 1) * 16 * (4 * H / 8) * 16 + 4 * L * 1024 + 16;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)lstm_bwd_ksplit_kernel<H, L, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((lstm_bwd_ksplit_kernel<H, L, RB>), dim3(kGrid), dim3(kThreads), SMEM, st, p);
-  return fh_launch_status();
-}
-
 template <int H, int L>
 static int launch_bwd(const ClBwd& p, int RB, hipStream_t st) {
-  return RB <= 16 ? launch_bwd_ks<H, L, 16>(p, st) : launch_bwd_ks<H, L, 32>(p, st);
+  constexpr int SMEM = (2 * L - 1) * 16 * (4 * H / 8) * 16 + 4 * L * 1024 + 16;
+  return RB <= 16 ? launch_cl<lstm_bwd_ksplit_kernel<H, L, 16>>(p, kGrid, kThreads, SMEM, st)
+                  : launch_cl<lstm_bwd_ksplit_kernel<H, L, 32>>(p, kGrid, kThreads, SMEM, st);
 }
 
 template <int H, int RB>
 static int launch_bwd_layer(const ClBwd& p, hipStream_t st) {
   using CF = ClLayerCfg<H, RB, 32>;
   constexpr bool HW = RB <= 64 && CF::SMEM_HW <= 163840;  // helper wave where its operand buffer fits
-  constexpr int SMEM = HW ? CF::SMEM_HW : CF::SMEM;
-  const bool hw = HW;
-  static bool attr[2] = {false, false};
-  if (!attr[hw]) {
-    hipError_t e = hw ? hipFuncSetAttribute((const void*)lstm_bwd_layer_kernel<H, RB, 32, HW>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM)
-                      : hipFuncSetAttribute((const void*)lstm_bwd_layer_kernel<H, RB, 32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr[hw] = true;
-  }
-  if (hw)
-    hipLaunchKernelGGL((lstm_bwd_layer_kernel<H, RB, 32, HW>), dim3(kGrid), dim3(kThreads + 64), SMEM, st, p);
-  else
-    hipLaunchKernelGGL((lstm_bwd_layer_kernel<H, RB, 32, false>), dim3(kGrid), dim3(kThreads), CF::SMEM, st, p);
-  return fh_launch_status();
+  return launch_cl<lstm_bwd_layer_kernel<H, RB, 32, HW>>(p, kGrid, HW ? kThreads + 64 : kThreads, HW ? CF::SMEM_HW : CF::SMEM, st);
 }
 template <int H>
 static int launch_bwd_layer_rb(const ClBwd& p, int RB, hipStream_t st) {
@@ -1430,24 +1393,15 @@ static int launch_bwd_layer_rb(const ClBwd& p, int RB, hipStream_t st) {
   }
 }
 
-
-// H = 256, rows form: the per-layer backward exchanges partial dh (lstm_bwd_rs.hip)
-static bool cluster_bwd_rs(const fhvae_lstm_desc* d) {
-  return cluster_eligible(d) && cluster_form(d) == 1 && d->H == 256 && !getenv("FHVAE_NO_RS");
-}
-
 // rows form, layer by layer: the top layer's recurrence as one persistent launch, then for every layer below the from-above term
 // dg^{l+1} . W_ih[l+1] of ALL steps as one GEMM into bd->ws_below (it is not recurrent), then that layer's launch with it as the
 // external gradient.  H = 256: 64 units per member, partial-dh exchange (lstm_bwd_rs.hip, 2048 rows per launch, larger batches
 // as consecutive launches) and the projection kernel (proj.hip); else 32 units per member, dg exchanged, generic engine.
-static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const ClusterWeights& w, hipStream_t st) {
+static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const ClusterWeights& w, hipStream_t st) {
   const fhvae_lstm_desc* d = &bd->f;
   const int H = (int)d->H, L = d->L;
-  const bool rs = cluster_bwd_rs(d);
-  const int HU = rs ? 64 : 32;
-  const int NU = H / HU, NC = kGrid / NU;
+  const bool rs = pl.bwd_rs;
   const int64_t B = d->B, T = d->T, G = 4 * H;
-  const int64_t chunk = (int64_t)NC * (rs ? 32 : 128);
   for (int l = L - 1; l >= 0; --l) {
     if (l < L - 1) {  // ws_below[T*B, H] = dg^{l+1} [T*B, 4H] . W_ih[l+1]  (its transposed bf16 copy [H,4H] is the K-contiguous operand)
       const u16* dg_up = (const u16*)bd->dgates + (int64_t)(l + 1) * T * B * G;
@@ -1466,16 +1420,9 @@ static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const ClusterWeight
       }
       if (e) return e;
     }
-    for (int64_t row0 = 0; row0 < B; row0 += chunk) {
-      const int64_t nrows = B - row0 < chunk ? B - row0 : chunk;
+    for (int64_t row0 = 0; row0 < B; row0 += pl.bwd.chunk) {
       ClBwd p = {};
-      int RB;
-      cluster_rows(nrows, NC, &p.Mc, &RB);
-      p.B = (int)B;
-      p.T = (int)T;
-      p.NU = NU;
-      p.row0 = (int)row0;
-      p.nrows = (int)nrows;
+      const int RB = chunk_params(p, d, pl, pl.bwd, w, row0);
       p.w_hh_t[0] = w.w_hh_t[l];
       p.gates = (const u16*)d->gates + (int64_t)l * T * B * G;
       p.cs = d->cs + (int64_t)l * T * B * H;
@@ -1486,14 +1433,11 @@ static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const ClusterWeight
       p.dgsum = (l == 0 && d->Ic > 0) ? bd->dgsum : nullptr;
       p.db_ih[0] = bd->db_ih[l];
       p.db_hh[0] = bd->db_hh[l];
-      p.sync = (unsigned*)d->lp;
-      p.xch = w.xch;
-      p.tlog = getenv("FHVAE_CLUSTER_TLOG") ? (unsigned long long*)((char*)d->lp + FHVAE_LSTM_SYNC_BYTES * 3 / 4) : nullptr;
       p.tlog_slot = l == L - 1;
       p.nt = 1;  // streaming hints on its once-read operands: HBM reads 202 -> 175 MB per launch (1.04x algorithmic), 0.5 % of a step
-      p.gates_um = cluster_fwd_wr_ok(d) ? 1 : 0;  // the forward on this workspace saved the gates unit-major (same predicate)
-      if (rs && l == 0 && bd->d_xc && d->Ic > 0) p.d_xc_zero = bd->d_xc, p.Ic = (int)d->Ic;  // (cluster_bwd_zeroes_dxc)
-      const int ts = trace_begin(st, kTraceBwdCell, 2.0 * nrows * H * (T - 1) * 4.0 * H);
+      p.gates_um = pl.fwd_wr;
+      if (rs && l == 0 && bd->d_xc && d->Ic > 0) p.d_xc_zero = bd->d_xc, p.Ic = (int)d->Ic;  // (LstmPlan::bwd_zeroes_dxc)
+      const int ts = trace_begin(st, kTraceBwdCell, 2.0 * p.nrows * H * (T - 1) * 4.0 * H);
       const int e = rs ? cluster_bwd_layer_rs(p, st) : (H == 256 ? launch_bwd_layer_rb<256>(p, RB, st) : launch_bwd_layer_rb<128>(p, RB, st));
       trace_end(st, ts);
       if (e) return e;
@@ -1502,33 +1446,16 @@ static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const ClusterWeight
   return FHVAE_OK;
 }
 
-// the partial-dh backward and the contraction-split backward clear d_xc themselves (their layer-0 epilogue covers every row once)
-bool cluster_bwd_zeroes_dxc(const fhvae_lstm_desc* d) { return cluster_bwd_rs(d) || cluster_form(d) == 2; }
-
-// the layer-by-layer backward (rows form, two layers or more) hands the from-above gradient to the lower layer through
-// bd->ws_below (T,B,H) f32
-bool cluster_needs_ws_below(const fhvae_lstm_desc* d) { return cluster_eligible(d) && cluster_form(d) == 1 && d->L >= 2; }
-
-int cluster_bwd(const fhvae_lstm_bwd_desc* bd, const ClusterWeights& w, hipStream_t st) {
+int cluster_bwd(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, const ClusterWeights& w, hipStream_t st) {
   const fhvae_lstm_desc* d = &bd->f;
   const int H = (int)d->H, L = d->L;
-  if (cluster_form(d) == 1) {
-    if (cluster_needs_ws_below(d) && !bd->ws_below) return FHVAE_ERR_NULL;  // (fhvae_lstm_ws_below_elems says when)
-    return cluster_bwd_layers(bd, w, st);
+  if (pl.form == 1) {
+    if (pl.needs_ws_below && !bd->ws_below) return FHVAE_ERR_NULL;  // (fhvae_lstm_ws_below_elems says when)
+    return cluster_bwd_layers(bd, pl, w, st);
   }
-
-  const int NU = H / 16, NC = kGrid / NU;
-  const int64_t chunk = (int64_t)NC * 128;
-  for (int64_t row0 = 0; row0 < d->B; row0 += chunk) {
-    const int64_t nrows = d->B - row0 < chunk ? d->B - row0 : chunk;
+  for (int64_t row0 = 0; row0 < d->B; row0 += pl.bwd.chunk) {
     ClBwd p = {};
-    int RB;
-    cluster_rows(nrows, NC, &p.Mc, &RB);
-    p.B = (int)d->B;
-    p.T = (int)d->T;
-    p.NU = NU;
-    p.row0 = (int)row0;
-    p.nrows = (int)nrows;
+    const int RB = chunk_params(p, d, pl, pl.bwd, w, row0);
     for (int l = 0; l < L; ++l) {
       p.w_ih_t[l] = w.w_ih_t[l];
       p.w_hh_t[l] = w.w_hh_t[l];
@@ -1540,13 +1467,10 @@ int cluster_bwd(const fhvae_lstm_bwd_desc* bd, const ClusterWeights& w, hipStrea
     p.hn_ld = L * H;
     p.dg = (u16*)bd->dgates;
     p.dgsum = d->Ic > 0 ? bd->dgsum : nullptr;
-    if (bd->d_xc && d->Ic > 0) p.d_xc_zero = bd->d_xc, p.Ic = (int)d->Ic;  // (cluster_bwd_zeroes_dxc)
+    if (bd->d_xc && d->Ic > 0) p.d_xc_zero = bd->d_xc, p.Ic = (int)d->Ic;  // (LstmPlan::bwd_zeroes_dxc)
     for (int l = 0; l < L; ++l) p.db_ih[l] = bd->db_ih[l], p.db_hh[l] = bd->db_hh[l];
-    p.sync = (unsigned*)d->lp;
-    p.xch = w.xch;
-    p.tlog = getenv("FHVAE_CLUSTER_TLOG") ? (unsigned long long*)((char*)d->lp + FHVAE_LSTM_SYNC_BYTES * 3 / 4) : nullptr;
     double fl = 0;
-    for (int l = 0; l < L; ++l) fl += 2.0 * nrows * H * ((l < L - 1 ? d->T * 4.0 * H : 0) + (d->T - 1) * 4.0 * H);
+    for (int l = 0; l < L; ++l) fl += 2.0 * p.nrows * H * ((l < L - 1 ? d->T * 4.0 * H : 0) + (d->T - 1) * 4.0 * H);
     const int ts = trace_begin(st, kTraceBwdCell, fl);
     int e;
     if (H == 256)
