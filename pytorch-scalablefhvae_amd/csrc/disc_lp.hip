@@ -1,5 +1,5 @@
 // disc_lp.hip -- K5 (simple_fhvae.py:119-122) for the bf16 compute mode: the structure of disc_mfma.hip with both products on
-// v_mfma_f32_16x16x32_bf16 and SPLIT operands.
+// v_mfma_f32_16x16x32_bf16 and SPLIT operands.  The arithmetic around the products is disc_tile.h's, shared with that kernel.
 //
 //   q.t = q_hi.t_hi + q_hi.t_lo + q_lo.t_hi   (v = v_hi + v_lo, v_hi = bf16(v), v_lo = bf16(v - v_hi): 16 mantissa bits each)
 //
@@ -7,7 +7,7 @@
 // 8 v_mfma_f32_16x16x4_f32 (256 cycles) of the f32 kernel, at an error of ~2^-16 |q||t| on the cross term (the norms are exact
 // f32), i.e. ~1e-3 absolute on a logit at N(0,1)-scale vectors: below the bf16 tolerance of everything upstream (z2_mu itself
 // comes out of bf16 LSTM nets), and the one logit that matters when training converges -- the query's own row -- is not
-// computed here at all (masked; the callers take it in the direct f32 form, see disc_mfma.hip).
+// computed here at all (masked; the callers take it in the direct f32 form, see disc_tile.h).
 // The second product G = sum_y w[y,x] Y[y] (both backward passes) takes w in bf16 and Y split: G = Y_hi^T.w + Y_lo^T.w, with the
 // weight sum W accumulated from the SAME rounded w, so that the gradient 2c (G - x W) = 2c sum w' (y - x) keeps the small
 // differences (y - x) of near rows (a W from unrounded w would leave sum (w' - w) y, ~0.4 % of |y|, in it).
@@ -16,7 +16,7 @@
 // accumulator registers, so w never leaves registers here either.
 // MFMA cycles per (32 streamed x 16 stationary) block: 6 + 4 = 10 x 16 against 2 x (8 + 8) x 32 in the f32 kernel: the kernel
 // is bound by the exp / weight arithmetic on the VALU instead.
-#include "disc_mfma.h"
+#include "disc_tile.h"
 
 #include <type_traits>
 
@@ -71,7 +71,7 @@ __device__ __forceinline__ bf16x8 frag_t(const char* img, int row0, int dj, int 
 // rounded weights.  Each wave leaves its partial tiles in an LDS slot of its own; the four slots are summed after each 64-row tile.
 // No global atomics in this mode (the chip retires ~70 G f32 atomics/s: (B/256) S D of them would cost more than the second
 // pass they replace): both sides leave PARTIALS with plain stores -- G[chunk][x][d] and G2[x-tile][y][d], WY[x-tile][y] -- and
-// two small kernels (disc_mfma.hip) reduce them: dq = sum over chunks; dtable += 2c (sum G2 - t_y sum WY).
+// two small kernels (disc.hip) reduce them: dq = sum over chunks; dtable += 2c (sum G2 - t_y sum WY).
 constexpr int kDtLd = 36;  // row stride of the LDS accumulator (floats): rows 4 apart fall into different banks
 template <int MODE, bool XQ>
 __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
@@ -88,8 +88,7 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
   __shared__ int yown[kYT / 32][4];  // !XQ: wave w staged a query of block b whose target is one of this workgroup's rows
   // backward epilogue: the transpose buffer tr[256][D + 1]; MODE 2, inside the loop: one [64 y][kDtLd] slot per wave for its
   // partial of the streamed side's product (plain writes; LDS float atomics from 8 waves cost more than the second pass did)
-  constexpr int kRed = !BW ? 1 : (BOTH && 4 * kYT * kDtLd > 256 * (kD + 1) ? 4 * kYT * kDtLd : 256 * (kD + 1));
-  __shared__ __attribute__((aligned(16))) float red[kRed];
+  __shared__ __attribute__((aligned(16))) float red[dt::red_floats(kD, MODE, kDtLd)];
   float (*tr)[kD + 1] = (float (*)[kD + 1]) red;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,21 +120,7 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
     nrm += __shfl_xor(nrm, 32, 64);
     xn[t] = nrm;
     split8(v, xh[t], xl[t]);
-    xmax[t] = 0.f;
-    xinv[t] = 0.f;
-    xtgt[t] = -1;
-    if (XQ) {
-      if (ok) {
-        const int64_t tg = a.idx[x] - a.row0;
-        xtgt[t] = (tg >= 0 && tg < a.NY) ? (int)tg : -1;
-        if (BW) {
-          xmax[t] = a.rmax[x];
-          xinv[t] = gscale / a.rsum[x];  // (the upstream scale rides on the normaliser)
-        }
-      }
-    } else {
-      xtgt[t] = ok ? x : -2;  // table row index: a streamed query hits it when its target == x
-    }
+    dt::x_scalars<BW>(a, XQ, x, ok, gscale, xmax[t], xinv[t], xtgt[t]);
   }
 
   // MODE 2: B fragments of the streamed side's product: k = x in frag_t's order (rows 4g..4g+3 and 16+4g..16+4g+3 of the
@@ -207,19 +192,7 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
       bool mine = false;  // (!XQ) this query's own row is among the workgroup's stationary rows
       if (c4 == 0) {
         yn[row] = nrm;
-        if (!XQ) {  // streamed queries: their (max, scale/sum, target)
-          const int y = y0 + row;
-          const bool ok = y < y_end;
-          ymax[row] = ok && MODE == 1 ? a.rmax[y] : 0.f;
-          yinv[row] = ok && MODE == 1 ? gscale / a.rsum[y] : 0.f;
-          int tg = -3;
-          if (ok) {
-            const int64_t vv = a.idx[y] - a.row0;
-            tg = (vv >= 0 && vv < a.NX) ? (int)vv : -3;
-          }
-          ytgt[row] = tg;
-          mine = tg >= (int)blockIdx.y * 256 && tg < (int)blockIdx.y * 256 + 256;
-        }
+        if (!XQ) mine = dt::y_scalars<MODE>(a, y0 + row, y_end, gscale, ymax[row], yinv[row], ytgt[row]);
       }
       if (!XQ) {  // pass p stages the 32 rows of block p, 8 per wave
         const bool any = __any(mine);
@@ -277,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
         constexpr bool MASKED = decltype(masked_c)::value;
         const bool xok = x0 + t * 16 + i < a.NX;
         const float cxn = a.c * xn[t];
-        float w8[8];
+        float w8[2][4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -285,38 +258,23 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[h], xl[t], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[h], xh[t], acc, 0, 0, 0);
           float lg[4];
+          // (the logits and their masks stand in both kernels: as a shared piece of disc_tile.h they cost disc_lp_kernel<1, true> 13
+          // registers, 193 -> 206, and the two-pass backward 1.5 %: B = 2048, S = 100000 0.294 -> 0.299 ms)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             lg[r] = c2 * acc[r] - (a.c * ynr[h][r] + cxn);
             if constexpr (MASKED) {
               const int y = yb + h * 16 + 4 * g + r;
               if (!(xok && y < y_end)) lg[r] = -INFINITY;
-              // the query's own row is handled exactly by the callers (disc_mfma.hip)
+              // the query's own row is handled exactly by the callers (disc_tile.h)
               const bool own = (MODE == 1 && !XQ) ? ytg[h][r] == xtgt[t] : xtgt[t] == y;
               if (own) lg[r] = -INFINITY;
             }
           }
-          if constexpr (MODE == 0) {
-            const float gm = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-            if (gm > m[t]) {
-              ssum[t] *= __expf(m[t] - gm);
-              m[t] = gm;
-            }
-            if (!MASKED || m[t] > -INFINITY) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) ssum[t] += __expf(lg[r] - m[t]);
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float p;
-              if (XQ)
-                p = __expf(lg[r] - xmax[t]) * xinv[t];
-              else
-                p = __expf(lg[r] - ymx[h][r]) * yiv[h][r];
-              w8[h * 4 + r] = (!MASKED || lg[r] > -INFINITY) ? p : 0.f;
-            }
-          }
+          if constexpr (MODE == 0)
+            dt::lse_update<MASKED>(lg, m[t], ssum[t]);
+          else
+            dt::weights<MASKED>(w8[h], lg, XQ, xmax[t], xinv[t], ymx[h], yiv[h]);
         }
         if constexpr (BW) {
           // w in bf16 (k-slot 8g + j <-> row 4g + j of the first, 16 + 4g + (j - 4) of the second tile: the order of frag_t);
@@ -327,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
           } wb;
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            wb.h[k] = f2bf(w8[k]);
+            wb.h[k] = f2bf(w8[k >> 2][k & 3]);
             wsum[t] += bf2f(wb.h[k]);
           }
 #pragma unroll
@@ -390,36 +348,15 @@ __global__ __launch_bounds__(256, 2) void disc_lp_kernel(DiscMfmaArgs a) {
       }
     }
     __syncthreads();
-    if constexpr (BOTH) {  // the tile's four slots summed: plain stores into this x-tile's slice of the partial buffer (every
-                           // (x-tile, y) is written exactly once); the next tile's slot writes are behind its staging barrier
-      for (int e = tid; e < kYT * kD; e += 256) {
-        const int row = e / kD, d = e % kD, o = row * kDtLd + d;
-        if (y0 + row < y_end)
-          a.G2[((int64_t)blockIdx.y * a.NY + y0 + row) * kD + d] =
-              (red[o] + red[kYT * kDtLd + o]) + (red[2 * kYT * kDtLd + o] + red[3 * kYT * kDtLd + o]);
-      }
-      if (tid < kYT && y0 + tid < y_end)
-        a.WY[(int64_t)blockIdx.y * a.NY + y0 + tid] = (wy_lds[0][tid] + wy_lds[1][tid]) + (wy_lds[2][tid] + wy_lds[3][tid]);
-    }
+    if constexpr (BOTH) dt::flush_slots<kD, kDtLd>(a, red, wy_lds, y0, y_end);
   }
 
   if constexpr (MODE == 0) {
-    // merge the 4 lane groups that share a stationary vector, then one partial per (chunk, x)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float mm = m[t], ss = ssum[t];
-#pragma unroll
-      for (int o = 16; o <= 32; o <<= 1) {
-        const float om = __shfl_xor(mm, o, 64), os = __shfl_xor(ss, o, 64);
-        const float nm = fmaxf(mm, om);
-        ss = (nm == -INFINITY) ? 0.f : ss * __expf(mm - nm) + os * __expf(om - nm);
-        mm = nm;
-      }
-      const int x = x0 + t * 16 + i;
-      if (g == 0 && x < a.NX) a.part[(int64_t)blockIdx.x * a.NX + x] = make_float2(mm, ss);
-    }
+    dt::fwd_epilogue(a, m, ssum, x0);
   } else {
     if constexpr (BOTH) __syncthreads();  // (tr shares its memory with the slots the last tile's sums were read from)
+    // (the backward epilogue stands in both kernels: as a shared piece of disc_tile.h it cost this kernel's two-pass backward 0.4 %,
+    // B = 2048, S = 100000: 0.2956 -> 0.2968 ms against a run-to-run spread of 0.0002, with no register or scratch change to show for it)
     // grad_x = 2c (G - X W); lane holds G[x = 16t+i][d = 16dj + 4g + reg]; transpose through LDS -> row-contiguous atomics
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

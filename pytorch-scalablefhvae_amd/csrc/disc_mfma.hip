@@ -5,7 +5,7 @@
 // The cross term q.t is a (B x S x D) contraction: it runs on exact-f32 MFMA (v_mfma_f32_16x16x4_f32: every product
 // and every accumulation step is an f32 fma, so the expanded form costs only the cancellation of the norms, ~1e-5
 // absolute on logits of 10..1000), and the exp / online log-sum-exp runs on the VALU under it (separate pipes).
-// The VALU kernels in loss.hip spend 2*D lane-instructions per (query,row) pair on the distance alone.
+// The VALU kernels in disc.hip spend 2*D lane-instructions per (query,row) pair on the distance alone.
 //
 // One kernel template, three uses.  A workgroup keeps 256 STATIONARY vectors X (64 per wave, as MFMA B-operand
 // fragments in registers) and streams the other set Y through LDS in tiles of 64 (the pieces of allpairs_f32.h, in a loop of
@@ -16,24 +16,20 @@
 // with w = g (softmax - onehot) recomputed from the per-query (max, sumexp) of the forward.  The logit tile comes out
 // of the MFMA with the stationary index on the lanes (col = lane&15) and the streamed index in the 4 accumulator
 // registers (row = 4*(lane>>4)+r): exactly the B-operand layout of the second product, so w never leaves registers.
-#include <algorithm>
-
+// This file holds the kernel and its launch (disc_f32_launch); the arithmetic around the products is disc_tile.h's, shared with the
+// bf16 kernel of disc_lp.hip; the engine choice, the grids, the workspaces and the reduce kernels are disc.hip's.
 #include "allpairs_f32.h"
-#include "disc_mfma.h"
+#include "disc_tile.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace fh {
 
+namespace {
+
 using ap::yoff;
 
-// The (query, own table row) pairs are NOT computed here.  The expanded form's absolute error ~1e-7 * 2c (|q|^2 + |t|^2) is
-// harmless on far rows (their softmax weight is 0 either way) but it is the whole signal on the pair training drives together
-// (q -> table[idx]).  That one logit per query is therefore masked out of these kernels (logit = -inf: no contribution to the
-// log-sum-exp, zero weight in both backward passes) and taken in the DIRECT form -c |q - t|^2 by the callers: the forward's
-// combine kernel merges exp(target - max) into the row sum, the backward adds the pair's gradient in disc_own_bwd_kernel
-// (loss.hip).  CE -> log(1 + sum_others) and p_target - 1 -> -sum_others then come out cleanly however large the norms are.
+// (The (query, own table row) pairs are masked out here and taken in the direct form by the callers: disc_tile.h.)
 template <int D, int MODE>
 __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   constexpr int CHN = D / 4;   // 16-byte chunks per vector
@@ -48,14 +44,13 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   // bf16 form and the reasoning): G2[y][d] = sum_x w[y,x] X[x][d] contracts over x, which sits on the lanes of the logit tile, so
   // each wave passes its weights through a private [16 y][64 x] f32 LDS image (4 ds_write_b32 per tile, one ds_read_b128 back:
   // lane (g, i) gets w[y = i][x = 16t + 4g .. + 3], the A operands of the 4 MFMAs of tile t); B = X[x0 + 16t + 4g + q][16dj + i].  WY[y] = sum_x w[y,x] is summed on the VALU from the same transposed registers.  Per-wave LDS slots,
-  // partial buffers and the two reduce kernels below instead of atomics.
+  // partial buffers and the two reduce kernels of disc.hip instead of atomics.
   constexpr bool BW = MODE >= 1, BOTH = MODE == 2;
   constexpr int kWLd = 68;        // row stride of the weight image (floats): the 4 lane groups write different banks
   constexpr int kDtLd = D + 4;    // row stride of a slot
   __shared__ __attribute__((aligned(16))) float wimg[BOTH ? 4 : 1][BOTH ? 16 * kWLd : 4];
   __shared__ float wy_lds[BOTH ? 4 : 1][BOTH ? YT : 1];
-  constexpr int kRed = !BW ? 1 : (BOTH && 4 * YT * kDtLd > 256 * (D + 1) ? 4 * YT * kDtLd : 256 * (D + 1));
-  __shared__ __attribute__((aligned(16))) float red[kRed];  // epilogue: tr[256][D + 1]; MODE 2, in the loop: 4 slots [64 y][kDtLd]
+  __shared__ __attribute__((aligned(16))) float red[dt::red_floats(D, MODE, kDtLd)];  // epilogue: tr; MODE 2, in the loop: 4 slots
   float (*tr)[D + 1] = (float (*)[D + 1]) red;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -88,21 +83,7 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
     nrm += __shfl_xor(nrm, 16, 64);
     nrm += __shfl_xor(nrm, 32, 64);
     xn[t] = nrm;
-    xmax[t] = 0.f;
-    xinv[t] = 0.f;
-    xtgt[t] = -1;
-    if (a.x_is_query) {
-      if (ok) {
-        const int64_t tg = a.idx[x] - a.row0;
-        xtgt[t] = (tg >= 0 && tg < a.NY) ? (int)tg : -1;
-        if (BW) {
-          xmax[t] = a.rmax[x];
-          xinv[t] = gscale / a.rsum[x];  // (the upstream scale rides on the normaliser)
-        }
-      }
-    } else {
-      xtgt[t] = ok ? x : -2;  // table row index: a streamed query hits it when its target == x
-    }
+    dt::x_scalars<BW>(a, a.x_is_query, x, ok, gscale, xmax[t], xinv[t], xtgt[t]);
   }
   float m[4], ssum[4], wsum[4];
   f32x4 gacc[4][NJ];
@@ -137,19 +118,7 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
       bool mine = false;
       if (part == 0) {
         yn[row] = nrm;
-        const int y = y0 + row;
-        if (!a.x_is_query) {
-          const bool ok = y < y_end;
-          ymax[row] = ok && MODE == 1 ? a.rmax[y] : 0.f;
-          yinv[row] = ok && MODE == 1 ? gscale / a.rsum[y] : 0.f;  // (the upstream scale rides on the normaliser)
-          int tg = -3;
-          if (ok) {
-            const int64_t v = a.idx[y] - a.row0;
-            tg = (v >= 0 && v < a.NX) ? (int)v : -3;
-          }
-          ytgt[row] = tg;
-          mine = tg >= (int)blockIdx.y * 256 && tg < (int)blockIdx.y * 256 + 256;
-        }
+        if (!a.x_is_query) mine = dt::y_scalars<MODE>(a, y0 + row, y_end, gscale, ymax[row], yinv[row], ytgt[row]);
       }
       {  // wave w holds the 16 rows of block w
         const bool any = __any(mine);
@@ -198,38 +167,23 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
         const float cxn = a.c * xn[t];
         float lg[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int r = 0; r < 4; ++r) {  // (the same text as in disc_lp.hip, see there)
           lg[r] = c2 * acc[r] - (a.c * ynr[r] + cxn);
           if constexpr (MASKED) {
             const int y = ybase + 4 * g + r;
             if (!(xok && y < y_end)) lg[r] = -INFINITY;
-            // the query's own row is handled exactly by the callers (see the note above the kernel)
+            // the query's own row is handled exactly by the callers (disc_tile.h)
             const bool own = (MODE == 1 && !a.x_is_query) ? ytg[r] == xtgt[t] : xtgt[t] == y;
             if (own) lg[r] = -INFINITY;
           }
         }
         if constexpr (MODE == 0) {
-          const float gm = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
-          if (gm > m[t]) {
-            ssum[t] *= __expf(m[t] - gm);
-            m[t] = gm;
-          }
-          if (!MASKED || m[t] > -INFINITY) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ssum[t] += __expf(lg[r] - m[t]);
-          }
+          dt::lse_update<MASKED>(lg, m[t], ssum[t]);
         } else {
           float w[4];
+          dt::weights<MASKED>(w, lg, a.x_is_query, xmax[t], xinv[t], ymx, yiv);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float p;
-            if (a.x_is_query)
-              p = __expf(lg[r] - xmax[t]) * xinv[t];
-            else
-              p = __expf(lg[r] - ymx[r]) * yiv[r];
-            w[r] = (!MASKED || lg[r] > -INFINITY) ? p : 0.f;  // (own pairs: masked above, added by disc_own_bwd_kernel)
-            wsum[t] += w[r];
-          }
+          for (int r = 0; r < 4; ++r) wsum[t] += w[r];
           float xb[BOTH ? 4 : 1][NJ];  // MODE 2: requested behind the exp arithmetic; their latency hides under the G product's MFMAs
           if constexpr (BOTH) {
 #pragma unroll
@@ -305,35 +259,14 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
       }
     }
     __syncthreads();
-    if constexpr (BOTH) {  // the tile's four slots summed into this x-tile's slice of the partial buffers (plain stores)
-      for (int e = tid; e < YT * D; e += 256) {
-        const int row = e / D, d = e % D, o = row * kDtLd + d;
-        if (y0 + row < y_end)
-          a.G2[((int64_t)blockIdx.y * a.NY + y0 + row) * D + d] =
-              (red[o] + red[YT * kDtLd + o]) + (red[2 * YT * kDtLd + o] + red[3 * YT * kDtLd + o]);
-      }
-      if (tid < YT && y0 + tid < y_end)
-        a.WY[(int64_t)blockIdx.y * a.NY + y0 + tid] = (wy_lds[0][tid] + wy_lds[1][tid]) + (wy_lds[2][tid] + wy_lds[3][tid]);
-    }
+    if constexpr (BOTH) dt::flush_slots<D, kDtLd>(a, red, wy_lds, y0, y_end);
   }
 
   if constexpr (MODE == 0) {
-    // merge the 4 lane groups that share a stationary vector, then one partial per (chunk, x)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float mm = m[t], ss = ssum[t];
-#pragma unroll
-      for (int o = 16; o <= 32; o <<= 1) {
-        const float om = __shfl_xor(mm, o, 64), os = __shfl_xor(ss, o, 64);
-        const float nm = fmaxf(mm, om);
-        ss = (nm == -INFINITY) ? 0.f : ss * __expf(mm - nm) + os * __expf(om - nm);
-        mm = nm;
-      }
-      const int x = x0 + t * 16 + i;
-      if (g == 0 && x < a.NX) a.part[(int64_t)blockIdx.x * a.NX + x] = make_float2(mm, ss);
-    }
+    dt::fwd_epilogue(a, m, ssum, x0);
   } else {
     if constexpr (BOTH) __syncthreads();  // (tr shares its memory with the slots the last tile's sums were read from)
+    // (the same text as in disc_lp.hip, see there)
     // grad_x = 2c (G - X W); lane holds G[x = 16t+i][d = 16dj + 4g + reg]; transpose through LDS -> row-contiguous atomics
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -347,8 +280,7 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
         if (x < a.NX) xv = *(const float4*)(a.X + (int64_t)x * D + dj * 16 + 4 * g);
         const float xr[4] = {xv.x, xv.y, xv.z, xv.w};
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          tr[wave * 64 + t * 16 + i][dj * 16 + 4 * g + r] = 2.f * a.c * (gacc[t][dj][r] - xr[r] * ws);
+        for (int r = 0; r < 4; ++r) tr[wave * 64 + t * 16 + i][dj * 16 + 4 * g + r] = 2.f * a.c * (gacc[t][dj][r] - xr[r] * ws);
       }
     }
     __syncthreads();
@@ -365,182 +297,23 @@ __global__ __launch_bounds__(256, 2) void disc_mfma_kernel(DiscMfmaArgs a) {
   }
 }
 
-// the reductions of the one-pass backward's partials (disc_lp.hip, MODE 2)
-// dY[y][d] += 2c (sum_xt G2[xt][y][d] - Y[y][d] sum_xt WY[xt][y])
-__global__ void disc_dt_finish_kernel(float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ g2,
-                                      const float* __restrict__ wy, int nxt, float c2, int64_t NY, int D) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NY * D) return;
-  const int64_t row = i / D;
-  float sg = 0.f, sw = 0.f;
-  for (int t = 0; t < nxt; ++t) {
-    sg += g2[(int64_t)t * NY * D + i];
-    sw += wy[(int64_t)t * NY + row];
-  }
-  dy[i] += c2 * (sg - y[i] * sw);
-}
-// dX[i] = sum_chunks G[chunk][i]
-__global__ void disc_dq_reduce_kernel(float* __restrict__ dx, const float* __restrict__ g, int nchunks, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int c = 0;
-  for (; c + 4 <= nchunks; c += 4) {
-    a0 += g[(int64_t)c * n + i], a1 += g[(int64_t)(c + 1) * n + i], a2 += g[(int64_t)(c + 2) * n + i], a3 += g[(int64_t)(c + 3) * n + i];
-  }
-  for (; c < nchunks; ++c) a0 += g[(int64_t)c * n + i];
-  dx[i] = (a0 + a1) + (a2 + a3);
-}
-
-// streamed vectors per workgroup for about `target` workgroups.  Forward (one partial per (chunk, x)): 1024.  Backward: every
-// workgroup adds its whole 256 x D partial gradient with atomics, so fewer, longer chunks pay (c2, S = 4600: 0.103 -> 0.078 ms per
-// step with 512; 384 and fewer lose on the large tables: S = 1M backward 6.4 ms with 512, 7.5 ms with 384)
-int mfma_chunk(int64_t nx, int64_t ny, int target) {
-  const int64_t xt = fh_cdiv(nx, 256);
-  return (int)fh_allpairs_chunk(ny, fh_cdiv(target, xt), 64);
-}
-
-// host-side entry points used by loss.hip
-bool disc_mfma_supported(int64_t B, int64_t S, int64_t D) { return (D == 32 || D == 16) && B * S >= (int64_t)1 << 16; }
-
-int64_t disc_mfma_ws_bytes(int64_t B, int64_t S) {
-  const int chunk = mfma_chunk(B, S);
-  return fh_cdiv(S, chunk) * B * (int64_t)sizeof(float2);
-}
-
-// one-pass backward: the queries go in groups of `tiles` 256-query tiles; a group needs its chunks' partials of dq
-// (nchunks x rows x D floats) and tiles x S x (D + 1) floats of the streamed side's partial sums
-static int64_t onepass_group_bytes(int64_t tiles, int64_t B, int64_t S, int64_t D) {
-  const int64_t rows = std::min<int64_t>(B, tiles * 256);
-  const int64_t nchunks = fh_cdiv(S, mfma_chunk(rows, S, 512));
-  return (nchunks * rows * D + tiles * S * (D + 1)) * (int64_t)sizeof(float);
-}
-// the most tiles per group (<= all of them) whose partials fit `bytes`; 0: not even one
-static int64_t onepass_group_tiles(int64_t bytes, int64_t B, int64_t S, int64_t D) {
-  const int64_t nxt = fh_cdiv(B, 256);
-  int64_t lo = 0, hi = nxt;  // (the size grows with the tile count)
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) / 2;
-    if (onepass_group_bytes(mid, B, S, D) <= bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-int64_t disc_onepass_ws_bytes(int64_t B, int64_t S, int64_t D) {
-  const int64_t t = onepass_group_tiles(kOnePassWsCap, B, S, D);
-  return t > 0 ? onepass_group_bytes(t, B, S, D) : 0;
-}
-
-int disc_mfma_fwd(const float* q, const float* table, const int64_t* idx, int64_t row0, float c, float2* part, int* nchunks,
-                  int64_t B, int64_t S, int64_t D, int lp, hipStream_t st) {
-  DiscMfmaArgs a = {};
-  a.X = q;
-  a.Y = table;
-  a.NX = (int)B;
-  a.NY = (int)S;
-  a.c = c;
-  a.x_is_query = 1;
-  a.idx = idx;
-  a.row0 = row0;
-  a.part = part;
-  a.chunk = mfma_chunk(B, S);
-  *nchunks = (int)fh_cdiv(S, a.chunk);
-  dim3 grid((unsigned)*nchunks, (unsigned)fh_cdiv(B, 256));
-  if (lp && D == 32)
-    disc_lp_launch(a, 0, grid, st);
-  else if (D == 32)
-    hipLaunchKernelGGL((disc_mfma_kernel<32, 0>), grid, dim3(256), 0, st, a);
+template <int D>
+void launch_d(const DiscMfmaArgs& a, int mode, dim3 grid, hipStream_t st) {
+  if (mode == 0)
+    hipLaunchKernelGGL((disc_mfma_kernel<D, 0>), grid, dim3(256), 0, st, a);
+  else if (mode == 1)
+    hipLaunchKernelGGL((disc_mfma_kernel<D, 1>), grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL((disc_mfma_kernel<16, 0>), grid, dim3(256), 0, st, a);
-  return fh_launch_status();
+    hipLaunchKernelGGL((disc_mfma_kernel<D, 2>), grid, dim3(256), 0, st, a);
 }
 
-int disc_mfma_bwd(const float* q, const float* table, const int64_t* idx, int64_t row0, float c, const float* rmax,
-                  const float* rsum, const float* gsc, float gmul, float* dq, float* dtable, float* ws, int64_t ws_bytes, int64_t B,
-                  int64_t S, int64_t D, int lp, hipStream_t st) {
-  DiscMfmaArgs a = {};
-  a.c = c;
-  a.idx = idx;
-  a.row0 = row0;
-  a.rmax = rmax;
-  a.rsum = rsum;
-  a.gsc = gsc;
-  a.gmul = gmul;
-  const int64_t gtiles = (dq && dtable && ws) ? onepass_group_tiles(ws_bytes, B, S, D) : 0;
-  if (gtiles > 0) {
-    // one pass: stationary = queries, streamed = table rows; dq as in the two-pass form, dtable from the same weights.  Query
-    // groups of gtiles tiles, one after the other on the same workspace (dtable accumulates over the groups)
-    for (int64_t x0 = 0; x0 < B; x0 += gtiles * 256) {
-      const int64_t nb = std::min<int64_t>(B - x0, gtiles * 256), nxt = fh_cdiv(nb, 256);
-      a.X = q + x0 * D;
-      a.Y = table;
-      a.NX = (int)nb;
-      a.NY = (int)S;
-      a.x_is_query = 1;
-      a.idx = idx + x0;
-      a.rmax = rmax + x0;
-      a.rsum = rsum + x0;
-      a.chunk = mfma_chunk(nb, S, 512);
-      const int64_t nchunks = fh_cdiv(S, a.chunk);
-      a.G = ws;                       // [nchunks][nb, D]
-      a.G2 = a.G + nchunks * nb * D;  // [nxt][S, D]
-      a.WY = a.G2 + nxt * S * D;      // [nxt][S]
-      dim3 grid((unsigned)nchunks, (unsigned)nxt);
-      if (lp && D == 32)
-        disc_lp_launch(a, 2, grid, st);
-      else if (D == 32)
-        hipLaunchKernelGGL((disc_mfma_kernel<32, 2>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((disc_mfma_kernel<16, 2>), grid, dim3(256), 0, st, a);
-      int e = fh_launch_status();
-      if (e) return e;
-      hipLaunchKernelGGL(disc_dq_reduce_kernel, dim3((unsigned)fh_cdiv(nb * D, 256)), dim3(256), 0, st, dq + x0 * D, a.G, (int)nchunks, nb * D);
-      hipLaunchKernelGGL(disc_dt_finish_kernel, dim3((unsigned)fh_cdiv(S * D, 256)), dim3(256), 0, st, dtable, table, a.G2, a.WY, (int)nxt,
-                         2.f * c, S, (int)D);
-      e = fh_launch_status();
-      if (e) return e;
-    }
-    return FHVAE_OK;
-  }
-  if (dq) {  // stationary = queries, streamed = table rows; the workgroups ADD their partial gradients: zero first
-    hipError_t he = hipMemsetAsync(dq, 0, (size_t)(B * D) * sizeof(float), st);
-    if (he != hipSuccess) return (int)he;
-    a.X = q;
-    a.Y = table;
-    a.NX = (int)B;
-    a.NY = (int)S;
-    a.x_is_query = 1;
-    a.G = dq;
-    a.chunk = mfma_chunk(B, S, 512);
-    dim3 grid((unsigned)fh_cdiv(S, a.chunk), (unsigned)fh_cdiv(B, 256));
-    if (lp && D == 32)
-      disc_lp_launch(a, 1, grid, st);
-    else if (D == 32)
-      hipLaunchKernelGGL((disc_mfma_kernel<32, 1>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((disc_mfma_kernel<16, 1>), grid, dim3(256), 0, st, a);
-    int e = fh_launch_status();
-    if (e) return e;
-  }
-  if (dtable) {  // stationary = table rows, streamed = queries
-    a.X = table;
-    a.Y = q;
-    a.NX = (int)S;
-    a.NY = (int)B;
-    a.x_is_query = 0;
-    a.G = dtable;
-    a.chunk = mfma_chunk(S, B, 512);
-    dim3 grid((unsigned)fh_cdiv(B, a.chunk), (unsigned)fh_cdiv(S, 256));
-    if (lp && D == 32)
-      disc_lp_launch(a, 1, grid, st);
-    else if (D == 32)
-      hipLaunchKernelGGL((disc_mfma_kernel<32, 1>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((disc_mfma_kernel<16, 1>), grid, dim3(256), 0, st, a);
-    int e = fh_launch_status();
-    if (e) return e;
-  }
-  return FHVAE_OK;
+}  // namespace
+
+void disc_f32_launch(const DiscMfmaArgs& a, int D, int mode, dim3 grid, hipStream_t st) {
+  if (D == 32)
+    launch_d<32>(a, mode, grid, st);
+  else
+    launch_d<16>(a, mode, grid, st);
 }
 
 }  // namespace fh

@@ -1,10 +1,8 @@
 // loss.hip -- the HBM-streaming half of the hot path:
-//   K3 fused lower bound (simple_fhvae.py:105-116), K4 mu2 gather (:53), K5 discriminative
-//   log-sum-exp cross-entropy over the mu2 table (:119-122), fused Adam (train_model.py:409-411),
-//   layout utilities.
+//   K3 fused lower bound (simple_fhvae.py:105-116), K4 mu2 gather (:53), the final loss, fused Adam
+//   (train_model.py:409-411), layout utilities and the pack / unpack helpers of the row-sharded table's
+//   exchange.  (K5, the discriminative loss: disc.hip.)
 #include "common.h"
-#include "disc_mfma.h"
-#include <cstdlib>
 
 namespace fh {
 
@@ -306,164 +304,6 @@ __global__ __launch_bounds__(256) void elbo_bwd_pair_kernel(fhvae_elbo_bwd_desc 
     bd.d_x_colsum[(int64_t)blockIdx.x * 2 * F + j] = (cs[0][j] + cs[1][j]) + (cs[2][j] + cs[3][j]);
 }
 
-// ---------------------------------------------------------------------------------------------
-// K5 discriminative log-sum-exp cross-entropy.
-// Forward: thread = query b (q row in registers), table rows are wave-uniform -> scalar loads
-// (s_load_dwordx*), so per (b,s) pair the VALU does only the 2*D sub/fma and the online-LSE
-// update; nothing of size B*S is written.  grid = (query tiles of 256) x (row chunks).
-// ---------------------------------------------------------------------------------------------
-struct DiscPlan {
-  int chunk;    // table rows per workgroup
-  int nchunks;
-  int btiles;
-};
-static inline DiscPlan disc_plan(int64_t B, int64_t S) {
-  DiscPlan p;
-  p.btiles = (int)fh_cdiv(B, 256);
-  int64_t want = fh_cdiv(1024, p.btiles);  // aim at ~1024 workgroups
-  int64_t chunk = fh_cdiv(S, want);
-  chunk = fh_cdiv(chunk, 8) * 8;
-  if (chunk < 8) chunk = 8;
-  p.chunk = (int)chunk;
-  p.nchunks = (int)fh_cdiv(S, chunk);
-  return p;
-}
-
-template <int D>
-__device__ __forceinline__ float sqdist(const float (&q)[D], const float* __restrict__ trow) {
-  float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-  for (int d = 0; d < D; d += 2) {
-    const float d0 = q[d] - trow[d], d1 = q[d + 1] - trow[d + 1];
-    a0 = fmaf(d0, d0, a0);
-    a1 = fmaf(d1, d1, a1);
-  }
-  return a0 + a1;
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void disc_fwd_kernel(const float* __restrict__ q, const float* __restrict__ table,
-                                                       float c, float2* __restrict__ part, int B, int S, int chunk) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  const int bb = b < B ? b : B - 1;
-  float qr[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) qr[d] = q[(int64_t)bb * D + d];
-  const int s0 = blockIdx.y * chunk;
-  const int s1 = min(S, s0 + chunk);
-  float m = -INFINITY, sum = 0.f;
-  for (int s = s0; s < s1; s += 8) {
-    float l[8];
-    float gm = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int su = s + u;
-      // rows past the chunk end are clamped (uniform scalar address) and masked to -inf
-      const float* trow = table + (int64_t)(su < s1 ? su : s1 - 1) * D;
-      l[u] = su < s1 ? -c * sqdist<D>(qr, trow) : -INFINITY;
-      gm = fmaxf(gm, l[u]);
-    }
-    if (gm > m) {
-      sum *= __expf(m - gm);  // m = -inf on the first group: exp(-inf) = 0
-      m = gm;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) sum += __expf(l[u] - m);
-  }
-  if (b < B) part[(int64_t)blockIdx.y * B + b] = make_float2(m, sum);
-}
-
-// one WAVE per query: lanes stride over the chunk partials (a thread-per-query loop was a chain of nchunks
-// dependent L2 loads: 165 us for 144 chunks), then a wave-level (max, sum) merge; lane 0 also evaluates the
-// target logit.
-template <int D>
-__global__ __launch_bounds__(256) void disc_combine_kernel(const float* __restrict__ q, const float* __restrict__ table,
-                                                           const int64_t* __restrict__ idx, int64_t row0, float c,
-                                                           const float2* __restrict__ part, int nchunks,
-                                                           float* __restrict__ row_max, float* __restrict__ row_sum,
-                                                           float* __restrict__ tgt, int B, int S, int own_excluded) {
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;
-  float m = -INFINITY, sum = 0.f;
-  for (int k = lane; k < nchunks; k += 64) {
-    const float2 p = part[(int64_t)k * B + b];
-    if (p.x > m) {
-      sum = sum * __expf(m - p.x) + p.y;
-      m = p.x;
-    } else {
-      sum += p.y * __expf(p.x - m);
-    }
-  }
-  const float gm = wave_max(m);
-  sum = m == -INFINITY ? 0.f : sum * __expf(m - gm);
-  sum = wave_sum(sum);
-  // target logit with EXACTLY the arithmetic of disc_fwd_kernel (same sqdist order), so that a target that is the
-  // row maximum gives (max - target) == 0 bit for bit
-  const int64_t s = idx[b] - row0;
-  if (lane == 0) {
-    float t = 0.f;
-    if (s >= 0 && s < S) {
-      float qr[D];
-#pragma unroll
-      for (int d = 0; d < D; ++d) qr[d] = q[(int64_t)b * D + d];
-      t = -c * sqdist<D>(qr, table + s * D);
-      if (own_excluded) {
-        // the MFMA kernels left the query's own row out of the partials (disc_mfma.hip): its exact logit joins here
-        const float nm = fmaxf(gm, t);
-        sum = (gm == -INFINITY ? 0.f : sum * __expf(gm - nm)) + __expf(t - nm);
-        row_max[b] = nm;
-        row_sum[b] = sum;
-        tgt[b] = t;
-        return;
-      }
-    }
-    row_max[b] = gm;
-    row_sum[b] = sum;
-    tgt[b] = t;
-  }
-}
-
-// Backward of the (query, own row) pairs the MFMA kernels leave out: w = g (p_own - 1), p_own = exp(target - max) / sum with the
-// DIRECT-form target logit; dq[b] += -2c w (q_b - t_y), dtable[y] += +2c w (q_b - t_y).  One thread per (query, 4 dims).
-template <int D>
-__global__ __launch_bounds__(256) void disc_own_bwd_kernel(const float* __restrict__ q, const float* __restrict__ table,
-                                                           const int64_t* __restrict__ idx, int64_t row0, float c,
-                                                           const float* __restrict__ rmax, const float* __restrict__ rsum,
-                                                           const float* __restrict__ gsc, float gmul, float* __restrict__ dq,
-                                                           float* __restrict__ dtable, int B, int S) {
-  constexpr int PER = D / 4;  // threads per query
-  const int tid = blockIdx.x * 256 + threadIdx.x;
-  const int b = tid / PER, part = tid % PER;
-  if (b >= B) return;
-  const int64_t s = idx[b] - row0;
-  if (s < 0 || s >= S) return;
-  float qr[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) qr[d] = q[(int64_t)b * D + d];
-  const float t = -c * sqdist<D>(qr, table + s * D);
-  const float w = (*gsc) * gmul * (__expf(t - rmax[b]) / rsum[b] - 1.f);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int d = part * 4 + k;
-    const float diff = qr[d] - table[s * D + d];
-    if (dq) atomicAdd(dq + (int64_t)b * D + d, -2.f * c * w * diff);
-    if (dtable) atomicAdd(dtable + s * D + d, 2.f * c * w * diff);
-  }
-}
-
-// single-workgroup deterministic mean of (max + log(sumexp) - target)
-__global__ __launch_bounds__(256) void ce_mean_kernel(const float* __restrict__ row_max, const float* __restrict__ row_sum,
-                                                      const float* __restrict__ tgt, float* __restrict__ out, int B, float scale) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += 256) s += (row_max[b] - tgt[b]) + logf(row_sum[b]);  // exact 0 + log s when the target row is the max
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = scale * ((red[0] + red[1] + red[2] + red[3]) / (float)B);
-}
-
 // loss = -(mean(lower_bound) + alpha * log_qy)  (train_model.py:243-251) in one launch, and its backward in one
 __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__ lb, const float* __restrict__ log_qy, float alpha,
                                                        float* __restrict__ out, int B, int* __restrict__ nan_flag) {
@@ -508,22 +348,6 @@ __global__ void shard_unpack_kernel(const float* __restrict__ pk, float* __restr
   else
     idx[b] = (int64_t)__float_as_int(pk[i]);
 }
-// merge of the W ranks' K5 partials (parts[w] = [max | sumexp | target], N each): m = max_w, s = sum_w sumexp_w exp(max_w - m),
-// t = sum_w target_w.  An empty shard's (-inf, 0, 0) contributes exp(-inf) * 0 = 0.
-__global__ void disc_merge_kernel(const float* __restrict__ parts, float* __restrict__ m, float* __restrict__ s, float* __restrict__ t,
-                                  int W, int64_t N) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  float mx = -INFINITY;
-  for (int w = 0; w < W; ++w) mx = fmaxf(mx, parts[((int64_t)w * 3 + 0) * N + i]);
-  float ss = 0.f, tt = 0.f;
-  for (int w = 0; w < W; ++w) {
-    const float rm = parts[((int64_t)w * 3 + 0) * N + i], rs = parts[((int64_t)w * 3 + 1) * N + i];
-    ss += rs > 0.f ? rs * __expf(rm - mx) : 0.f;
-    tt += parts[((int64_t)w * 3 + 2) * N + i];
-  }
-  m[i] = mx, s[i] = ss, t[i] = tt;
-}
 // backward buffer [dq * scale | dmu2 rows of the local queries (zeros elsewhere)], N x 2D
 __global__ void shard_bwd_pack_kernel(const float* __restrict__ dq, float scale, const float* __restrict__ dmu2, int64_t own0, int64_t nown,
                                       float* __restrict__ out, int64_t N, int D) {
@@ -553,99 +377,6 @@ __global__ void shard_bwd_unpack_kernel(const float* __restrict__ buf, int64_t o
   }
 }
 
-// Backward, query side: dq[b,:] = -2c * sum_s w_bs (q_b - t_s), w = g (p - onehot)
-template <int D>
-__global__ __launch_bounds__(256) void disc_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ table,
-                                                          const int64_t* __restrict__ idx, int64_t row0, float c,
-                                                          const float* __restrict__ rmax, const float* __restrict__ rsum,
-                                                          const float* __restrict__ gsc, float gmul,
-                                                          float* __restrict__ dq, int B, int S, int chunk) {
-  __shared__ float tr[256][D + 1];
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  const int bb = b < B ? b : B - 1;
-  float qr[D], V[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    qr[d] = q[(int64_t)bb * D + d];
-    V[d] = 0.f;
-  }
-  const float g = *gsc * gmul;
-  // p = exp(logit - max) / sumexp: the max is one of the logits exactly, so the subtraction is exact for
-  // the rows that matter (an lse = max + log(sum) would carry the ulp of |max| ~ 1e3 into every p)
-  const float mb = rmax[bb], inv_s = 1.f / rsum[bb];
-  const int64_t tg = idx[bb] - row0;
-  const int s0 = blockIdx.y * chunk, s1 = min(S, s0 + chunk);
-  for (int s = s0; s < s1; ++s) {
-    const float* trow = table + (int64_t)s * D;
-    float df[D];
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d += 2) {
-      df[d] = qr[d] - trow[d];
-      df[d + 1] = qr[d + 1] - trow[d + 1];
-      a0 = fmaf(df[d], df[d], a0);
-      a1 = fmaf(df[d + 1], df[d + 1], a1);
-    }
-    const float lg = -c * (a0 + a1);
-    const float w = g * (__expf(lg - mb) * inv_s - (s == tg ? 1.f : 0.f));
-#pragma unroll
-    for (int d = 0; d < D; ++d) V[d] = fmaf(w, df[d], V[d]);
-  }
-  // transpose through LDS so the atomics go out as contiguous rows (MI355X_MICROARCH.md, float atomics)
-#pragma unroll
-  for (int d = 0; d < D; ++d) tr[threadIdx.x][d] = -2.f * c * V[d];
-  __syncthreads();
-  for (int i = threadIdx.x; i < 256 * D; i += 256) {
-    const int r = i / D, d = i % D;
-    const int br = blockIdx.x * 256 + r;
-    if (br < B) atomicAdd(dq + (int64_t)br * D + d, tr[r][d]);
-  }
-}
-
-// Backward, table side: thread = table row s (row in registers), queries are wave-uniform.
-// dtable[s,:] += 2c * sum_b w_bs (q_b - t_s)
-template <int D>
-__global__ __launch_bounds__(256) void disc_bwd_dt_kernel(const float* __restrict__ q, const float* __restrict__ table,
-                                                          const int64_t* __restrict__ idx, int64_t row0, float c,
-                                                          const float* __restrict__ rmax, const float* __restrict__ rsum,
-                                                          const float* __restrict__ gsc, float gmul,
-                                                          float* __restrict__ dtable, int B, int S, int bchunk) {
-  __shared__ float tr[256][D + 1];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  const int ss = s < S ? s : S - 1;
-  float t[D], U[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    t[d] = table[(int64_t)ss * D + d];
-    U[d] = 0.f;
-  }
-  const float g = *gsc * gmul;
-  const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
-  for (int b = b0; b < b1; ++b) {
-    const float* qrow = q + (int64_t)b * D;
-    float df[D];
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d += 2) {
-      df[d] = qrow[d] - t[d];
-      df[d + 1] = qrow[d + 1] - t[d + 1];
-      a0 = fmaf(df[d], df[d], a0);
-      a1 = fmaf(df[d + 1], df[d + 1], a1);
-    }
-    const float lg = -c * (a0 + a1);
-    const float w = g * (__expf(lg - rmax[b]) / rsum[b] - ((int64_t)s == idx[b] - row0 ? 1.f : 0.f));
-#pragma unroll
-    for (int d = 0; d < D; ++d) U[d] = fmaf(w, df[d], U[d]);
-  }
-#pragma unroll
-  for (int d = 0; d < D; ++d) tr[threadIdx.x][d] = 2.f * c * U[d];
-  __syncthreads();
-  for (int i = threadIdx.x; i < 256 * D; i += 256) {
-    const int r = i / D, d = i % D;
-    const int sr = blockIdx.x * 256 + r;
-    if (sr < S) atomicAdd(dtable + (int64_t)sr * D + d, tr[r][d]);
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Adam
@@ -869,72 +600,8 @@ extern "C" int fhvae_elbo_bwd(const fhvae_elbo_bwd_desc* d, void* stream) {
   return fh_launch_status();
 }
 
-// disc_mfma.hip / disc_lp.hip: the matrix-core forms for large (B x S), D == 32 (declared in disc_mfma.h)
-  // namespace fh
-
-extern "C" int64_t fhvae_disc_lse_bwd_ws_bytes(int64_t B, int64_t S, int64_t D) {
-  return (B > 0 && S > 0 && D > 0 && disc_mfma_supported(B, S, D)) ? disc_onepass_ws_bytes(B, S, D) : 0;
-}
-
 extern "C" int64_t fhvae_elbo_colsum_rows(int64_t B) { return B > 0 ? fh_cdiv(B, 2) : 0; }
 
-extern "C" int64_t fhvae_disc_lse_ws_bytes(int64_t B, int64_t S) {
-  if (B <= 0 || S <= 0) return 0;
-  DiscPlan p = disc_plan(B, S);
-  const int64_t a = (int64_t)p.nchunks * B * (int64_t)sizeof(float2), b = disc_mfma_ws_bytes(B, S);
-  return a > b ? a : b;
-}
-
-#define DISC_DISPATCH(D_, CALL) \
-  switch (D_) {                 \
-    case 4: { constexpr int DD = 4; CALL; } break;   \
-    case 8: { constexpr int DD = 8; CALL; } break;   \
-    case 16: { constexpr int DD = 16; CALL; } break; \
-    case 32: { constexpr int DD = 32; CALL; } break; \
-    case 64: { constexpr int DD = 64; CALL; } break; \
-    default: return FHVAE_ERR_SHAPE;                 \
-  }
-
-extern "C" int fhvae_disc_lse_fwd(const float* q, const float* table, const int64_t* idx, int64_t row0, float inv_two_var,
-                                  float* row_max, float* row_sumexp, float* tgt_logit, float* ce_mean, float ce_scale, void* ws,
-                                  int64_t B, int64_t S, int64_t D, int dtype, void* stream) {
-  if (dtype != FHVAE_F32 && dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
-  FH_CHECK_PTR(q);
-  FH_CHECK_PTR(table);
-  FH_CHECK_PTR(idx);
-  FH_CHECK_PTR(row_max);
-  FH_CHECK_PTR(row_sumexp);
-  FH_CHECK_PTR(tgt_logit);
-  FH_CHECK_PTR(ws);
-  FH_CHECK_POS(B);
-  FH_CHECK_POS(S);
-  FH_CHECK_I32(B);
-  FH_CHECK_I32(S);
-  hipStream_t st = (hipStream_t)stream;
-  DiscPlan p = disc_plan(B, S);
-  float2* part = (float2*)ws;
-  int e, own_excluded = 0;
-  if (disc_mfma_supported(B, S, D) && !getenv("FHVAE_DISC_VALU")) {
-    e = disc_mfma_fwd(q, table, idx, row0, inv_two_var, part, &p.nchunks, B, S, D, dtype == FHVAE_BF16, st);
-    own_excluded = 1;
-  } else {
-    dim3 grid((unsigned)p.btiles, (unsigned)p.nchunks);
-    DISC_DISPATCH(D, hipLaunchKernelGGL((disc_fwd_kernel<DD>), grid, dim3(256), 0, st, q, table, inv_two_var, part, (int)B,
-                                        (int)S, p.chunk));
-    e = fh_launch_status();
-  }
-  if (e) return e;
-  DISC_DISPATCH(D, hipLaunchKernelGGL((disc_combine_kernel<DD>), dim3((unsigned)fh_cdiv(B, 4)), dim3(256), 0, st, q, table, idx,
-                                      row0, inv_two_var, part, p.nchunks, row_max, row_sumexp, tgt_logit, (int)B, (int)S,
-                                      own_excluded));
-  e = fh_launch_status();
-  if (e) return e;
-  if (ce_mean) {
-    hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(256), 0, st, row_max, row_sumexp, tgt_logit, ce_mean, (int)B, ce_scale);
-    e = fh_launch_status();
-  }
-  return e;
-}
 
 extern "C" int fhvae_shard_pack(const float* q, const int64_t* idx, float* out, int64_t B, int64_t D, void* stream) {
   FH_CHECK_PTR(q);
@@ -954,19 +621,6 @@ extern "C" int fhvae_shard_unpack(const float* packed, float* q, int64_t* idx, i
   hipLaunchKernelGGL(shard_unpack_kernel, dim3((unsigned)fh_cdiv(N * (D + 1), 256)), dim3(256), 0, (hipStream_t)stream, packed, q, idx, N, (int)D);
   return fh_launch_status();
 }
-extern "C" int fhvae_disc_merge_partials(const float* parts, float* row_max, float* row_sumexp, float* tgt_logit, int64_t W, int64_t N,
-                                         void* stream) {
-  FH_CHECK_PTR(parts);
-  FH_CHECK_PTR(row_max);
-  FH_CHECK_PTR(row_sumexp);
-  FH_CHECK_PTR(tgt_logit);
-  FH_CHECK_POS(W);
-  FH_CHECK_POS(N);
-  FH_CHECK_I32(W);
-  hipLaunchKernelGGL(disc_merge_kernel, dim3((unsigned)fh_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, parts, row_max, row_sumexp,
-                     tgt_logit, (int)W, N);
-  return fh_launch_status();
-}
 extern "C" int fhvae_shard_bwd_pack(const float* dq_all, float dq_scale, const float* dmu2_local, int64_t own0, int64_t n_own, float* out,
                                     int64_t N, int64_t D, void* stream) {
   FH_CHECK_PTR(out);
@@ -984,69 +638,6 @@ extern "C" int fhvae_shard_bwd_unpack(const float* buf, int64_t own0, int64_t n_
   hipLaunchKernelGGL(shard_bwd_unpack_kernel, dim3((unsigned)fh_cdiv(N * 2 * D, 256)), dim3(256), 0, (hipStream_t)stream, buf, own0, n_own,
                      dq_local, dmu2_all, N, (int)D);
   return fh_launch_status();
-}
-
-extern "C" int fhvae_disc_ce_mean(const float* row_max, const float* row_sumexp, const float* tgt_logit, float* ce_mean,
-                                  float ce_scale, int64_t B, void* stream) {
-  FH_CHECK_PTR(row_max);
-  FH_CHECK_PTR(row_sumexp);
-  FH_CHECK_PTR(tgt_logit);
-  FH_CHECK_PTR(ce_mean);
-  FH_CHECK_POS(B);
-  FH_CHECK_I32(B);
-  hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_max, row_sumexp, tgt_logit, ce_mean,
-                     (int)B, ce_scale);
-  return fh_launch_status();
-}
-
-extern "C" int fhvae_disc_lse_bwd(const float* q, const float* table, const int64_t* idx, int64_t row0, float inv_two_var,
-                                  const float* row_max, const float* row_sumexp, const float* g_scale, float g_mul,
-                                  float* dq, float* dtable, void* ws, int64_t ws_bytes, int64_t B, int64_t S, int64_t D, int dtype,
-                                  void* stream) {
-  if (dtype != FHVAE_F32 && dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
-  FH_CHECK_PTR(q);
-  FH_CHECK_PTR(table);
-  FH_CHECK_PTR(idx);
-  FH_CHECK_PTR(row_max);
-  FH_CHECK_PTR(row_sumexp);
-  FH_CHECK_PTR(g_scale);
-  FH_CHECK_POS(B);
-  FH_CHECK_POS(S);
-  FH_CHECK_I32(B);
-  FH_CHECK_I32(S);
-  hipStream_t st = (hipStream_t)stream;
-  if (disc_mfma_supported(B, S, D) && !getenv("FHVAE_DISC_VALU")) {
-    if (ws && (((uintptr_t)ws) & 15)) return FHVAE_ERR_ALIGN;
-    int e = disc_mfma_bwd(q, table, idx, row0, inv_two_var, row_max, row_sumexp, g_scale, g_mul, dq, dtable, (float*)ws,
-                          ws ? ws_bytes : 0, B, S, D, dtype == FHVAE_BF16, st);
-    if (e) return e;
-    if (dq || dtable) {
-      DISC_DISPATCH(D, hipLaunchKernelGGL((disc_own_bwd_kernel<DD>), dim3((unsigned)fh_cdiv(B * (DD / 4), 256)), dim3(256), 0, st, q,
-                                          table, idx, row0, inv_two_var, row_max, row_sumexp, g_scale, g_mul, dq, dtable, (int)B,
-                                          (int)S));
-      e = fh_launch_status();
-    }
-    return e;
-  }
-  if (dq) {
-    hipError_t he = hipMemsetAsync(dq, 0, (size_t)(B * D) * sizeof(float), st);
-    if (he != hipSuccess) return (int)he;
-    DiscPlan p = disc_plan(B, S);
-    dim3 grid((unsigned)p.btiles, (unsigned)p.nchunks);
-    DISC_DISPATCH(D, hipLaunchKernelGGL((disc_bwd_dq_kernel<DD>), grid, dim3(256), 0, st, q, table, idx, row0, inv_two_var,
-                                        row_max, row_sumexp, g_scale, g_mul, dq, (int)B, (int)S, p.chunk));
-    int e = fh_launch_status();
-    if (e) return e;
-  }
-  if (dtable) {
-    DiscPlan p = disc_plan(S, B);  // roles swapped: threads = rows, chunks over queries
-    dim3 grid((unsigned)p.btiles, (unsigned)p.nchunks);
-    DISC_DISPATCH(D, hipLaunchKernelGGL((disc_bwd_dt_kernel<DD>), grid, dim3(256), 0, st, q, table, idx, row0, inv_two_var,
-                                        row_max, row_sumexp, g_scale, g_mul, dtable, (int)B, (int)S, p.chunk));
-    int e = fh_launch_status();
-    if (e) return e;
-  }
-  return FHVAE_OK;
 }
 
 extern "C" int fhvae_adam_step(float* p, float* g, float* m, float* v, void* p_lp, int64_t n, float lr, float beta1,

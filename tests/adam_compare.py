@@ -1,4 +1,4 @@
-"""One comparator for the fused Adam step (fhvae_adam_step, csrc/loss.hip:653-727) against its float64 oracle (oracle/adam_ref.py):
+"""One comparator for the fused Adam step (fhvae_adam_step, csrc/loss.hip:384-458) against its float64 oracle (oracle/adam_ref.py):
 tests/test_adam_oracle_gpu.py checks the kernel with it, tests/test_adam_oracle_cpu.py checks that a float32 emulation of the
 kernel's arithmetic passes it everywhere and that it rejects the errors a kernel could hide.
 
@@ -53,7 +53,7 @@ from oracle.adam_ref import adam_ref_terms, f32
 U = 2.0 ** -24
 V_TINY = 2.0 ** -126
 KEYS = ("p", "m", "v", "dp")
-GRID_CAP_ELEMS = 8192 * 256 * 4  # one pass of the capped grid: 8192 workgroups x 256 lanes x 4 elements (loss.hip:1061-1062)
+GRID_CAP_ELEMS = 8192 * 256 * 4  # one pass of the capped grid: 8192 workgroups x 256 lanes x 4 elements (loss.hip:652-653)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The grid arithmetic of the matrix-core K5 kernels (csrc/disc_mfma.hip), mirrored in Python for the tests that size workspaces
+"""The grid arithmetic of the matrix-core K5 kernels (csrc/disc.hip: mfma_chunk, onepass_group_bytes), mirrored in Python for the tests that size workspaces
 by it.  No imports: CPU and GPU tests share it."""
 
 

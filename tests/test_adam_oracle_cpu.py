@@ -1,6 +1,6 @@
 """The float64 oracle of the fused Adam step (oracle/adam_ref.py) and the comparator of the GPU checks (tests/adam_compare.py), on
 the CPU: the oracle is torch.optim.Adam in float64; a float32 emulation of the kernel's expressions in the kernel's order
-(csrc/loss.hip adam_one :653-661 and the two bias corrections of :676) passes compare() on every input family, step count, beta
+(csrc/loss.hip adam_one :384-392 and the two bias corrections of :407) passes compare() on every input family, step count, beta
 pair and gradient scale tests/test_adam_oracle_gpu.py uses, no element left out; and every deliberately wrong variant of that
 emulation is rejected on at least one of those cases.
 

@@ -1,4 +1,4 @@
-"""The fused Adam step (hip_binding.adam_step_ -> fhvae_adam_step, csrc/loss.hip:653-727; hip_optim.FusedAdam) against the float64
+"""The fused Adam step (hip_binding.adam_step_ -> fhvae_adam_step, csrc/loss.hip:384-458; hip_optim.FusedAdam) against the float64
 oracle of its own arithmetic (oracle/adam_ref.py) with the one comparator and the derived bounds of tests/adam_compare.py.
 
 Every comparison is one step from the device's own state (p, g, m, v copied to the CPU before the launch), no element left out.

@@ -1,6 +1,6 @@
 """Every form of K5 (hip_binding.raw_disc_fwd / raw_disc_bwd / disc_lse) against the float64 oracle of its own arithmetic
 (oracle/disc_ref.py), with one comparator and one set of constants per form (tests/disc_compare.py): the VALU direct form
-(loss.hip), the exact-f32 MFMA expanded form (disc_mfma.hip) and the bf16 split-operand form (disc_lp.hip), each MFMA form's
+(disc.hip), the exact-f32 MFMA expanded form (disc_mfma.hip) and the bf16 split-operand form (disc_lp.hip), each MFMA form's
 forward and its backward as two passes (ws_bytes = 0), one pass over the whole problem (MODE 2) and one pass in query groups of
 one and of two 256-query tiles.  Each case prints its measurements and, for comparison, the same numbers against the exact direct
 form.  The oracle runs in float64 on the GPU (torch's dgemm), the tensors never leave the device."""
@@ -29,7 +29,7 @@ def hb():
 
 
 def _form(B, S, D, lp):
-    """The form fhvae_disc_lse_fwd / _bwd dispatch to (loss.hip:917, 1018; disc_mfma.hip disc_mfma_supported; disc_lp for D = 32)."""
+    """The form fhvae_disc_lse_fwd / _bwd dispatch to (disc.hip disc_engine: direct = the VALU kernels, expanded = disc_mfma.hip, split = disc_lp.hip)."""
     if D in (16, 32) and B * S >= 65536:
         return "split" if lp and D == 32 else "expanded"
     return "direct"

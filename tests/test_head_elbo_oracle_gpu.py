@@ -149,7 +149,7 @@ def _pair_ref(gb, ld):
     return w
 
 
-# elbo_bwd_pair_kernel (loss.hip:241-307; fhvae_elbo_bwd takes it when d_x_pair_lp is given, loss.hip:856-866): F4 = F / 4 lanes per
+# elbo_bwd_pair_kernel (loss.hip:241-307; fhvae_elbo_bwd takes it when d_x_pair_lp is given, loss.hip:587-597): F4 = F / 4 lanes per
 # row, RP = 64 / F4 rows per pass (F = 4: 64; 8: 32; 80: 3; 128: 2; 132 and 256: 1), 2F = 512 fills the LDS row cs[.][512];
 # a wave takes passes p0, p0 + 2, ... four at a time (T = 50 at F = 80: 17 passes, each wave loops); odd B leaves the second
 # segment slot of the last workgroup empty; ld_pair > 2F writes the zero padding (loss.hip:290-294).

@@ -1,5 +1,5 @@
-"""SHA-256 of what the three all-pairs kernels (csrc/sv.hip, csrc/tsne.hip, the f32 K5 of csrc/disc_mfma.hip) write, on
-seeded inputs -- one line "name digest" per output, for comparing two builds of the library bit for bit.
+"""SHA-256 of what the all-pairs kernels (csrc/sv.hip, csrc/tsne.hip, the f32 K5 of csrc/disc_mfma.hip and the bf16 K5 of
+csrc/disc_lp.hip) write, on seeded inputs -- one line "name digest" per output, for comparing two builds of the library bit for bit.
 
     python tools/allpairs_digest.py [--lib PATH/libfhvae_hip.so] > listing.txt
     python tools/allpairs_digest.py --compare PARENT_RUN1 PARENT_RUN2 RESULT
@@ -19,7 +19,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SV_EXTRA = [(130, 48, 1024, 6, 5), (130, 128, 1024, 6, 6)]  # (D = 48: 12 chunks per row under the 4-chunk swizzle)
 TSNE_EXTRA = [(130, 48, 8.0)]
-K5 = [(257, 4097, 32, "unrelated", "edges"), (300, 4633, 16, "separated", "edges"), (2048, 33, 32, "unrelated", "edges")]
+# (B, S, D, regime, pattern, lp); lp: the bf16 compute mode (its own kernel for D = 32)
+K5 = [(257, 4097, 32, "unrelated", "edges", False), (300, 4633, 16, "separated", "edges", False), (2048, 33, 32, "unrelated", "edges", False),
+      (257, 4097, 32, "unrelated", "edges", True), (300, 4633, 32, "separated", "edges", True), (2048, 33, 32, "unrelated", "edges", True)]
 
 
 def digest(t):
@@ -61,15 +63,15 @@ def listing():
         yield what + "Y after 5 steps", y
 
     gsc = torch.tensor([0.7], device="cuda")
-    for seed, (B, S, D, regime, pattern) in enumerate(K5):
-        what = "k5 f32 B%d S%d D%d " % (B, S, D)
+    for seed, (B, S, D, regime, pattern, lp) in enumerate(K5):
+        what = "k5 %s B%d S%d D%d " % ("bf16" if lp else "f32", B, S, D)
         q, t, idx = (a.cuda() for a in DC.make_inputs(B, S, D, regime, pattern, seed))
-        rmax, rsum, tgt, ce = hb.raw_disc_fwd(q, t, idx, lp=False)
+        rmax, rsum, tgt, ce = hb.raw_disc_fwd(q, t, idx, lp=lp)
         for name, r in (("rmax", rmax), ("rsum", rsum), ("tgt", tgt), ("ce", ce)):
             yield what + "fwd " + name, r
         for name, ws_bytes in (("one pass", None), ("two passes", 0)):
             sink = torch.zeros(S, D, device="cuda")
-            dq, _ = hb.raw_disc_bwd(q, t, idx, rmax, rsum, gsc, 1.0 / B, dt_sink=sink, lp=False, ws_bytes=ws_bytes)
+            dq, _ = hb.raw_disc_bwd(q, t, idx, rmax, rsum, gsc, 1.0 / B, dt_sink=sink, lp=lp, ws_bytes=ws_bytes)
             yield what + "bwd %s dq" % name, dq
             yield what + "bwd %s dt" % name, sink
 
