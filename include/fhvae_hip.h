@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FHVAE_ABI_VERSION 11
+#define FHVAE_ABI_VERSION 12
 
 enum { FHVAE_F32 = 0, FHVAE_BF16 = 1 };
 
@@ -270,6 +270,51 @@ int fhvae_wgrad_f32(const float* a, int64_t lda, const float* b, int64_t ldb, fl
  * once).  One tile per CU, every row of `a` read once (csrc/proj.hip).  FHVAE_ERR_ALIGN when the preconditions do not hold. */
 int fhvae_proj_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, const float* bias, float* c, int64_t ldc,
                     int64_t M, int64_t N, int64_t K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Launch plans of the three matrix-product kernels: what fhvae_proj_bf16, the weight-gradient entries and the generic engine
+ * behind the linear layers would launch for the given sizes.  Host only: no stream, nothing is launched, and the pointers of
+ * the descriptors are looked at for alignment and equality only (never dereferenced).  Each fills caller-provided plans and
+ * returns the number of launches (< 0: the error the entry point would return before its first launch).  These ARE the
+ * functions the launchers call (csrc/proj.hip, csrc/wgrad.hip, csrc/gemm.hip), not a description of them.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct fhvae_proj_plan {
+  int32_t BM, BN, tiles; /* proj_kernel<BM, BN> on tiles = ceil(M / BM) * ceil(N / BN) workgroups */
+} fhvae_proj_plan;
+int fhvae_plan_proj(int64_t M, int64_t N, fhvae_proj_plan* out);
+
+#define FHVAE_WGRAD_MAX_PROBLEMS 16
+typedef struct fhvae_wgrad_plan {
+  int32_t BN, sk, grid, n; /* wgrad_kernel<., BN> on `grid` workgroups over n problems; sk: the cost model's K slices */
+  struct {
+    int32_t which; /* index of the problem in the call */
+    int32_t m_tiles, n_tiles, ksteps_per, splitk, shared_c;
+  } p[FHVAE_WGRAD_MAX_PROBLEMS];
+} fhvae_wgrad_plan;
+/* the launches of n problems of one dtype in launch order: the problems with N > 128 in chunks of 16, then the others.
+ * FHVAE_ERR_ALIGN if a problem is not eligible, FHVAE_ERR_LIMIT beyond 256 problems or `cap` launches. */
+int fhvae_plan_wgrad(const fhvae_wgrad_desc* x, int n, int dtype, fhvae_wgrad_plan* out, int cap);
+
+#define FHVAE_GEMM_MAX_GROUP 4
+typedef struct fhvae_gemm_desc { /* one problem C[M,N] = sum over two K segments of A . B^T, as the generic engine sees it */
+  const void* a[2]; const void* b[2]; int64_t lda[2], ldb[2];
+  const void* c; const void* c2; const void* clp; int64_t ldc, ldclp; /* f32 output(s), bf16 copy (any may be NULL) */
+  int32_t M, N, K[2], a_kc[2], b_kc[2]; /* K[s] = 0: segment unused; *_kc: 1 = the contraction index is contiguous */
+  int32_t splitk, mode;                 /* on entry: K slices (0 = choose, needs mode 1); 0 store, 1 add, 2 atomic add */
+} fhvae_gemm_desc;
+enum { FHVAE_GEMM_SLOW = 0, FHVAE_GEMM_PLAIN, FHVAE_GEMM_SWAP, FHVAE_GEMM_SWAP_DMA, FHVAE_GEMM_LONGK, FHVAE_GEMM_GROUP,
+       FHVAE_GEMM_GROUP_ONCE };
+typedef struct fhvae_gemm_plan { /* one launch */
+  int32_t first, n; /* problems [first, first + n) of the call; n > 1: one grouped launch */
+  int32_t status;   /* != 0: this problem's launch returns that error (the launches before it have gone out) */
+  int32_t variant;  /* FHVAE_GEMM_*: scalar fallback; unswapped kernel; swapped epilogue; ... with the LDS-DMA main loop; the
+                       long-K 128x64 bf16 tile; grouped; grouped with every output written once (swapped epilogue) */
+  int32_t BM, BN, CH, akc, bkc; /* tile, 16-byte chunks per panel row, orientation (0 for the scalar fallback) */
+  uint32_t grid[3];
+  int32_t splitk[FHVAE_GEMM_MAX_GROUP], mode[FHVAE_GEMM_MAX_GROUP]; /* resolved, per problem of the launch */
+} fhvae_gemm_plan;
+/* n problems of one call (fhvae_gauss_head_reparam_fwd makes 2): one grouped launch or one launch each; out holds n plans */
+int fhvae_plan_gemm(const fhvae_gemm_desc* d, int n, int dtype, fhvae_gemm_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * mu2 gather (K4): mu2[b,:] = table[idx[b],:]  -- torch.gather, simple_fhvae.py:53.

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 namespace fh {
 
@@ -89,7 +90,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int bx, int by, i
   zero_acc(acc);
   RowIdent arm{p.M}, brm{p.N};
   bool dma = false;
-  if constexpr (kDma)  // (mirrored by gemm_plan's dma_tiles in tests/gemm_plan.py)
+  if constexpr (kDma)  // (mirrored by dma_tiles in tests/matmul_plan_sweep.py: change both)
     dma = p.splitk == 1 && m0 + BM <= p.M && n0 + BN <= p.N && seg_glds_ok<T>(p.seg[0], TL::BK) && seg_glds_ok<T>(p.seg[1], TL::BK);
   if (dma) {
     if constexpr (kDma) mainloop_glds<T, BM, BN, WM, WN, CH, NBUF, SWAP>(acc, p.seg, m0, n0, arm, brm, smem);
@@ -121,6 +122,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, int bx, int by, i
     return;
   }
   // swapped MFMA roles: acc[tm][tn][r] = C[m = tm*16 + (lane & 15)][n = tn*16 + (lane >> 4)*4 + r]
+  // (mirrored by store_vec in tests/matmul_plan_sweep.py: change both)
   const bool vec = (p.ldc & 3) == 0 && (p.N & 3) == 0 && (!p.C || ((uintptr_t)p.C & 15) == 0) && (!p.C2 || ((uintptr_t)p.C2 & 15) == 0) &&
                    (!p.Clp || ((p.ldclp & 3) == 0 && ((uintptr_t)p.Clp & 7) == 0));
 #pragma unroll
@@ -218,193 +220,210 @@ __global__ void gemm_slow_kernel(GemmParams p) {
   gemm_store(p, row, col, acc);
 }
 
-template <typename T, int BM, int BN, int CH>
-static void launch_fast(const GemmParams& p, dim3 grid, hipStream_t st) {
-  // (mirrored by gemm_plan's `kernel` in tests/gemm_plan.py: change both)
-  const int akc = p.seg[0].K > 0 ? p.seg[0].a_kc : p.seg[1].a_kc;
-  const int bkc = p.seg[0].K > 0 ? p.seg[0].b_kc : p.seg[1].b_kc;
-  if (akc && bkc) {
-    if (CH == 32 && BM == 64 && p.splitk == 1 && (int64_t)grid.x * grid.y <= 256)
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, true, true, CH == 32 && BM == 64, true>), grid, dim3(kThreads), 0, st, p);
-    else if (p.splitk == 1 && p.mode != 2)
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, true, true, false, true>), grid, dim3(kThreads), 0, st, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, true, true>), grid, dim3(kThreads), 0, st, p);
-  }
-  else if (!akc && !bkc)
-    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, false, false>), grid, dim3(kThreads), 0, st, p);
-  else if constexpr (sizeof(T) == 4) {
-    if (akc)
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, true, false>), grid, dim3(kThreads), 0, st, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, false, true>), grid, dim3(kThreads), 0, st, p);
-  }
+// ---------------------------------------------------------------------------------------------
+// The launch plan: every decision of a call -- grouped or not, and per launch the kernel, tile, orientation, K slices, epilogue
+// mode and grid -- made once, on the host, from sizes, leading dimensions and pointer alignment alone.  fhvae_plan_gemm hands it
+// to a caller (the tests read it); launch_gemm_group fills the kernel arguments from it and launches.
+// ---------------------------------------------------------------------------------------------
+struct GemmFacts {  // what one problem offers, whichever way it goes out
+  bool agree;       // both segments share the operand orientation (true for every caller)
+  bool fast;        // the branch-free staging path takes it (else the scalar fallback); bf16 engine: KC/KC or KM/KM only
+  int akc, bkc, ktot, kmax;
+};
+static GemmFacts gemm_facts(const GemmParams& p, bool bf) {
+  const Seg &s0 = p.seg[0], &s1 = p.seg[1], &s = s0.K > 0 ? s0 : s1;
+  GemmFacts f;
+  f.agree = !(s0.K > 0 && s1.K > 0 && (s0.a_kc != s1.a_kc || s0.b_kc != s1.b_kc));
+  f.fast = bf ? (seg_fast_ok<u16>(s0, p.M, p.N) && seg_fast_ok<u16>(s1, p.M, p.N)) : (seg_fast_ok<float>(s0, p.M, p.N) && seg_fast_ok<float>(s1, p.M, p.N));
+  if (bf && ((s0.K > 0 && s0.a_kc != s0.b_kc) || (s1.K > 0 && s1.a_kc != s1.b_kc))) f.fast = false;
+  f.akc = s.a_kc, f.bkc = s.b_kc, f.ktot = s0.K + s1.K, f.kmax = s0.K > s1.K ? s0.K : s1.K;
+  return f;
 }
 
-// splitk == 0 on entry means "choose": only legal with mode 1 (accumulate), switched to atomics when split
-static int auto_splitk(int64_t tiles, int64_t panels) {  // (mirrored by auto_splitk in tests/gemm_plan.py)
-  if (tiles >= 192 || panels < 4) return 1;
-  int64_t s = fh_cdiv(512, tiles);
-  if (s > panels / 2) s = panels / 2;
-  if (s < 1) s = 1;
-  if (s > 128) s = 128;
-  return (int)s;
+// `want` K slices over `panels` panels: at least two panels per slice, at most `cap` slices
+static int clamp_splitk(int64_t want, int64_t panels, int64_t cap) {
+  if (want > panels / 2) want = panels / 2;
+  if (want < 1) want = 1;
+  return (int)(want > cap ? cap : want);
 }
+// splitk == 0 on entry means "choose": only legal with mode 1 (accumulate), switched to atomics when split.  Enough slices that
+// `tiles` output tiles offer `target` workgroups
+static int auto_splitk(int64_t target, int64_t tiles, int64_t panels) { return panels < 4 ? 1 : clamp_splitk(fh_cdiv(target, tiles), panels, 128); }
 
-int launch_gemm(const GemmParams& p_in, int dtype, hipStream_t st) {
-  GemmParams p = p_in;  // (the decisions below are mirrored by gemm_plan in tests/gemm_plan.py: change both)
-  if (p.M <= 0 || p.N <= 0) return FHVAE_ERR_SHAPE;
-  if (dtype != FHVAE_F32 && dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
-  const bool want_auto = p.splitk == 0;
-  if (want_auto && p.mode != 1) return FHVAE_ERR_SHAPE;
-  if (p.splitk < 1) p.splitk = 1;
-  // both segments must share the operand orientation (true for every caller)
-  if (p.seg[0].K > 0 && p.seg[1].K > 0 && (p.seg[0].a_kc != p.seg[1].a_kc || p.seg[0].b_kc != p.seg[1].b_kc))
-    return FHVAE_ERR_SHAPE;
-  const bool bf = dtype == FHVAE_BF16;
-  bool fast = bf ? (seg_fast_ok<u16>(p.seg[0], p.M, p.N) && seg_fast_ok<u16>(p.seg[1], p.M, p.N))
-                 : (seg_fast_ok<float>(p.seg[0], p.M, p.N) && seg_fast_ok<float>(p.seg[1], p.M, p.N));
-  if (bf)
-    for (int s = 0; s < 2; ++s)
-      if (p.seg[s].K > 0 && p.seg[s].a_kc != p.seg[s].b_kc) fast = false;  // bf16 engine: KC/KC or KM/KM only
-  if (!fast) {
-    p.splitk = 1;  // the fallback does not split: same semantics with one slice
-    const int64_t n = (int64_t)p.M * p.N;
-    if (bf)
-      hipLaunchKernelGGL(gemm_slow_kernel<u16>, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, st, p);
-    else
-      hipLaunchKernelGGL(gemm_slow_kernel<float>, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, st, p);
-    return fh_launch_status();
-  }
-  const int ktot = p.seg[0].K + p.seg[1].K;
-  const int kmax = p.seg[0].K > p.seg[1].K ? p.seg[0].K : p.seg[1].K;
+static fhvae_gemm_plan plan_one(const GemmParams& p, int dtype, int first) {
+  fhvae_gemm_plan pl = {};
+  pl.first = first, pl.n = 1;
+  const bool bf = dtype == FHVAE_BF16, want_auto = p.splitk == 0;
   const int epc = bf ? 8 : 4;
-  // 128x128 tiles (half the L2->LDS traffic per FLOP) once the problem offers enough of them
-  // (measured: with fewer than ~2 workgroups per CU the per-CU load bandwidth, not the aggregate L2 traffic,
-  // is the limit, and 64x64 tiles on more CUs win: 2048x1024x512 bf16 takes 11 us with 64^2, 21 us with 128^2)
-  // long-K bf16 weight gradients (KM/KM, K = T*B >= 16384): 128x64 tiles with 128-k panels (a third less operand traffic per
-  // FLOP than 64x64; 56 KB of LDS = two workgroups per CU) and exactly as many K slices as fill the chip twice over
-  // (512 workgroups).  1024x256 over K = 40960: 52 -> 43 us; other slice counts were slower (256: -6 %, 768: -4 % per step).
-  if (bf && want_auto && ktot >= 16384 && p.M >= 128 && p.seg[1].K == 0 && !p.seg[0].a_kc && !p.seg[0].b_kc) {
-    const int64_t tiles = fh_cdiv(p.M, 128) * fh_cdiv(p.N, 64);
-    int64_t sk = fh_cdiv(512, tiles);
-    const int64_t panels = fh_cdiv(ktot, 128);
-    if (sk > panels / 2) sk = panels / 2;
-    if (sk < 1) sk = 1;
-    p.splitk = (int)sk;
-    if (p.splitk > 1) p.mode = 2;
-    dim3 grid((unsigned)fh_cdiv(p.N, 64), (unsigned)fh_cdiv(p.M, 128), (unsigned)p.splitk);
-    hipLaunchKernelGGL((gemm_kernel<u16, 128, 64, 4, 1, 16, false, false>), grid, dim3(kThreads), 0, st, p);
-    return fh_launch_status();
-  }
-  const bool big = kmax > 16 * epc && fh_cdiv(p.M, 128) * fh_cdiv(p.N, 128) >= 512;
-  const int tb = big ? 128 : 64;
-  const int ch = big ? 16 : (kmax <= 16 * epc ? 8 : 32);
-  if (want_auto) {
-    p.splitk = auto_splitk(fh_cdiv(p.M, tb) * fh_cdiv(p.N, tb), fh_cdiv(ktot, ch * epc));
-    if (p.splitk > 1) p.mode = 2;
-  }
-  dim3 grid((unsigned)fh_cdiv(p.N, tb), (unsigned)fh_cdiv(p.M, tb), (unsigned)p.splitk);
-  if (!bf) {
-    if (big)
-      launch_fast<float, 128, 128, 16>(p, grid, st);
-    else if (ch == 8)
-      launch_fast<float, 64, 64, 8>(p, grid, st);
-    else
-      launch_fast<float, 64, 64, 32>(p, grid, st);
+  const GemmFacts f = gemm_facts(p, bf);
+  if (p.M <= 0 || p.N <= 0)
+    pl.status = FHVAE_ERR_SHAPE;
+  else if (dtype != FHVAE_F32 && dtype != FHVAE_BF16)
+    pl.status = FHVAE_ERR_DTYPE;
+  else if ((want_auto && p.mode != 1) || !f.agree)
+    pl.status = FHVAE_ERR_SHAPE;
+  if (pl.status) return pl;
+  int splitk = p.splitk < 1 ? 1 : p.splitk;
+  if (!f.fast) {
+    splitk = 1;  // the fallback does not split: same semantics with one slice
+    pl.variant = FHVAE_GEMM_SLOW;
+    pl.grid[0] = (unsigned)fh_cdiv((int64_t)p.M * p.N, 256), pl.grid[1] = 1;
   } else {
-    if (big)
-      launch_fast<u16, 128, 128, 16>(p, grid, st);
-    else if (ch == 8)
-      launch_fast<u16, 64, 64, 8>(p, grid, st);
-    else
-      launch_fast<u16, 64, 64, 32>(p, grid, st);
+    pl.akc = f.akc, pl.bkc = f.bkc;
+    // long-K bf16 weight gradients (KM/KM, K = T*B >= 16384): 128x64 tiles with 128-k panels (a third less operand traffic per
+    // FLOP than 64x64; 56 KB of LDS = two workgroups per CU) and exactly as many K slices as fill the chip twice over
+    // (512 workgroups).  1024x256 over K = 40960: 52 -> 43 us; other slice counts were slower (256: -6 %, 768: -4 % per step).
+    if (bf && want_auto && f.ktot >= 16384 && p.M >= 128 && p.seg[1].K == 0 && !f.akc && !f.bkc) {
+      pl.variant = FHVAE_GEMM_LONGK, pl.BM = 128, pl.BN = 64, pl.CH = 16;
+      splitk = clamp_splitk(fh_cdiv(512, fh_cdiv(p.M, 128) * fh_cdiv(p.N, 64)), fh_cdiv(f.ktot, 128), 512);
+    } else {
+      // 128x128 tiles (half the L2->LDS traffic per FLOP) once the problem offers enough of them
+      // (measured: with fewer than ~2 workgroups per CU the per-CU load bandwidth, not the aggregate L2 traffic,
+      // is the limit, and 64x64 tiles on more CUs win: 2048x1024x512 bf16 takes 11 us with 64^2, 21 us with 128^2)
+      const bool big = f.kmax > 16 * epc && fh_cdiv(p.M, 128) * fh_cdiv(p.N, 128) >= 512;
+      pl.BM = pl.BN = big ? 128 : 64;
+      pl.CH = big ? 16 : (f.kmax <= 16 * epc ? 8 : 32);
+      const int64_t tiles = fh_cdiv(p.M, pl.BM) * fh_cdiv(p.N, pl.BN);
+      if (want_auto) splitk = tiles >= 192 ? 1 : auto_splitk(512, tiles, fh_cdiv(f.ktot, pl.CH * epc));
+      const bool kc1 = f.akc && f.bkc && splitk == 1;  // KC/KC without a K split: the swapped epilogue
+      // the LDS-DMA instantiation needs 128 KB of LDS: launched only for small grids (gemm_kernel)
+      pl.variant = kc1 && pl.CH == 32 && pl.BM == 64 && tiles <= 256 ? FHVAE_GEMM_SWAP_DMA : kc1 && p.mode != 2 ? FHVAE_GEMM_SWAP : FHVAE_GEMM_PLAIN;
+    }
+    pl.grid[0] = (unsigned)fh_cdiv(p.N, pl.BN), pl.grid[1] = (unsigned)fh_cdiv(p.M, pl.BM);
   }
-  return fh_launch_status();
+  pl.grid[2] = (unsigned)splitk;
+  pl.splitk[0] = splitk;
+  pl.mode[0] = want_auto && splitk > 1 ? 2 : p.mode;
+  return pl;
 }
 
-// n <= kMaxGroup problems in one launch when they share dtype, orientation and the 64x64 / 512-byte-panel configuration
+// The plan of n problems of one call, into out[n]: returns the number of launches, or the error of a call that launches nothing.
+// n <= kMaxGroup problems go out as ONE launch when they share dtype, orientation and the 64x64 / 512-byte-panel configuration
 // and take the branch-free staging path; otherwise (and for n == 1) one launch each.  splitk == 0 (auto) is resolved per
 // problem against the group's total tile count.
-int launch_gemm_group(const GemmParams* ps, int n, int dtype, hipStream_t st) {
-  if (n <= 0) return FHVAE_OK;
+static int plan_gemm(const GemmParams* ps, int n, int dtype, fhvae_gemm_plan* out) {
   const bool bf = dtype == FHVAE_BF16;
   const int epc = bf ? 8 : 4;
   bool ok = n > 1 && n <= kMaxGroup;
-  int akc = -1, bkc = -1;
+  GemmFacts f0 = {};
   int64_t tiles = 0;
   for (int i = 0; i < n && ok; ++i) {
     const GemmParams& p = ps[i];
     if (p.M <= 0 || p.N <= 0) return FHVAE_ERR_SHAPE;
-    const bool fast = bf ? (seg_fast_ok<u16>(p.seg[0], p.M, p.N) && seg_fast_ok<u16>(p.seg[1], p.M, p.N))
-                         : (seg_fast_ok<float>(p.seg[0], p.M, p.N) && seg_fast_ok<float>(p.seg[1], p.M, p.N));
-    const int kmax = p.seg[0].K > p.seg[1].K ? p.seg[0].K : p.seg[1].K;
-    const int a = p.seg[0].K > 0 ? p.seg[0].a_kc : p.seg[1].a_kc, b = p.seg[0].K > 0 ? p.seg[0].b_kc : p.seg[1].b_kc;
-    if (p.seg[0].K > 0 && p.seg[1].K > 0 && (p.seg[0].a_kc != p.seg[1].a_kc || p.seg[0].b_kc != p.seg[1].b_kc)) ok = false;
-    if (!fast || kmax <= 16 * epc || (p.splitk == 0 && p.mode != 1)) ok = false;
-    if (p.seg[0].K + p.seg[1].K > 16384) ok = false;  // long contractions are bandwidth-bound: separate launches with the
-                                                       // XCD-aware tile order measured faster (B = 2048: 616k vs 604k segments/s)
-    if (bf && a != b) ok = false;
-    if (akc < 0) akc = a, bkc = b;
-    if (a != akc || b != bkc) ok = false;
+    const GemmFacts f = gemm_facts(p, bf);
+    if (i == 0) f0 = f;
+    // long contractions (> 16384) are bandwidth-bound: separate launches with the XCD-aware tile order measured faster
+    // (B = 2048: 616k vs 604k segments/s)
+    ok = f.agree && f.fast && f.kmax > 16 * epc && !(p.splitk == 0 && p.mode != 1) && f.ktot <= 16384 && f.akc == f0.akc && f.bkc == f0.bkc;
     tiles += fh_cdiv(p.M, 64) * fh_cdiv(p.N, 64);
   }
   if (!ok) {
+    for (int i = 0; i < n; ++i) out[i] = plan_one(ps[i], dtype, i);
+    return n;
+  }
+  fhvae_gemm_plan& g = out[0];
+  g = {};
+  g.n = n, g.BM = g.BN = 64, g.CH = 32, g.akc = f0.akc, g.bkc = f0.bkc;
+  g.grid[0] = g.grid[1] = 1;
+  bool once = f0.akc && f0.bkc;  // every output written once (no split-K atomics): the 16-byte-store epilogue
+  for (int i = 0; i < n; ++i) {
+    const GemmParams& p = ps[i];
+    g.splitk[i] = p.splitk, g.mode[i] = p.mode;
+    if (p.splitk == 0) {
+      // enough K slices that the group as a whole offers ~3 workgroups per CU (long contractions are bandwidth-bound:
+      // they want the occupancy; short ones are latency-bound: they want the parallelism)
+      g.splitk[i] = auto_splitk(768, tiles, fh_cdiv(p.seg[0].K + p.seg[1].K, 32 * epc));
+      if (g.splitk[i] > 1) g.mode[i] = 2;
+    }
+    if (g.splitk[i] < 1) g.splitk[i] = 1;
+    g.grid[0] = std::max(g.grid[0], (unsigned)fh_cdiv(p.N, 64)), g.grid[1] = std::max(g.grid[1], (unsigned)fh_cdiv(p.M, 64));
+    g.grid[2] += (unsigned)g.splitk[i];
+    once = once && g.splitk[i] == 1 && g.mode[i] != 2;
+  }
+  g.variant = once ? FHVAE_GEMM_GROUP_ONCE : FHVAE_GEMM_GROUP;
+  return 1;
+}
+
+// the plan's (tile, variant) -> the kernel instantiation, for one type and orientation; p: the single problem, g: the group
+template <typename T, int BM, int BN, int CH, bool AKC, bool BKC>
+static void launch_tile(int variant, const GemmParams& p, dim3 grid, hipStream_t st) {
+  constexpr bool KC = AKC && BKC;
+  if (KC && variant == FHVAE_GEMM_SWAP_DMA)
+    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, AKC, BKC, KC && CH == 32 && BM == 64, KC>), grid, dim3(kThreads), 0, st, p);
+  else if (KC && variant == FHVAE_GEMM_SWAP)
+    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, AKC, BKC, false, KC>), grid, dim3(kThreads), 0, st, p);
+  else
+    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, 2, 2, CH, AKC, BKC>), grid, dim3(kThreads), 0, st, p);
+}
+template <typename T, bool AKC, bool BKC>
+static void launch_oriented(const fhvae_gemm_plan& pl, const GemmParams* p, const GemmGroup* g, dim3 grid, hipStream_t st) {
+  if (g && AKC && BKC && pl.variant == FHVAE_GEMM_GROUP_ONCE)
+    hipLaunchKernelGGL((gemm_group_kernel<T, 64, 64, 2, 2, 32, AKC, BKC, AKC && BKC>), grid, dim3(kThreads), 0, st, *g);
+  else if (g)
+    hipLaunchKernelGGL((gemm_group_kernel<T, 64, 64, 2, 2, 32, AKC, BKC>), grid, dim3(kThreads), 0, st, *g);
+  else if (pl.BM == 128)
+    launch_tile<T, 128, 128, 16, AKC, BKC>(pl.variant, *p, grid, st);
+  else if (pl.CH == 8)
+    launch_tile<T, 64, 64, 8, AKC, BKC>(pl.variant, *p, grid, st);
+  else
+    launch_tile<T, 64, 64, 32, AKC, BKC>(pl.variant, *p, grid, st);
+}
+
+// one launch of a plan: fill the kernel arguments, then the one type x orientation ladder
+static int launch_planned(const fhvae_gemm_plan& pl, const GemmParams* ps, int dtype, hipStream_t st) {
+  if (pl.status) return pl.status;
+  const bool bf = dtype == FHVAE_BF16;
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  GemmParams p = ps[pl.first];
+  p.splitk = pl.splitk[0], p.mode = pl.mode[0];
+  GemmGroup grp = {};
+  for (int i = 0; i < pl.n && pl.n > 1; ++i) {
+    grp.n = pl.n;
+    grp.p[i] = ps[i];
+    grp.p[i].splitk = pl.splitk[i], grp.p[i].mode = pl.mode[i];
+    grp.zbase[i + 1] = grp.zbase[i] + pl.splitk[i];
+  }
+  const GemmGroup* g = pl.n > 1 ? &grp : nullptr;
+  if (pl.variant == FHVAE_GEMM_SLOW) {
+    if (bf)
+      hipLaunchKernelGGL(gemm_slow_kernel<u16>, grid, dim3(256), 0, st, p);
+    else
+      hipLaunchKernelGGL(gemm_slow_kernel<float>, grid, dim3(256), 0, st, p);
+  } else if (pl.variant == FHVAE_GEMM_LONGK)
+    hipLaunchKernelGGL((gemm_kernel<u16, 128, 64, 4, 1, 16, false, false>), grid, dim3(kThreads), 0, st, p);
+  else if (bf && pl.akc)
+    launch_oriented<u16, true, true>(pl, &p, g, grid, st);
+  else if (bf)
+    launch_oriented<u16, false, false>(pl, &p, g, grid, st);
+  else if (pl.akc && pl.bkc)
+    launch_oriented<float, true, true>(pl, &p, g, grid, st);
+  else if (!pl.akc && !pl.bkc)
+    launch_oriented<float, false, false>(pl, &p, g, grid, st);
+  else if (pl.akc)
+    launch_oriented<float, true, false>(pl, &p, g, grid, st);
+  else
+    launch_oriented<float, false, true>(pl, &p, g, grid, st);
+  return fh_launch_status();
+}
+
+int launch_gemm_group(const GemmParams* ps, int n, int dtype, hipStream_t st) {
+  if (n > kMaxGroup) {  // more than a group can hold: one launch each
     for (int i = 0; i < n; ++i) {
-      int e = launch_gemm(ps[i], dtype, st);
+      const int e = launch_gemm(ps[i], dtype, st);
       if (e) return e;
     }
     return FHVAE_OK;
   }
-  GemmGroup g = {};
-  g.n = n;
-  unsigned gx = 1, gy = 1;
-  for (int i = 0; i < n; ++i) {
-    GemmParams p = ps[i];
-    if (p.splitk == 0) {
-      // enough K slices that the group as a whole offers ~3 workgroups per CU (long contractions are bandwidth-bound:
-      // they want the occupancy; short ones are latency-bound: they want the parallelism)
-      const int64_t panels = fh_cdiv(p.seg[0].K + p.seg[1].K, 32 * epc);
-      int64_t sk = panels < 4 ? 1 : fh_cdiv(768, tiles);
-      if (sk > panels / 2) sk = panels / 2;
-      if (sk < 1) sk = 1;
-      if (sk > 128) sk = 128;
-      p.splitk = (int)sk;
-      if (p.splitk > 1) p.mode = 2;
-    }
-    if (p.splitk < 1) p.splitk = 1;
-    g.p[i] = p;
-    g.zbase[i + 1] = g.zbase[i] + p.splitk;
-    gx = gx > (unsigned)fh_cdiv(p.N, 64) ? gx : (unsigned)fh_cdiv(p.N, 64);
-    gy = gy > (unsigned)fh_cdiv(p.M, 64) ? gy : (unsigned)fh_cdiv(p.M, 64);
+  fhvae_gemm_plan pl[kMaxGroup];
+  const int launches = n > 0 ? plan_gemm(ps, n, dtype, pl) : 0;
+  for (int l = 0; l < launches; ++l) {
+    const int e = launch_planned(pl[l], ps, dtype, st);
+    if (e) return e;
   }
-  dim3 grid(gx, gy, (unsigned)g.zbase[n]);
-  bool once = true;  // every output written once (no split-K atomics): the 16-byte-store epilogue
-  for (int i = 0; i < n; ++i) once = once && g.p[i].splitk == 1 && g.p[i].mode != 2;
-  if (bf) {
-    if (akc && once)
-      hipLaunchKernelGGL((gemm_group_kernel<u16, 64, 64, 2, 2, 32, true, true, true>), grid, dim3(kThreads), 0, st, g);
-    else if (akc)
-      hipLaunchKernelGGL((gemm_group_kernel<u16, 64, 64, 2, 2, 32, true, true>), grid, dim3(kThreads), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_group_kernel<u16, 64, 64, 2, 2, 32, false, false>), grid, dim3(kThreads), 0, st, g);
-  } else if (akc && bkc && once)
-    hipLaunchKernelGGL((gemm_group_kernel<float, 64, 64, 2, 2, 32, true, true, true>), grid, dim3(kThreads), 0, st, g);
-  else if (akc && bkc)
-    hipLaunchKernelGGL((gemm_group_kernel<float, 64, 64, 2, 2, 32, true, true>), grid, dim3(kThreads), 0, st, g);
-  else if (!akc && !bkc)
-    hipLaunchKernelGGL((gemm_group_kernel<float, 64, 64, 2, 2, 32, false, false>), grid, dim3(kThreads), 0, st, g);
-  else if (akc)
-    hipLaunchKernelGGL((gemm_group_kernel<float, 64, 64, 2, 2, 32, true, false>), grid, dim3(kThreads), 0, st, g);
-  else
-    hipLaunchKernelGGL((gemm_group_kernel<float, 64, 64, 2, 2, 32, false, true>), grid, dim3(kThreads), 0, st, g);
-  return fh_launch_status();
+  return launches < 0 ? launches : FHVAE_OK;
 }
 
-// kept for callers that want an explicit split (none at present)
-int pick_splitk(int64_t M, int64_t N, int64_t K) {
-  return auto_splitk(fh_cdiv(M, 64) * fh_cdiv(N, 64), fh_cdiv(K, 128));
-}
+int launch_gemm(const GemmParams& p, int dtype, hipStream_t st) { return launch_gemm_group(&p, 1, dtype, st); }
 
 // ---------------------------------------------------------------------------------------------
 // small elementwise / reduction helpers
@@ -636,6 +655,19 @@ __global__ __launch_bounds__(256) void add_split_kernel(const float* __restrict_
 }  // namespace fh
 
 using namespace fh;
+
+extern "C" int fhvae_plan_gemm(const fhvae_gemm_desc* d, int n, int dtype, fhvae_gemm_plan* out) {
+  if (n <= 0) return 0;
+  FH_CHECK_PTR(d);
+  FH_CHECK_PTR(out);
+  std::vector<GemmParams> ps(n, GemmParams{});
+  for (int i = 0; i < n; ++i) {
+    for (int s = 0; s < 2; ++s) ps[i].seg[s] = Seg{d[i].a[s], d[i].lda[s], d[i].a_kc[s], d[i].b[s], d[i].ldb[s], d[i].b_kc[s], d[i].K[s], 0};
+    ps[i].M = d[i].M, ps[i].N = d[i].N, ps[i].ldc = d[i].ldc, ps[i].ldclp = d[i].ldclp, ps[i].splitk = d[i].splitk, ps[i].mode = d[i].mode;
+    ps[i].C = (float*)d[i].c, ps[i].C2 = (float*)d[i].c2, ps[i].Clp = (u16*)d[i].clp;
+  }
+  return plan_gemm(ps.data(), n, dtype, out);
+}
 
 extern "C" int fhvae_linear_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* b, float* y,
                                 int64_t ldy, void* y_lp, int64_t M, int64_t K, int64_t N, int relu, int dtype,

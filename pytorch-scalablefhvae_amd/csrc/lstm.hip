@@ -983,7 +983,7 @@ static bool wg_from_desc(const fhvae_wgrad_desc* x, WgProblem& p) {
   p.lda = x->lda, p.ldb = x->ldb, p.ldc = x->ldc;
   p.M = (int)x->M, p.N = (int)x->N, p.K = (int)x->K;
   p.a_col0 = (int)x->a_col0;
-  return wgrad_eligible(p) && x->ldc >= x->N;  // (mirrored by wgrad_desc_ok in tests/gemm_plan.py)
+  return wgrad_eligible(p) && x->ldc >= x->N;
 }
 
 extern "C" int fhvae_wgrad_desc_ok(const fhvae_wgrad_desc* x) {

@@ -180,6 +180,20 @@ static int launch_bn(const ProjArgs& a, int bm, hipStream_t st) {
   }
 }
 
+// The launch plan: all N columns per tile where they fit (BN = 256 or 128), and the row tile that fills the chip's 256 CUs in
+// the fewest rounds with the least padding: one round if it can.  fhvae_plan_proj hands it to a caller, launch_proj launches it.
+static fhvae_proj_plan plan_proj(int64_t M, int64_t N) {
+  fhvae_proj_plan pl = {256, N > 128 ? 256 : 128, 0};
+  const int64_t ncol = fh_cdiv(N, pl.BN);
+  double best_t = 1e30;
+  for (int bm = 64; bm <= 256; bm += 32) {
+    const int64_t tiles = fh_cdiv(M, bm) * ncol;
+    const double t = (double)fh_cdiv(tiles, 256) * (bm + 24);  // per-tile time ~ rows + a fixed cost (weights, fill, drain)
+    if (t < best_t) best_t = t, pl.BM = bm, pl.tiles = (int)tiles;
+  }
+  return pl;
+}
+
 bool proj_eligible(const void* a, int64_t lda, const void* b, int64_t ldb, const float* c, int64_t ldc, int64_t M, int64_t N,
                    int64_t K) {
   if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return false;
@@ -193,23 +207,21 @@ int launch_proj(const void* a, int64_t lda, const void* b, int64_t ldb, float* c
                 int64_t N, int64_t K, hipStream_t st, const float* bias2, int bias_split) {
   if (!proj_eligible(a, lda, b, ldb, c, ldc, M, N, K) || (bias2 && (bias_split % 4))) return FHVAE_ERR_ALIGN;
   ProjArgs p = {(const u16*)a, (const u16*)b, c, bias, bias2, bias_split, lda, ldb, ldc, (int)M, (int)N, (int)K};
-  const int BN = N > 128 ? 256 : 128;
-  const int64_t ncol = fh_cdiv(N, BN);
-  // (mirrored by proj_plan in tests/gemm_plan.py: change both)
-  // the row tile that fills the chip's 256 CUs in the fewest rounds with the least padding: one round if it can
-  int best = 256;
-  double best_t = 1e30;
-  for (int bm = 64; bm <= 256; bm += 32) {
-    const int64_t tiles = fh_cdiv(M, bm) * ncol;
-    const double t = (double)fh_cdiv(tiles, 256) * (bm + 24);  // per-tile time ~ rows + a fixed cost (weights, fill, drain)
-    if (t < best_t) best_t = t, best = bm;
-  }
-  return BN == 256 ? launch_bn<256>(p, best, st) : launch_bn<128>(p, best, st);
+  const fhvae_proj_plan pl = plan_proj(M, N);
+  return pl.BN == 256 ? launch_bn<256>(p, pl.BM, st) : launch_bn<128>(p, pl.BM, st);
 }
 
 }  // namespace fh
 
 using namespace fh;
+
+extern "C" int fhvae_plan_proj(int64_t M, int64_t N, fhvae_proj_plan* out) {
+  FH_CHECK_PTR(out);
+  FH_CHECK_POS(M);
+  FH_CHECK_POS(N);
+  *out = plan_proj(M, N);
+  return 1;
+}
 
 extern "C" int fhvae_proj_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, const float* bias, float* c, int64_t ldc,
                                int64_t M, int64_t N, int64_t K, void* stream) {

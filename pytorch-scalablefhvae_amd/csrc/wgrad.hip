@@ -32,12 +32,13 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "gemm_core.h"
 
 namespace fh {
 
-constexpr int kWgThreads = 512, kWgBM = 256, kMaxWgProblems = 16;
+constexpr int kWgThreads = 512, kWgBM = 256, kMaxWgProblems = FHVAE_WGRAD_MAX_PROBLEMS;
 
 struct WgBf16 {
   using T = u16;
@@ -275,7 +276,7 @@ template __global__ void wgrad_kernel<WgF32, 128>(WgGroupT<WgF32>);
 template <class T>
 bool wgrad_eligible(const WgProblemT<T>& p) {
   using E = WgElem<T>;
-  constexpr int64_t ES = sizeof(T);  // (mirrored by wgrad_desc_ok in tests/gemm_plan.py)
+  constexpr int64_t ES = sizeof(T);
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.A || !p.B || !p.C) return false;
   if ((((uintptr_t)p.A) | ((uintptr_t)p.B)) & 15) return false;
   if ((p.lda % (16 / ES)) || (p.ldb % (16 / ES)) || p.lda < p.a_col0 + p.M || p.ldb < p.N || p.a_col0 < 0) return false;
@@ -284,73 +285,100 @@ bool wgrad_eligible(const WgProblemT<T>& p) {
   return true;
 }
 
-template <class T, int BN>
-static int launch_class(const WgProblemT<T>* ps, const int* which, int n, hipStream_t st) {
+// One launch of the plan: the K slices of its problems (all of the tile class l.BN) and the grid.
+// One launch is about one workgroup per CU: the K slices are what is left after the tiles.
+template <class T>
+static void plan_launch(const WgProblemT<T>* ps, fhvae_wgrad_plan& l) {
   using E = WgElem<T>;
-  // (mirrored, cost model included, by wgrad_class_plan in tests/gemm_plan.py: change both)
-  // one launch of about one workgroup per CU: the K slices are what is left after the tiles
-  for (int at = 0; at < n; at += kMaxWgProblems) {
-    const int cnt = n - at < kMaxWgProblems ? n - at : kMaxWgProblems;
-    int64_t tiles = 0, ks_max = 1;
-    for (int k = 0; k < cnt; ++k) {
-      const WgProblemT<T>& p = ps[which[at + k]];
-      tiles += fh_cdiv(p.M, kWgBM) * fh_cdiv(p.N, BN);
-      ks_max = std::max<int64_t>(ks_max, fh_cdiv(p.K, E::BK));
-    }
-    // K slices: every extra slice adds a tile of f32 atomics per output tile (the chip adds ~1.3 TB/s, guide: global float
-    // atomics) and shortens the slices; pick the count that minimises  waves x steps x t_step + atomic bytes / rate
-    // (t_step: one BK-k step of a workgroup at the element's MFMA rate over 256 CUs)
-    const double t_step = 2.0 * kWgBM * BN * E::BK / (E::kRate / 256), tile_bytes = 4.0 * kWgBM * BN;
-    int64_t sk = 1;
-    double best = 1e30;
-    for (int64_t c = 1; c <= 64 && c * 2 <= ks_max; ++c) {
-      const double waves = (double)fh_cdiv(tiles * c, 256), steps = (double)fh_cdiv(ks_max, c) + 2.0;
-      const double t = waves * steps * t_step + (c > 1 ? tiles * c * tile_bytes / 1.3e12 : 0.0);
-      if (t < best) best = t, sk = c;
-    }
-    WgGroupT<E> g = {};
-    g.n = cnt;
-    for (int k = 0; k < cnt; ++k) {
-      WgProblemT<T> p = ps[which[at + k]];
-      p.m_tiles = (int)fh_cdiv(p.M, kWgBM);
-      p.n_tiles = (int)fh_cdiv(p.N, BN);
-      const int64_t ks_total = fh_cdiv(p.K, E::BK);
-      int64_t s = sk;
-      if (s > ks_total / 2) s = ks_total / 2;
-      if (s < 1) s = 1;
-      p.ksteps_per = (int)fh_cdiv(ks_total, s);
-      p.splitk = (int)fh_cdiv(ks_total, p.ksteps_per);
-      g.p[k] = p;
-      g.base[k + 1] = g.base[k] + p.m_tiles * p.n_tiles * p.splitk;
-    }
+  int64_t tiles = 0, ks_max = 1;
+  for (int k = 0; k < l.n; ++k) {
+    const WgProblemT<T>& p = ps[l.p[k].which];
+    tiles += fh_cdiv(p.M, kWgBM) * fh_cdiv(p.N, l.BN);
+    ks_max = std::max<int64_t>(ks_max, fh_cdiv(p.K, E::BK));
+  }
+  // K slices: every extra slice adds a tile of f32 atomics per output tile (the chip adds ~1.3 TB/s, guide: global float
+  // atomics) and shortens the slices; pick the count that minimises  waves x steps x t_step + atomic bytes / rate
+  // (t_step: one BK-k step of a workgroup at the element's MFMA rate over 256 CUs)
+  const double t_step = 2.0 * kWgBM * l.BN * E::BK / (E::kRate / 256), tile_bytes = 4.0 * kWgBM * l.BN;
+  int64_t sk = 1;
+  double best = 1e30;
+  for (int64_t c = 1; c <= 64 && c * 2 <= ks_max; ++c) {
+    const double waves = (double)fh_cdiv(tiles * c, 256), steps = (double)fh_cdiv(ks_max, c) + 2.0;
+    const double t = waves * steps * t_step + (c > 1 ? tiles * c * tile_bytes / 1.3e12 : 0.0);
+    if (t < best) best = t, sk = c;
+  }
+  l.sk = (int)sk;
+  for (int k = 0; k < l.n; ++k) {
+    auto& q = l.p[k];
+    const WgProblemT<T>& p = ps[q.which];
+    q.m_tiles = (int)fh_cdiv(p.M, kWgBM);
+    q.n_tiles = (int)fh_cdiv(p.N, l.BN);
+    const int64_t ks_total = fh_cdiv(p.K, E::BK);
+    int64_t s = sk;
+    if (s > ks_total / 2) s = ks_total / 2;
+    if (s < 1) s = 1;
+    q.ksteps_per = (int)fh_cdiv(ks_total, s);
+    q.splitk = (int)fh_cdiv(ks_total, q.ksteps_per);
+    l.grid += q.m_tiles * q.n_tiles * q.splitk;
     // two problems of one launch that accumulate into the same matrix (a net queued twice: gradient accumulation over two
     // backward passes before one optimizer step) must not take the plain read-modify-write path
-    for (int a = 0; a < cnt; ++a)
-      for (int b = 0; b < cnt; ++b)
-        if (a != b && g.p[a].C == g.p[b].C) g.p[a].shared_c = 1;
-    const dim3 grid((unsigned)g.base[cnt]), block(kWgThreads);
-    hipLaunchKernelGGL((wgrad_kernel<E, BN>), grid, block, 0, st, g);
-    const int e = fh_launch_status();
-    if (e) return e;
+    for (int b = 0; b < l.n; ++b)
+      if (b != k && ps[l.p[b].which].C == p.C) q.shared_c = 1;
   }
-  return FHVAE_OK;
+}
+
+// The launch plan of a call: its launches in launch order -- the problems with N > 128 (BN = 256) in chunks of kMaxWgProblems,
+// then the others (BN = 128) -- into out[cap]; returns their number.  Host arithmetic on sizes, alignments and the equality of
+// the C pointers; fhvae_plan_wgrad hands it to a caller, launch_wgrad launches it.
+template <class T>
+static int plan_wgrad(const WgProblemT<T>* ps, int n, fhvae_wgrad_plan* out, int cap) {
+  if (n > 256) return FHVAE_ERR_LIMIT;
+  for (int k = 0; k < n; ++k)
+    if (!wgrad_eligible(ps[k])) return FHVAE_ERR_ALIGN;
+  int launches = 0;
+  for (const int BN : {256, 128}) {
+    fhvae_wgrad_plan* l = nullptr;
+    for (int k = 0; k < n; ++k) {
+      if ((ps[k].N > 128) != (BN == 256)) continue;
+      if (!l || l->n == kMaxWgProblems) {
+        if (launches == cap) return FHVAE_ERR_LIMIT;
+        l = &out[launches++];
+        *l = {};
+        l->BN = BN;
+      }
+      l->p[l->n++].which = k;
+    }
+  }
+  for (int i = 0; i < launches; ++i) plan_launch(ps, out[i]);
+  return launches;
+}
+
+template <class T, int BN>
+static int launch_class(const WgProblemT<T>* ps, const fhvae_wgrad_plan& l, hipStream_t st) {
+  WgGroupT<WgElem<T>> g = {};
+  g.n = l.n;
+  for (int k = 0; k < l.n; ++k) {
+    const auto& q = l.p[k];
+    WgProblemT<T>& p = g.p[k] = ps[q.which];
+    p.m_tiles = q.m_tiles, p.n_tiles = q.n_tiles, p.ksteps_per = q.ksteps_per, p.splitk = q.splitk;
+    if (q.shared_c) p.shared_c = 1;
+    g.base[k + 1] = g.base[k] + q.m_tiles * q.n_tiles * q.splitk;
+  }
+  hipLaunchKernelGGL((wgrad_kernel<WgElem<T>, BN>), dim3((unsigned)l.grid), dim3(kWgThreads), 0, st, g);
+  return fh_launch_status();
 }
 
 template <class T>
 int launch_wgrad(const WgProblemT<T>* ps, int n, hipStream_t st) {
   if (n <= 0) return FHVAE_OK;
-  int wide[256], narrow[256], nw = 0, nn = 0;  // (mirrored by wgrad_plan in tests/gemm_plan.py)
-  if (n > 256) return FHVAE_ERR_LIMIT;
-  for (int k = 0; k < n; ++k) {
-    if (!wgrad_eligible(ps[k])) return FHVAE_ERR_ALIGN;
-    if (ps[k].N > 128)
-      wide[nw++] = k;
-    else
-      narrow[nn++] = k;
+  constexpr int kMaxLaunches = 256 / kMaxWgProblems + 1;  // of 256 problems in two tile classes
+  fhvae_wgrad_plan pl[kMaxLaunches];
+  const int launches = plan_wgrad(ps, n, pl, kMaxLaunches);
+  for (int i = 0; i < launches; ++i) {
+    const int e = pl[i].BN == 256 ? launch_class<T, 256>(ps, pl[i], st) : launch_class<T, 128>(ps, pl[i], st);
+    if (e) return e;
   }
-  int e = launch_class<T, 256>(ps, wide, nw, st);
-  if (e) return e;
-  return launch_class<T, 128>(ps, narrow, nn, st);
+  return launches < 0 ? launches : FHVAE_OK;
 }
 
 template bool wgrad_eligible<u16>(const WgProblem&);
@@ -379,6 +407,27 @@ static int wgrad_entry(const T* a, int64_t lda, const T* b, int64_t ldb, float* 
   p.M = (int)M, p.N = (int)N, p.K = (int)K;
   if (!wgrad_eligible(p)) return FHVAE_ERR_ALIGN;
   return launch_wgrad(&p, 1, (hipStream_t)stream);
+}
+
+template <class T>
+static int plan_descs(const fhvae_wgrad_desc* x, int n, fhvae_wgrad_plan* out, int cap) {
+  std::vector<WgProblemT<T>> ps(n, WgProblemT<T>{});
+  for (int i = 0; i < n; ++i) {
+    for (const int64_t v : {x[i].M, x[i].N, x[i].K, x[i].a_col0})
+      if (v != (int)v) return FHVAE_ERR_LIMIT;
+    ps[i].A = (const T*)x[i].a, ps[i].B = (const T*)x[i].b, ps[i].C = x[i].c;
+    ps[i].lda = x[i].lda, ps[i].ldb = x[i].ldb, ps[i].ldc = x[i].ldc;
+    ps[i].M = (int)x[i].M, ps[i].N = (int)x[i].N, ps[i].K = (int)x[i].K, ps[i].a_col0 = (int)x[i].a_col0;
+  }
+  return plan_wgrad(ps.data(), n, out, cap);
+}
+
+extern "C" int fhvae_plan_wgrad(const fhvae_wgrad_desc* x, int n, int dtype, fhvae_wgrad_plan* out, int cap) {
+  if (n <= 0) return 0;
+  FH_CHECK_PTR(x);
+  FH_CHECK_PTR(out);
+  if (dtype != FHVAE_F32 && dtype != FHVAE_BF16) return FHVAE_ERR_DTYPE;
+  return dtype == FHVAE_BF16 ? plan_descs<u16>(x, n, out, cap) : plan_descs<float>(x, n, out, cap);
 }
 
 // C[M,N] (f32, ldc) += A[K,M]^T . B[K,N]: operands with the contraction index as the ROW of both (lda, ldb in elements, multiples

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libfhvae_hip.so")
 
 F32, BF16 = 0, 1
 MAX_LAYERS = 4
-ABI_VERSION = 11  # FHVAE_ABI_VERSION of include/fhvae_hip.h
+ABI_VERSION = 12  # FHVAE_ABI_VERSION of include/fhvae_hip.h
 #: ``2*exp(pz2_logvar)`` evaluated exactly like simple_fhvae.py:88,:120 (numpy float32 arithmetic)
 PZ2_LOGVAR = np.log(0.5 ** 2).astype(np.float32)
 INV_TWO_VAR = float(np.float32(1.0) / (np.float32(2.0) * np.exp(PZ2_LOGVAR)))
@@ -80,6 +80,28 @@ class WgradDesc(C.Structure):
 
 
 #: every symbol include/fhvae_hip.h declares: name -> (restype, argtypes)
+class ProjPlan(C.Structure):
+    _fields_ = [("BM", _i32), ("BN", _i32), ("tiles", _i32)]
+
+
+class WgradPlanProblem(C.Structure):
+    _fields_ = [(k, _i32) for k in ("which", "m_tiles", "n_tiles", "ksteps_per", "splitk", "shared_c")]
+
+
+class WgradPlan(C.Structure):
+    _fields_ = [("BN", _i32), ("sk", _i32), ("grid", _i32), ("n", _i32), ("p", WgradPlanProblem * 16)]
+
+
+class GemmDesc(C.Structure):
+    _fields_ = [("a", _vp * 2), ("b", _vp * 2), ("lda", _i64 * 2), ("ldb", _i64 * 2), ("c", _vp), ("c2", _vp), ("clp", _vp), ("ldc", _i64),
+                ("ldclp", _i64), ("M", _i32), ("N", _i32), ("K", _i32 * 2), ("a_kc", _i32 * 2), ("b_kc", _i32 * 2), ("splitk", _i32), ("mode", _i32)]
+
+
+class GemmPlan(C.Structure):
+    _fields_ = [(k, _i32) for k in ("first", "n", "status", "variant", "BM", "BN", "CH", "akc", "bkc")] + [
+        ("grid", C.c_uint32 * 3), ("splitk", _i32 * 4), ("mode", _i32 * 4)]
+
+
 SIGNATURES = {
     "fhvae_abi_version": (C.c_int, []),
     "fhvae_strerror": (C.c_char_p, [C.c_int]),
@@ -112,6 +134,9 @@ SIGNATURES = {
     "fhvae_wgrad_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "fhvae_wgrad_f32": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "fhvae_proj_bf16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "fhvae_plan_proj": (C.c_int, [_i64, _i64, _vp]),
+    "fhvae_plan_wgrad": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
+    "fhvae_plan_gemm": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "fhvae_mu2_gather_fwd": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "fhvae_mu2_gather_bwd": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp]),
     "fhvae_shard_pack": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),

@@ -879,11 +879,11 @@ def _run_refusal(r):
     return tr, ei
 
 
-#: declared by the header but not called from hip_binding.py (tests and tools ask the library for its tile sizes themselves;
+#: declared by the header but not called from hip_binding.py (tests and tools ask the library for its tile sizes and launch plans themselves;
 #: load_library, which the stub stands in for, checks the version; the f32 head's backward is one fused call, so the
 #: stand-alone fhvae_gauss_reparam_bwd has no caller)
 NOT_CALLED = {"fhvae_abi_version", "fhvae_strerror", "fhvae_gauss_reparam_bwd", "fhvae_feats_tile_rows", "fhvae_kaldi_fbank_tile_rows", "fhvae_synth_tile_rows",
-              "fhvae_resample_tile_rows", "fhvae_mel_invert_tile_rows"}
+              "fhvae_resample_tile_rows", "fhvae_mel_invert_tile_rows", "fhvae_plan_proj", "fhvae_plan_wgrad", "fhvae_plan_gemm"}
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,7 @@
 """CPU side of the matrix-product oracle tests (tests/test_gemm_oracle_gpu.py):
-  coverage     the dispatch mirrors of tests/gemm_plan.py say which compiled branch each GPU case reaches; every branch the
-               three launchers can take must be reached by a row of the GPU file's case tables (remove a row and this fails);
+  coverage     the library's own launch plans (fhvae_plan_proj / _wgrad / _gemm through tests/matmul_plan_sweep.py) say which
+               compiled branch each GPU case reaches; every branch the three launchers can take must be reached by a row of the
+               GPU file's case tables (remove a row and this fails);
   sensitivity  the comparator and the canary check reject the errors a kernel could hide, with an f32 emulation (blocked f32
                products, split-K partials added one by one into c0) standing in for the kernel;
   noise floor  the unfaulted emulation stays below the comparator's constants from K = 1 to K = 40960 and 1 to 40 slices;
@@ -10,7 +11,7 @@ import ctypes as C
 import pytest
 import torch
 
-import gemm_plan as GP
+import matmul_plan_sweep as GP
 import head_elbo_compare as HC
 import test_gemm_oracle_gpu as G
 from oracle import gemm_ref as GR
@@ -35,6 +36,13 @@ def test_proj_cases_reach_every_instantiation():
     res = {(M % p[0], p[0]) for (M, _, _), p in plans.items()}
     assert any(r == 1 for r, _ in res) and any(r == bm - 1 for r, bm in res)  # the last row tile: one row, all but one
     assert {(K // 64) % 2 for _, _, K in plans} == {0, 1}  # the two-stage loop ends on either LDS object
+
+
+def _wgrad_desc_ok(K, M, N, lda, ldb, ldc, a_col0=0, bf16=True):
+    """fhvae_wgrad_desc_ok (bf16 operands); for f32 operands the plan query's own eligibility and the same `ldc >= N`."""
+    lib, hb = GP.library()
+    d = hb.WgradDesc(GP.P, lda, a_col0, GP.P, ldb, GP.P, ldc, M, N, K)
+    return lib.fhvae_wgrad_desc_ok(C.byref(d)) == 1 if bf16 else GP.wgrad_launches([d], False)[0] == 1 and ldc >= N
 
 
 def _wg_tags(K, M, N, bf16):
@@ -63,7 +71,7 @@ def test_wgrad_cases_reach_every_branch_in_both_tile_classes(bf16):
     have = {128: set(), 256: set()}
     for K, M, N, _, _ in G.WGRAD_CASES:
         lda, ldb = G.wgrad_lds(M, N)
-        assert GP.wgrad_desc_ok(K, M, N, lda, ldb, N, 0, bf16)
+        assert _wgrad_desc_ok(K, M, N, lda, ldb, N, 0, bf16)
         BN, t = _wg_tags(K, M, N, bf16)
         have[BN] |= t
     for BN in (128, 256):
@@ -94,9 +102,9 @@ def test_grouped_cases_reach_the_grouping_logic():
     for probs in G.GROUPS.values():
         for K, M, N, _ in probs:
             lda, ldb = G.wgrad_lds(M, N)
-            assert GP.wgrad_desc_ok(K, M, N, lda, ldb, N + 7)
+            assert _wgrad_desc_ok(K, M, N, lda, ldb, N + 7)
     K, D, N = G.PAIR["K"], G.PAIR["D"], G.PAIR["N"]
-    assert D == 40 and (2 * D) % 8 == 0 and all(GP.wgrad_desc_ok(K, D, N, 2 * D + 8, N + 8, N + 7, i * D) for i in range(2))
+    assert D == 40 and (2 * D) % 8 == 0 and all(_wgrad_desc_ok(K, D, N, 2 * D + 8, N + 8, N + 7, i * D) for i in range(2))
 
 
 LINEAR_REQUIRED = {
@@ -147,7 +155,7 @@ def test_linear_cases_reach_every_gemm_plan_outcome():
             assert pl["dw"] == "slow" or pl["dw"][2] == dw_split, (M, K, N)
             have |= _linear_tags(M, K, N, relu)
     assert have == LINEAR_REQUIRED, (sorted(LINEAR_REQUIRED - have), sorted(have - LINEAR_REQUIRED))
-    # the mirror's own branches that no linear layer takes: bf16 long-K weight gradients and mixed bf16 orientations
+    # the plan's branches that no linear layer takes: bf16 long-K weight gradients and mixed bf16 orientations
     assert GP.gemm_plan(1024, 256, 40960, 0, 0, 1024, 256, auto=True, dtype="bf16")[:4] == ((128, 64), 16, 16, 32)
     assert GP.gemm_plan(64, 64, 64, 1, 0, 64, 64, dtype="bf16") == "slow"
     assert GP.auto_splitk(192, 100) == 1 and GP.auto_splitk(4, 3) == 1 and GP.auto_splitk(1, 1000) == 128
@@ -232,19 +240,14 @@ def test_noise_floor_is_below_the_constants(dt):
 # fhvae_wgrad_desc_ok (csrc/lstm.hip wg_from_desc -> csrc/wgrad.hip wgrad_eligible)
 # ---------------------------------------------------------------------------------------------
 def test_wgrad_desc_ok_at_its_boundaries():
-    import build_ext
-
-    build_ext.build(verbose=False)
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    P = 1 << 20  # a 16-byte aligned address; nothing is dereferenced
+    lib, hb = GP.library()
+    P = GP.P  # a 16-byte aligned address; nothing is dereferenced
 
     def ok(K, M, N, lda, ldb, ldc, a_col0=0, a=P):
         d = hb.WgradDesc(a, lda, a_col0, P, ldb, P, ldc, M, N, K)
         got = lib.fhvae_wgrad_desc_ok(C.byref(d))
-        if a == P:
-            assert bool(got) == GP.wgrad_desc_ok(K, M, N, lda, ldb, ldc, a_col0), (K, M, N, lda, ldb, ldc, a_col0)
+        # the plan query refuses what the launcher refuses: the same rule, without wg_from_desc's `ldc >= N`
+        assert bool(got) == (GP.wgrad_launches([d], True)[0] == 1 and ldc >= N), (K, M, N, lda, ldb, ldc, a_col0)
         return got
 
     K30 = (1 << 30) // (512 * 2)  # K lda 2 == 2^30 at lda = 512

@@ -4,8 +4,8 @@ hip_binding.raw_linear_fwd / raw_linear_bwd -- against the float64 oracle of the
 launch branch.  The comparator and its constants are the heads' (tests/head_elbo_compare.py: check_contraction, check_bias,
 HEAD["bf16"] / HEAD["f32"]): per element |err| <= c U sqrt(K) (|A| |B| + |c0| + |bias|), 64 x 64 tile bins.
 
-The case tables below are chosen with the dispatch mirrors of tests/gemm_plan.py; tests/test_gemm_oracle_cpu.py proves on the
-CPU that they reach every compiled branch, and every GPU case asserts the branch it was chosen for.
+The case tables below are chosen with the library's launch plans (tests/matmul_plan_sweep.py); tests/test_gemm_oracle_cpu.py
+proves on the CPU that they reach every compiled branch, and every GPU case asserts the branch it was chosen for.
 
 Every case: the operands are the leading rows and columns of wider and taller allocations whose every other element is NaN
 (leading-dimension padding, k-rows past K of KM operands, k-columns [K, ld) of KC operands: what the kernel may address but
@@ -30,7 +30,7 @@ import ctypes as C
 import pytest
 import torch
 
-import gemm_plan as GP
+import matmul_plan_sweep as GP
 import head_elbo_compare as HC
 from oracle import gemm_ref as GR
 
@@ -132,7 +132,7 @@ WGRAD_CASES = [
     (1, 256, 256, 0, 0), (7, 40, 24, 0, 0), (100, 300, 130, 0, 0), (70, 300, 260, 0, 0), (129, 520, 129, 0, 0),
     (197, 256, 128, 0, 0), (576, 264, 72, 0, 0),
     (100, 300, 130, 3, 5), (197, 256, 128, 3, 5),  # ldc > N, one per tile class: nothing outside C[:M, :N] is written
-    # what the mirror asks for beyond those (tests/test_gemm_oracle_cpu.py lists the properties per element type and tile class):
+    # what the coverage test asks for beyond those (tests/test_gemm_oracle_cpu.py lists the properties per element type and tile class):
     # K % BK in {0, 1, BK - 1} for BK = 64 and 32, a short last slice, a grid of 16 or more that is no multiple of 8
     (1537, 264, 24, 0, 0), (63, 40, 24, 0, 0), (2047, 40, 520, 0, 0), (64, 40, 130, 0, 0), (383, 40, 520, 0, 0),
 ]

@@ -29,7 +29,7 @@ def test_symbols_declared_exported_bound(lib):
     for n in NAMES:
         assert re.search(r"\b%s\s*\(" % n, text), n
         assert hasattr(lib, n) and n in hb.SIGNATURES
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
 
 
 def test_argument_errors_on_the_host(lib):

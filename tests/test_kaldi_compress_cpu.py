@@ -286,7 +286,7 @@ def test_symbols_cli_and_argument_errors():
     text = open(os.path.join(ROOT, "include", "fhvae_hip.h")).read()
     for name in ("fhvae_kaldi_decompress", "fhvae_kaldi_compress"):
         assert name + "(" in text and hasattr(lib, name) and name in hb.SIGNATURES
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
     assert lib.fhvae_kaldi_decompress(None, 0, None, 0, 0, None, 0, 0, None, None) == -1
     assert lib.fhvae_kaldi_compress(None, 0, 0, None, 0, 0, None, None, 0, None, None) == -1
     assert hb.KALDI_CM_DESC.itemsize == 40 and "FHVAE_KALDI_CM_TILE_ROWS %d" % hb.KALDI_CM_TILE_ROWS in text

@@ -297,7 +297,7 @@ def test_symbols_and_argument_errors_before_launch(lib):
     text = open(os.path.join(ROOT, "include", "fhvae_hip.h")).read()
     for name in ("fhvae_kaldi_fbank_fwd", "fhvae_kaldi_fbank_tile_rows"):
         assert name + "(" in text and hasattr(lib, name) and name in hb.SIGNATURES
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
     buf = (ctypes.c_float * 4096)()
     p = ctypes.cast(buf, ctypes.c_void_p)
     base = dict(wave=p, n_samples=4000, wave_ptr=p, frame_ptr=p, ids=p, U=1, n_frames=23, dft=p, mel=p, N=400, S=160, P=512, n_mels=80,

@@ -203,7 +203,7 @@ def test_abi_argument_errors_before_launch(lib):
     tr = lib.fhvae_mel_invert_tile_rows
     assert tr(80, 201) == 64 and tr(40, 201) == 64 and tr(40, 101) == 64 and tr(80, 276) == 32 and tr(256, 1025) == 8
     assert tr(0, 201) == 0 and tr(257, 201) == 0 and tr(80, 1) == 0 and tr(80, 1026) == 0
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
 
 
 def test_binding_refuses_cpu_tensors():

@@ -181,7 +181,7 @@ def test_library_refuses_bad_arguments_before_any_launch(F):
     import hip_binding as hb
 
     lib = hb.load_library()
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
     buf = (ctypes.c_float * 4096)()
     p = ctypes.cast(buf, ctypes.c_void_p)
     ok = dict(n_in=100, U=1, n_rows=1, L=2, M=1, P=8, KP=256, WL=63, ratio=2.0, n_exc=0, alt_taps=0, alt_wl=0, n_out=200)

@@ -204,7 +204,7 @@ def test_synth_abi_argument_errors_before_launch(lib):
 
     assert lib.fhvae_synth_tile_rows(400) == 64 and lib.fhvae_synth_tile_rows(200) == 64 and lib.fhvae_synth_tile_rows(551) == 64
     assert lib.fhvae_synth_tile_rows(2048) == 16 and lib.fhvae_synth_tile_rows(1) == 0 and lib.fhvae_synth_tile_rows(2049) == 0
-    assert lib.fhvae_abi_version() == 11
+    assert lib.fhvae_abi_version() == 12
 
 
 def test_binding_refuses_cpu_tensors():
