@@ -7,9 +7,13 @@ namespace fh {
 // The first FHVAE_LSTM_SYNC_BYTES of the bf16 workspace (fhvae_lstm_desc.lp) are the kernels' sync block (u32 words):
 constexpr int kSyncStatus = 0;    // 0 = ok; bit 0: a bounded spin gave up, bit 1: a workgroup could not read its XCD
 constexpr int kSyncSticky = 2;    // two words: address of fhvae_lstm_desc.sticky_status (0 = none), written when the block is armed
-constexpr int kSyncXcdCnt = 16;   // 8 arrival counters (one per XCD): ticket & 31 = a workgroup's slot on its XCD, ticket >> 5 = the launch
 constexpr int kSyncFlags = 64;    // + cluster * 32: one word per workgroup of the cluster = the last step it has published
-constexpr int kSyncWordsUsed = 3072;  // the words the operand cast re-arms: the cluster kernels' flags end at kSyncFlags + 64 * 32; the last
+// 8 arrival counters, one per XCD, at kSyncXcdCnt + XCD * kSyncXcdStride (words 2112, 2144, .. 2336, behind the flags): ticket & 31 =
+// a workgroup's slot on its XCD, ticket >> 5 = the launch.  ONE 128-byte line per counter: returning atomics on one line are
+// serialised at the memory side, and a launch takes 256 tickets before its first step
+constexpr int kSyncXcdCnt = kSyncFlags + 64 * 32;
+constexpr int kSyncXcdStride = 32;
+constexpr int kSyncWordsUsed = 3072;  // the words the operand cast re-arms: flags to word 2111, tickets to 2367, the rest unused; the last
                                       // quarter of the block (from byte 12288) is the phase-clock log of the profiling tools
 // The block is zeroed once per forward (by the operand-cast launch that precedes every bf16 forward); the launches that then
 // share it -- forward chunks, later the backward's, however often it runs -- number themselves: every launch takes 32 tickets

@@ -39,7 +39,7 @@ __device__ __forceinline__ int cluster_join(unsigned* sync, int* s_word) {
     const unsigned x = xcc_id();
     int v = -1;
     if (x < 8) {
-      const unsigned ticket = __hip_atomic_fetch_add(sync + kSyncXcdCnt + x, 1u, RLX_AGENT);
+      const unsigned ticket = __hip_atomic_fetch_add(sync + kSyncXcdCnt + x * kSyncXcdStride, 1u, RLX_AGENT);
       v = (int)(((ticket >> 5) << 8) | (x * 32 + (ticket & 31u)));
     }
     if (v < 0) cluster_give_up(sync, 2u);
