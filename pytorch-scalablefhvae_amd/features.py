@@ -46,6 +46,16 @@ and Kaldi's filterbank features (csrc/kaldi_fbank.hip: fhvae_kaldi_fbank_fwd), n
                       the symmetric window, the HTK mel triangles over bins 0 .. P/2 - 1 and the kernel's padded bases
   compute_kaldi_fbank a list of waveforms -> a list of (nframes, num-mel-bins) float32 arrays (dither by Philox, reproducible)
 
+and energy voice-activity detection (csrc/vad.hip, include/fhvae_vad.h; the binding is vad.py):
+
+  energy_vad          the reference's AudioUtils.energy_vad (utils.py:275-300): centred RMS per frame, voiced above th_ratio times
+                      the utterance's mean -> one bool array per waveform
+  kaldi_vad_options   a Kaldi config file of the four --vad-* options or a dict -> the full option set
+  kaldi_energy_vad    compute-vad-decision on Kaldi's raw log energy (snip-edges frames, no dither)
+  vad_decide          the decision alone, on energies that come from anywhere
+  compute_features / compute_kaldi_fbank (..., vad=...) return (features, decisions) from the waveform already on the device,
+                      with drop=True only the voiced rows (selected on the device, in front of the download / the compression)
+
 Utterances shorter than n_fft // 2 + 1 samples are an error (one reflection of the centre padding must suffice; numpy's
 repeated reflection for shorter inputs is not reproduced).
 """
@@ -648,9 +658,9 @@ def _download(out, statuses, what, ptr):
     return [r[ptr[j]:ptr[j + 1]].copy() for j in range(len(ptr) - 1)]
 
 
-def _feats_batch(hb, wave_d, lens, n_fft, hop, n_mels, ftype, bases, device, what, statuses=()):
+def _feats_batch(hb, wave_d, lens, n_fft, hop, n_mels, ftype, bases, device, what, statuses=(), vad=None):
     """fhvae_feats_fwd on the concatenated waveforms of `lens` samples on the device -> their features; `statuses`: the status
-    words of what ran before it on the stream."""
+    words of what ran before it on the stream.  `vad` (a _vad_spec): -> (features, decisions), see _vad_finish."""
     import torch
 
     frame_ptr = _ptr(num_frames(lens, n_fft, hop))
@@ -658,12 +668,14 @@ def _feats_batch(hb, wave_d, lens, n_fft, hop, n_mels, ftype, bases, device, wha
     out = torch.empty((int(frame_ptr[-1]), n_mels if ftype == "fbank" else n_fft // 2 + 1), dtype=torch.float32, device=device)
     status = torch.zeros(1, dtype=torch.int32, device=device)
     hb.feats_fwd(wave_d, ptrs_d[0], ptrs_d[1], bases.dft, bases.mel, n_fft, hop, n_mels, ftype, out, status)
+    if vad is not None:
+        return _vad_finish(wave_d, ptrs_d, frame_ptr, out, vad, tuple(statuses) + (status,), what)
     return _download(out, tuple(statuses) + (status,), what, frame_ptr)
 
 
-def _run_batch(hb, waves, n_fft, hop, n_mels, ftype, bases, device):
+def _run_batch(hb, waves, n_fft, hop, n_mels, ftype, bases, device, vad=None):
     return _feats_batch(hb, _upload(waves, device), np.array([len(w) for w in waves], dtype=np.int64), n_fft, hop, n_mels, ftype,
-                        bases, device, "fhvae_feats_fwd: status %d (inconsistent wave_ptr / frame_ptr)")
+                        bases, device, "fhvae_feats_fwd: status %d (inconsistent wave_ptr / frame_ptr)", vad=vad)
 
 
 def batches(lengths, max_samples=BATCH_SAMPLES):
@@ -736,14 +748,14 @@ def resample(waves, sr_in, sr_out, device="cuda", max_samples=BATCH_SAMPLES):
     return out
 
 
-def _features_resampled(hb, waves, rd, n_fft, hop, n_mels, ftype, bases, device, names):
+def _features_resampled(hb, waves, rd, n_fft, hop, n_mels, ftype, bases, device, names, vad=None):
     """One batch at a source rate: resampled on the device and handed to fhvae_feats_fwd there (no host round trip)."""
     y, olens, status = _resample_batch(hb, waves, rd, device)
     for j, n in enumerate(olens):
         if n < n_fft // 2 + 1:
             raise ValueError("%s: %d samples after resampling; at least n_fft // 2 + 1 = %d are needed" % (names[j], n, n_fft // 2 + 1))
     return _feats_batch(hb, y, olens, n_fft, hop, n_mels, ftype, bases, device,
-                        "fhvae_resample_fwd / fhvae_feats_fwd: status %s (inconsistent pointers)", (status,))
+                        "fhvae_resample_fwd / fhvae_feats_fwd: status %s (inconsistent pointers)", (status,), vad=vad)
 
 
 def _rate_groups(rates, n):
@@ -756,7 +768,7 @@ def _rate_groups(rates, n):
     return groups
 
 
-def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples):
+def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples, vad=None):
     import hip_binding as hb
 
     n_fft, hop = check_params(sr, ftype, win_t, hop_t, n_mels)
@@ -765,10 +777,13 @@ def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names
     banks = {r: resample_bank(r, sr) for r in groups if r != sr}  # (an unsupported ratio fails before any work)
     out = [None] * len(waves)
     bases = None
+    spec = _vad_spec_reference(vad, n_fft, hop) if vad is not None else None
     for r, idx in groups.items():
         if r == sr:
             got = compute_features([waves[j] for j in idx], sr, ftype, win_t, hop_t, n_mels, [names[j] for j in idx], device,
-                                   max_samples)
+                                   max_samples, vad=vad)
+            if vad is not None:
+                got = list(zip(*got))
         else:
             ws = [np.ascontiguousarray(waves[j], dtype=np.float32).reshape(-1) for j in idx]
             if bases is None:
@@ -776,22 +791,27 @@ def _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names
             rd = _ResampleDev(banks[r], device)
             got = []
             for a, b in batches([len(w) for w in ws], max_samples):
-                got.extend(_features_resampled(hb, ws[a:b], rd, n_fft, hop, n_mels, ftype, bases, device,
-                                               [names[j] for j in idx[a:b]]))
+                g = _features_resampled(hb, ws[a:b], rd, n_fft, hop, n_mels, ftype, bases, device, [names[j] for j in idx[a:b]], spec)
+                got.extend(g if vad is None else zip(*g))
         for j, g in zip(idx, got):
             out[j] = g
+    if vad is not None:
+        return [o[0] for o in out], [o[1] for o in out]
     return out
 
 
 def compute_features(waves, sr, ftype="fbank", win_t=0.025, hop_t=0.010, n_mels=80, names=None, device="cuda",
-                     max_samples=BATCH_SAMPLES, rates=None):
+                     max_samples=BATCH_SAMPLES, rates=None, vad=None):
     """Features of every waveform (float32 1-D arrays at rate `sr`) -> list of float32 (nframes, n_mels) for "fbank" or
     (nframes, n_fft // 2 + 1) for "spec", in input order.  Batched into launches of at most `max_samples` samples.
     `names` (optional) label the utterances in error messages.  `rates` (optional, one source rate per waveform): the
     waveforms whose rate is not `sr` are grouped by rate, resampled to `sr` on the device (see resample) and their features
-    computed from the device copy; the others take the same path as without `rates`."""
+    computed from the device copy; the others take the same path as without `rates`.  `vad` (optional, a dict with
+    "th_ratio" (default 1.04 / 2) and "drop" (default False)): -> (features, decisions), the decisions of energy_vad computed
+    from the waveform already on the device (after resampling), one bool array over the utterance's frames each; with drop
+    only the voiced rows of every utterance are selected on the device and downloaded (an utterance may be left with none)."""
     if rates is not None:
-        return _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples)
+        return _compute_features_rates(waves, rates, sr, ftype, win_t, hop_t, n_mels, names, device, max_samples, vad)
     import hip_binding as hb
 
     n_fft, hop = check_params(sr, ftype, win_t, hop_t, n_mels)
@@ -800,13 +820,18 @@ def compute_features(waves, sr, ftype="fbank", win_t=0.025, hop_t=0.010, n_mels=
         if len(w) < n_fft // 2 + 1:
             name = names[j] if names is not None else "utterance %d" % j
             raise ValueError("%s: %d samples; at least n_fft // 2 + 1 = %d are needed" % (name, len(w), n_fft // 2 + 1))
+    spec = _vad_spec_reference(vad, n_fft, hop) if vad is not None else None
     if not waves:
-        return []
+        return [] if vad is None else ([], [])
     bases = _Bases(sr, n_fft, n_mels, ftype, device)
-    out = []
+    out, vads = [], []
     for a, b in batches([len(w) for w in waves], max_samples):
-        out.extend(_run_batch(hb, waves[a:b], n_fft, hop, n_mels, ftype, bases, device))
-    return out
+        got = _run_batch(hb, waves[a:b], n_fft, hop, n_mels, ftype, bases, device, spec)
+        if vad is not None:
+            vads.extend(got[1])
+            got = got[0]
+        out.extend(got)
+    return out if vad is None else (out, vads)
 
 
 # ---------------------------------------------------------------------------------------------------------- synthesis
@@ -1331,7 +1356,7 @@ class _KaldiBases:
         self.mel = torch.from_numpy(kaldi_mel_basis(sr, P, opts["num-mel-bins"], opts["low-freq"], opts["high-freq"])).to(device)
 
 
-def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device, compress=None, names=None):
+def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device, compress=None, names=None, vad=None):
     import torch
 
     N, S, P = sizes
@@ -1349,6 +1374,8 @@ def _kaldi_batch(hb, waves, ids, opts, sizes, seed, bases, device, compress=None
     hb.kaldi_fbank_fwd(wave_d, ptrs_d[0], ptrs_d[1], ids_d, bases.dft, bases.mel, N, S, P, n_mels,
                        opts["preemphasis-coefficient"], dither, seed, flags, out, status)
     what = "fhvae_kaldi_fbank_fwd: status %d (inconsistent wave_ptr / frame_ptr)"
+    if vad is not None:
+        return _vad_finish(wave_d, ptrs_d, frame_ptr, out, vad, (status,), what, compress, names)
     if compress is None:
         return _download(out, (status,), what, frame_ptr)
     st = int(status.cpu().item())
@@ -1398,7 +1425,7 @@ def kaldi_compress(feats, rows, method="auto", names=None):
 
 
 def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, device="cuda", max_samples=BATCH_SAMPLES,
-                        rates=None, compress=None):
+                        rates=None, compress=None, vad=None):
     """Kaldi filterbank features of every waveform -> list of float32 (nframes, num-mel-bins), in input order.  `waves` are
     float32 1-D arrays as read_wav returns them (full scale 1.0; they are put on Kaldi's int16 scale here) at the rate
     sample-frequency of `opts` (what kaldi_fbank_options takes: a config file, a dict, or None for Kaldi's defaults).  `seed` and `stream_ids` (one 64-bit
@@ -1407,7 +1434,11 @@ def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, d
     another rate are first converted with `resample`; without it every waveform is taken to be at sample-frequency, as
     Kaldi refuses other rates.  An utterance shorter than one frame is an error that names it (`names`).  With `compress`
     ("auto", "two-byte" or "one-byte") the features stay on the device, are coded there as Kaldi compressed matrices
-    (kaldi_compress) and come back as kaldi_io_lite.CompressedMatrix (token, header, payload) instead of arrays."""
+    (kaldi_compress) and come back as kaldi_io_lite.CompressedMatrix (token, header, payload) instead of arrays.  `vad`
+    (optional, a dict with "opts" (what kaldi_vad_options takes, default Kaldi's) and "drop" (default False)): ->
+    (features, decisions), the decisions of kaldi_energy_vad computed from the waveform already on the device, one bool array
+    over the utterance's frames each; with drop only the voiced rows are selected on the device, in front of the compression
+    and the download, and an utterance left with none comes back as an empty (0, num-mel-bins) array."""
     if compress is not None:
         import kaldi_io_lite
 
@@ -1434,12 +1465,237 @@ def compute_kaldi_fbank(waves, opts=None, seed=0, stream_ids=None, names=None, d
         if len(w) < sizes[0]:
             raise ValueError("%s: %d samples%s; one frame needs %d (Kaldi would skip the utterance)"
                              % (names[j], len(w), " after resampling" if rates is not None else "", sizes[0]))
+    spec = _vad_spec_kaldi(vad, opts, sizes) if vad is not None else None
     if not waves:
-        return []
+        return [] if vad is None else ([], [])
     import hip_binding as hb
 
     bases = _KaldiBases(opts, sizes[0], sizes[2], device)
+    out, vads = [], []
+    for a, b in batches([len(w) for w in waves], max_samples):
+        got = _kaldi_batch(hb, waves[a:b], ids[a:b], opts, sizes, int(seed), bases, device, compress, names[a:b], spec)
+        if vad is not None:
+            vads.extend(got[1])
+            got = got[0]
+        out.extend(got)
+    return out if vad is None else (out, vads)
+
+
+# ---------------------------------------------------------------------------------------------------------- energy VAD
+# include/fhvae_vad.h holds the definitions; vad.py the binding.  Nothing here runs librosa or a Kaldi binary.
+KALDI_VAD_DEFAULTS = {"vad-energy-threshold": 5.0, "vad-energy-mean-scale": 0.5, "vad-frames-context": 0,
+                      "vad-proportion-threshold": 0.6}
+VAD_MAX_FRAME = 4096  # FHVAE_VAD_MAX_FRAME
+VAD_MAX_CTX = 1024  # FHVAE_VAD_MAX_CTX
+VAD_TH_RATIO = 1.04 / 2  # utils.py:280
+KALDI_VAD_SYNTAX = KALDI_SYNTAX.replace("--num-mel-bins=80", "--vad-energy-threshold=5.5")
+
+
+def kaldi_vad_options(source=None):
+    """The option set of Kaldi's compute-vad-decision from a config file (path) or a dict of option names (dashes, as Kaldi
+    spells them) -> dict with the four options, the defaults of include/fhvae_vad.h filled in.  An unknown option, a value of
+    the wrong kind or outside its range raises ValueError naming the option and the file, as kaldi_fbank_options does."""
+    where = "options"
+    given = {}
+    if source is None:
+        pass
+    elif isinstance(source, dict):
+        given = {str(k).lstrip("-").replace("_", "-"): v for k, v in source.items()}
+    else:
+        where = str(source)
+        try:
+            fh = open(where)
+        except OSError as e:
+            raise ValueError("%s: cannot read the Kaldi VAD configuration (%s); expected a text file with %s"
+                             % (where, e.strerror or e, KALDI_VAD_SYNTAX)) from None
+        with fh:
+            for ln, raw in enumerate(fh, 1):
+                line = raw.split("#", 1)[0].strip()
+                if not line:
+                    continue
+                if not line.startswith("--"):
+                    raise ValueError("%s:%d: %r is not an option; expected %s" % (where, ln, line, KALDI_VAD_SYNTAX))
+                name, _, value = line[2:].partition("=")
+                given[name.strip()] = value.strip()
+    opts = dict(KALDI_VAD_DEFAULTS)
+    for name, value in given.items():
+        if name not in KALDI_VAD_DEFAULTS:
+            raise ValueError("%s: unknown option --%s (supported: %s)" % (where, name, ", ".join(sorted(KALDI_VAD_DEFAULTS))))
+        kind = type(KALDI_VAD_DEFAULTS[name])
+        try:
+            if kind is int and not isinstance(value, str) and int(value) != value:
+                raise ValueError
+            opts[name] = kind(value)
+        except (TypeError, ValueError):
+            raise ValueError("%s: option --%s has the value %r, not a %s" % (where, name, value, kind.__name__)) from None
+    try:
+        check_vad_decision(opts["vad-energy-threshold"], opts["vad-energy-mean-scale"], opts["vad-frames-context"],
+                           opts["vad-proportion-threshold"])
+    except ValueError as e:
+        raise ValueError("%s: %s" % (where, e)) from None
+    return opts
+
+
+def check_vad_decision(thr_abs, mean_scale, ctx, proportion):
+    """ValueError for parameters fhvae_vad_decide refuses."""
+    if not (np.isfinite(thr_abs) and np.isfinite(mean_scale)):
+        raise ValueError("the energy threshold %r and mean scale %r must be finite" % (thr_abs, mean_scale))
+    if int(ctx) != ctx or not 0 <= ctx <= VAD_MAX_CTX:
+        raise ValueError("the frames context %r is not a whole number in [0, %d]" % (ctx, VAD_MAX_CTX))
+    if not 0.0 < proportion <= 1.0:
+        raise ValueError("the proportion threshold %r is outside (0, 1]" % (proportion,))
+
+
+def _vad_dict(vad, allowed):
+    if not isinstance(vad, dict) or set(vad) - set(allowed):
+        raise ValueError("vad must be a dict with the keys %s, got %r" % (", ".join(allowed), vad))
+    return vad
+
+
+def _vad_spec(mode, flags, frame_len, hop, thr_abs, mean_scale, ctx, proportion, drop):
+    check_vad_decision(thr_abs, mean_scale, ctx, proportion)
+    if not 2 <= frame_len <= VAD_MAX_FRAME or hop < 1:
+        raise ValueError("a VAD frame of %d samples every %d is outside [2, %d] / below 1" % (frame_len, hop, VAD_MAX_FRAME))
+    return {"mode": mode, "flags": flags, "frame_len": int(frame_len), "hop": int(hop), "thr_abs": float(thr_abs),
+            "mean_scale": float(mean_scale), "ctx": int(ctx), "proportion": float(proportion), "drop": bool(drop)}
+
+
+def _vad_spec_reference(vad, n_fft, hop):
+    """The reference's convention (utils.py:295-299): centred RMS over the feature's own frames, voiced above th_ratio * mean."""
+    import vad as V
+
+    vad = _vad_dict(vad, ("th_ratio", "drop"))
+    return _vad_spec(V.VAD_RMS_CENTER, 0, n_fft, hop, 0.0, vad.get("th_ratio", VAD_TH_RATIO), 0, 1.0, vad.get("drop", False))
+
+
+def _vad_spec_kaldi(vad, fbank_opts, sizes):
+    """Kaldi's convention: raw log energy over the fbank's own snip-edges frames, ComputeVadEnergy's four options."""
+    import vad as V
+
+    vad = _vad_dict(vad, ("opts", "drop"))
+    o = kaldi_vad_options(vad.get("opts"))
+    return _vad_spec(V.VAD_LOGE_SNIP, V.VAD_REMOVE_DC if fbank_opts["remove-dc-offset"] else 0, sizes[0], sizes[1],
+                     o["vad-energy-threshold"], o["vad-energy-mean-scale"], o["vad-frames-context"], o["vad-proportion-threshold"],
+                     vad.get("drop", False))
+
+
+VAD_WHAT = "fhvae_vad_energy / fhvae_vad_decide / fhvae_vad_select: status %d (inconsistent wave_ptr / frame_ptr / rank)"
+
+
+def _vad_device(wave_d, ptrs_d, n_frames, spec):
+    """Energies and decisions of a batch that is on the device -> (vad uint8, rank int64, status), all on the device."""
+    import torch
+
+    import vad as V
+
+    status = torch.zeros(1, dtype=torch.int32, device=wave_d.device)
+    e = V.energy(wave_d, ptrs_d[0], ptrs_d[1], n_frames, spec["frame_len"], spec["hop"], spec["mode"], spec["flags"], status)
+    vad_d, rank_d = V.decide(e, ptrs_d[1], spec["thr_abs"], spec["mean_scale"], spec["ctx"], spec["proportion"], status)
+    return vad_d, rank_d, status
+
+
+def _vad_host(vad_d, rank_d, status, ptrs_d, frame_ptr, statuses=(), what=None):
+    """Downloads the decisions and the voiced count of every utterance (rank at frame_ptr), which synchronises; a set status
+    word raises.  -> (one bool array per utterance, voiced_ptr (U + 1,) int64)."""
+    voiced_ptr = rank_d[ptrs_d[1]].cpu().numpy()
+    v = vad_d.cpu().numpy()
+    st = tuple(int(s.cpu().item()) for s in statuses)
+    if any(st):
+        raise RuntimeError(what % (st[0] if len(st) == 1 else (st,)))
+    sv = int(status.cpu().item())
+    if sv:
+        raise RuntimeError(VAD_WHAT % sv)
+    return [v[frame_ptr[j]:frame_ptr[j + 1]].astype(bool) for j in range(len(frame_ptr) - 1)], voiced_ptr
+
+
+def _vad_finish(wave_d, ptrs_d, frame_ptr, out, spec, statuses, what, compress=None, names=None):
+    """The end of a feature batch with VAD: the decisions from the waveform on the device, then the features (`out`, on the
+    device) whole, or with drop their voiced rows only (fhvae_vad_select in front of the download / of kaldi_compress).
+    -> (features, decisions)."""
+    import torch
+
+    import vad as V
+
+    vad_d, rank_d, status = _vad_device(wave_d, ptrs_d, int(frame_ptr[-1]), spec)
+    vads, voiced_ptr = _vad_host(vad_d, rank_d, status, ptrs_d, frame_ptr, statuses, what)
+    rows_ptr = frame_ptr
+    if spec["drop"]:
+        out = V.select(out, vad_d, rank_d, int(voiced_ptr[-1]), status)
+        rows_ptr = voiced_ptr
+    if compress is None:
+        feats = _download(out, (status,), VAD_WHAT, rows_ptr)
+    else:
+        sv = int(status.cpu().item())
+        if sv:
+            raise RuntimeError(VAD_WHAT % sv)
+        rows = np.diff(rows_ptr)
+        keep = [j for j in range(len(rows)) if rows[j] > 0]  # (kaldi_compress needs a row)
+        coded = kaldi_compress(out, rows[keep], compress, [names[j] for j in keep] if names is not None else None) if keep else []
+        feats = [np.zeros((0, out.shape[1]), dtype=np.float32) for _ in rows]
+        for j, c in zip(keep, coded):
+            feats[j] = c
+    return feats, vads
+
+
+def _vad_waves(waves, scale, spec, min_len, frames_of, names, device, max_samples):
+    waves = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in waves]
+    for j, w in enumerate(waves):
+        if len(w) < min_len:
+            raise ValueError("%s: %d samples; at least %d are needed" % (names[j] if names is not None else "utterance %d" % j, len(w), min_len))
     out = []
     for a, b in batches([len(w) for w in waves], max_samples):
-        out.extend(_kaldi_batch(hb, waves[a:b], ids[a:b], opts, sizes, int(seed), bases, device, compress, names[a:b]))
+        lens = np.array([len(w) for w in waves[a:b]], dtype=np.int64)
+        frame_ptr = _ptr(frames_of(lens))
+        wave_d = _upload(waves[a:b], device, scale=scale)
+        ptrs_d = _upload_ptrs([_ptr(lens), frame_ptr], device)
+        vad_d, rank_d, status = _vad_device(wave_d, ptrs_d, int(frame_ptr[-1]), spec)
+        out.extend(_vad_host(vad_d, rank_d, status, ptrs_d, frame_ptr)[0])
     return out
+
+
+def energy_vad(waves, sr, win_t=0.025, hop_t=0.010, th_ratio=VAD_TH_RATIO, names=None, device="cuda", max_samples=BATCH_SAMPLES):
+    """The reference's AudioUtils.energy_vad (utils.py:275-300) for every waveform (float32 1-D arrays at rate `sr`, full scale
+    1.0) -> one (frames,) bool array each: the RMS energy of the centred frames of int(sr * win_t) samples every
+    int(sr * hop_t) (librosa.feature.rms), voiced where it exceeds th_ratio times the utterance's mean.  The frames are those
+    of compute_features.  An utterance shorter than win_length // 2 + 1 samples is an error that names it."""
+    n_fft, hop = frame_sizes(sr, win_t, hop_t)
+    spec = _vad_spec_reference({"th_ratio": th_ratio}, n_fft, hop)
+    return _vad_waves(waves, None, spec, n_fft // 2 + 1, lambda n: num_frames(n, n_fft, hop), names, device, max_samples)
+
+
+def kaldi_energy_vad(waves, fbank_opts=None, vad_opts=None, names=None, device="cuda", max_samples=BATCH_SAMPLES):
+    """compute-vad-decision for every waveform (float32 1-D arrays at full scale 1.0, at the sample-frequency of `fbank_opts`)
+    -> one (frames,) bool array each.  The frames are those of compute_kaldi_fbank for `fbank_opts` (frame-length, frame-shift,
+    snip-edges; remove-dc-offset applies to the energy too); the energy is Kaldi's raw log energy without dither; `vad_opts` is
+    what kaldi_vad_options takes."""
+    opts = kaldi_fbank_options(fbank_opts)
+    sizes = check_kaldi_options(opts)
+    spec = _vad_spec_kaldi({"opts": vad_opts}, opts, sizes)
+    return _vad_waves(waves, 32768.0, spec, sizes[0], lambda n: kaldi_num_frames(n, sizes[0], sizes[1]), names, device, max_samples)
+
+
+def vad_decide(energies, thr_abs, mean_scale, ctx, proportion, device="cuda"):
+    """The decision of include/fhvae_vad.h on energies that come from anywhere (a list of 1-D arrays, one per utterance, each
+    with at least one frame; they are rounded to float32) -> one bool array each:
+    voiced where at least `proportion` of the frames within `ctx` of it exceed thr_abs + mean_scale * the utterance's mean."""
+    import torch
+
+    import vad as V
+
+    check_vad_decision(thr_abs, mean_scale, ctx, proportion)
+    energies = [np.ascontiguousarray(e, dtype=np.float32).reshape(-1) for e in energies]
+    if not energies:
+        return []
+    for j, e in enumerate(energies):
+        if len(e) < 1:
+            raise ValueError("utterance %d has no frame" % j)
+    frame_ptr = _ptr([len(e) for e in energies])
+    e_d = _upload(energies, device)
+    ptr_d = _upload_ptrs([frame_ptr], device)
+    status = torch.zeros(1, dtype=torch.int32, device=e_d.device)
+    vad_d, _ = V.decide(e_d, ptr_d[0], thr_abs, mean_scale, ctx, proportion, status)
+    v = vad_d.cpu().numpy()
+    sv = int(status.cpu().item())
+    if sv:
+        raise RuntimeError(VAD_WHAT % sv)
+    return [v[frame_ptr[j]:frame_ptr[j + 1]].astype(bool) for j in range(len(energies))]

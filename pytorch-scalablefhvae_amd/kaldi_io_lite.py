@@ -21,12 +21,17 @@ The device decode (fhvae_kaldi_decompress) evaluates the same operations in the 
   read_raw("path:offset" | "path")           (token, min_value, range, rows, cols, payload) without decoding
   read_ark(path)                             iterates (key, matrix) over a binary archive
   write_len_scp(path, items)                 "key nframes" per line (feat-to-len scp:... ark,t:...)
+  write_vec_ark_scp(ark_path, scp_path, items)   (key, vector) pairs -> an archive of float vectors and its scp
+  load_vec("path:offset" | "path") / read_vec_ark(path)   one float vector; iterates (key, vector)
+
+A float vector entry (what compute-vad-decision writes as vad.ark) is
+    key, one space, "\\0B", the token "FV " (float32) or "DV " (float64), "\\4" + int32 dim, dim little-endian values.
 
 A compressed header with range <= 0, a non-finite min_value or range, or a non-positive size is refused.  Kaldi writes
 an EMPTY compressed matrix as an all-zero header: it falls under the range <= 0 refusal (an utterance without frames
 has no place in a corpus).
 
-Not built: text archives, vectors, piped ("... |") script entries, Kaldi's fixed-range integer compression methods;
+Not built: text archives, integer vectors, piped ("... |") script entries, Kaldi's fixed-range integer compression methods;
 each is refused with a message that says which and where.
 """
 from __future__ import annotations
@@ -296,3 +301,71 @@ def write_len_scp(path, items):
     with open(path, "w") as fh:
         for key, n in items:
             fh.write("%s %d\n" % (key, int(n)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- vectors
+_VEC_TOKENS = {b"FV": np.dtype("<f4"), b"DV": np.dtype("<f8")}
+
+
+def write_vec_ark_scp(ark_path, scp_path, items):
+    """Writes every (key, vector) of `items` to the binary archive `ark_path` as a float32 vector ("FV ") and one
+    "key ark_path:offset" line per entry to `scp_path` (compute-vad-decision's vad.ark / vad.scp).  Returns the number of entries."""
+    count = 0
+    with open(ark_path, "wb") as ark, open(scp_path, "w") as scp:
+        for key, vec in items:
+            key = str(key)
+            if not key or any(c.isspace() for c in key):
+                raise ValueError("%r is not a Kaldi key (empty or with blanks)" % key)
+            v = np.ascontiguousarray(vec, dtype="<f4")
+            if v.ndim != 1:
+                raise ValueError("%s: a vector is 1-D, got shape %s" % (key, v.shape))
+            ark.write(key.encode("utf-8") + b" ")
+            scp.write("%s %s:%d\n" % (key, ark_path, ark.tell()))
+            ark.write(b"\0BFV " + b"\4" + struct.pack("<i", v.shape[0]) + v.tobytes())
+            count += 1
+    return count
+
+
+def _read_vector(fh, where):
+    """The vector whose "\\0B" header starts at the current position of `fh`."""
+    if fh.read(2) != b"\0B":
+        raise ValueError("%s: not a binary Kaldi vector (text archives are not supported; write with ark, not ark,t)" % where)
+    tok = fh.read(3)
+    if len(tok) != 3 or tok[2:3] != b" " or tok[:2] not in _VEC_TOKENS:
+        raise ValueError("%s: %r is not a vector token (FV or DV)" % (where, tok.decode("latin-1")))
+    dims = fh.read(5)
+    if len(dims) != 5 or dims[0:1] != b"\4":
+        raise ValueError("%s: bad vector header" % where)
+    dim = struct.unpack("<i", dims[1:5])[0]
+    if dim < 0:
+        raise ValueError("%s: negative vector size %d" % (where, dim))
+    dt = _VEC_TOKENS[tok[:2]]
+    raw = fh.read(dim * dt.itemsize)
+    if len(raw) != dim * dt.itemsize:
+        raise ValueError("%s: the file ends inside a vector of %d" % (where, dim))
+    return np.frombuffer(raw, dtype=dt).astype(dt.newbyteorder("="))
+
+
+def load_vec(rxfilename):
+    """The float vector an scp value names: "path:offset" (offset of the entry's "\\0B") or "path"."""
+    path, off = _open_spec(rxfilename)
+    with open(path, "rb") as fh:
+        fh.seek(int(off))
+        return _read_vector(fh, "%s:%s" % (path, off))
+
+
+def read_vec_ark(path):
+    """Iterates (key, vector) over the binary archive of float vectors at `path`."""
+    with open(path, "rb") as fh:
+        while True:
+            key = b""
+            while True:
+                c = fh.read(1)
+                if not c:
+                    if key.strip():
+                        raise ValueError("%s: the file ends inside a key" % path)
+                    return
+                if c == b" ":
+                    break
+                key += c
+            yield key.decode("utf-8"), _read_vector(fh, "%s:%d" % (path, fh.tell()))

@@ -3,7 +3,7 @@
 features.compute_kaldi_fbank on the MI355X and kaldi_io_lite; no Kaldi binary is run).
 
     python pytorch-scalablefhvae_amd/prepare_kaldi_data.py DATASET_DIR [--fbank_conf ./misc/fbank.conf] [--set_name train]
-        [--seed 0] [--resample] [--compress [--compression-method auto]] [--verify-md5]
+        [--seed 0] [--resample] [--compress [--compression-method auto]] [--verify-md5] [--vad {mark,drop} [--vad_conf FILE]]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<key> <path>"
 lines) and writes, in wav.scp order, <DATASET_DIR>/<set>/feats.ark (binary archive of float32 matrices), feats.scp
@@ -18,6 +18,14 @@ one option per line, for example
     --num-mel-bins=80
 
 (features.kaldi_fbank_options lists what is supported).
+
+With --vad the frames are marked voiced or not as compute-vad-decision does (features.kaldi_energy_vad: Kaldi's raw log energy
+of the fbank's own frames, no dither; --vad_conf is a config file of the four --vad-* options, features.kaldi_vad_options), on
+the GPU from the waveform the features are computed from.  Both modes write the decisions of every utterance over its
+ORIGINAL frames as float vectors (1.0 / 0.0) to <DATASET_DIR>/<set>/vad.ark and vad.scp.  "mark" leaves feats.ark, feats.scp
+and len.scp what a run without the flag writes; "drop" keeps the voiced rows only (select-voiced-frames: selected on the GPU
+in front of the compression and the download; len.scp then holds the voiced count), skips an utterance without a voiced
+frame, naming it on stderr, and closes with one line that counts the skipped utterances and the share of frames dropped.
 
 Differences from the reference:
   * --kaldi_root is accepted and ignored.
@@ -48,6 +56,7 @@ import kaldi_io_lite  # noqa: E402
 
 READ_THREADS = 8  # file reads overlapping the GPU work (of the 16 CPUs a job gets; not sized by os.cpu_count())
 CHUNK_FILES = 512  # files read ahead of the batch being computed
+VAD_MODES = (None, "mark", "drop")
 
 
 def read_wav_scp(path):
@@ -67,17 +76,27 @@ def read_wav_scp(path):
 
 
 def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None,
-                  compress=None, verify_md5=False):
+                  compress=None, verify_md5=False, vad=None, vad_conf=None):
     """prepare_kaldi_data.py:10-82: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (dataset_dir, feats.ark, feats.scp, len.scp)).  `timings` (optional dict) receives seconds spent in
-    "read", "gpu" and "write".  `compress`: None (float32 matrices) or a method of kaldi_io_lite.METHODS."""
+    "read", "gpu" and "write".  `compress`: None (float32 matrices) or a method of kaldi_io_lite.METHODS.  `vad`: None, "mark"
+    or "drop" (the module docstring) with `vad_conf`, what features.kaldi_vad_options takes; then the result's second entry
+    also holds vad.ark and vad.scp, and `count` counts the utterances written."""
+    if vad not in VAD_MODES:
+        raise ValueError("vad must be one of %s, got %r" % (", ".join(str(m) for m in VAD_MODES), vad))
+    if vad is None and vad_conf is not None:
+        raise ValueError("--vad_conf needs --vad {mark,drop}")
     opts = features.kaldi_fbank_options(fbank_conf)
+    vad_opts = features.kaldi_vad_options(vad_conf) if vad is not None else None
     sr = int(opts["sample-frequency"])
     set_dir = Path(dataset_dir) / set_name
     wav_path = set_dir / "wav.scp"
     if not os.path.exists(wav_path):
         raise ValueError(f"The wav.scp file at {wav_path} does not exist!")
     feat_ark, feat_scp, len_scp = set_dir / "feats.ark", set_dir / "feats.scp", set_dir / "len.scp"
+    vad_ark, vad_scp = set_dir / "vad.ark", set_dir / "vad.scp"
+    decisions = []  # (key, float vector) of every utterance, in wav.scp order (one byte per 10 ms of audio)
+    stats = {"skipped": 0, "in": 0, "out": 0}
     entries = read_wav_scp(wav_path)
     t = {} if timings is None else timings
     for k in ("read", "gpu", "write"):
@@ -108,11 +127,21 @@ def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_r
                 feats = features.compute_kaldi_fbank([g[2] for g in got], opts, seed=seed,
                                                      stream_ids=[features.kaldi_stream_id(g[0]) for g in got],
                                                      names=["%s (%s)" % (g[0], g[1]) for g in got],
-                                                     rates=[g[3] for g in got] if resample else None, compress=compress)
+                                                     rates=[g[3] for g in got] if resample else None, compress=compress,
+                                                     **({} if vad is None else {"vad": {"opts": vad_opts, "drop": vad == "drop"}}))
+                feats, vads = feats if vad is not None else (feats, [None] * len(got))
                 dt = time.time() - t0
                 t["gpu"] += dt
                 t0 = time.time()
-                for g, feat in zip(got, feats):
+                for g, feat, v in zip(got, feats, vads):
+                    if v is not None:
+                        decisions.append((g[0], v.astype("float32")))
+                        stats["in"] += len(v)
+                        stats["out"] += len(feat)
+                        if vad == "drop" and len(feat) == 0:
+                            print(f"prepare_kaldi_data: {g[0]} ({g[1]}) has no voiced frame: skipped", file=sys.stderr)
+                            stats["skipped"] += 1
+                            continue
                     lens.append((g[0], len(feat)))
                     yield g[0], feat
                     if len(lens) % 1000 == 0:
@@ -122,6 +151,14 @@ def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_r
     count = kaldi_io_lite.write_ark_scp(str(feat_ark), str(feat_scp), items())
     kaldi_io_lite.write_len_scp(len_scp, lens)
     print(f"Processed {count} files in {set_name} set over {time.time() - start_time} seconds.")
+    if vad is not None:
+        kaldi_io_lite.write_vec_ark_scp(str(vad_ark), str(vad_scp), decisions)
+    if vad == "drop":
+        print("Skipped %d of %d utterances without a voiced frame; dropped %d of %d frames (%.1f%%) in the %s set."
+              % (stats["skipped"], count + stats["skipped"], stats["in"] - stats["out"], stats["in"],
+                 100.0 * (stats["in"] - stats["out"]) / max(stats["in"], 1), set_name))
+    if vad is not None:
+        return count, (Path(dataset_dir), feat_ark, feat_scp, len_scp, vad_ark, vad_scp)
     return count, (Path(dataset_dir), feat_ark, feat_scp, len_scp)
 
 
@@ -138,11 +175,18 @@ def build_parser():
     p.add_argument("--compress", action="store_true", help="Write Kaldi compressed matrices (coded on the GPU), as copy-feats --compress=true does")
     p.add_argument("--compression-method", type=str, default="auto", choices=list(kaldi_io_lite.METHODS),
                    help="With --compress: Kaldi's automatic method (one byte with column headers; two bytes up to 8 frames), or two or one byte per value")
+    p.add_argument("--vad", type=str, default=None, choices=["mark", "drop"],
+                   help="Energy VAD on the GPU (compute-vad-decision): write vad.ark / vad.scp (mark), or also keep the voiced frames only (drop, select-voiced-frames)")
+    p.add_argument("--vad_conf", type=str, default=None,
+                   help="With --vad: Kaldi config file of --vad-energy-threshold, --vad-energy-mean-scale, --vad-frames-context, --vad-proportion-threshold")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.vad_conf is not None and args.vad is None:
+        parser.error("--vad_conf needs --vad {mark,drop}")
     print(args)
     if args.kaldi_root is not None:
         print("--kaldi_root is ignored: the features are computed on the GPU, no Kaldi binary is run")
@@ -152,7 +196,8 @@ def main(argv=None):
     try:
         for s in sets:
             total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample,
-                                   compress=args.compression_method if args.compress else None, verify_md5=args.verify_md5)[0]
+                                   compress=args.compression_method if args.compress else None, verify_md5=args.verify_md5,
+                                   vad=args.vad, vad_conf=args.vad_conf)[0]
     except ValueError as e:
         print("prepare_kaldi_data: %s" % e, file=sys.stderr)
         return 1

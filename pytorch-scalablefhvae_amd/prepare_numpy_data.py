@@ -3,10 +3,19 @@ prepare_numpy_data.py:50-205, with the features computed on the MI355X by featur
 
     python pytorch-scalablefhvae_amd/prepare_numpy_data.py DATASET_DIR [--np_dir OUT] [--set_name train]
         [--ftype {fbank,spec}] [--sr RATE] [--resample] [--win_t 0.025] [--hop_t 0.010] [--n_mels 80] [--verify-md5]
+        [--vad {mark,drop} [--vad_th_ratio 0.52]]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<seq> <path>"
 lines) and writes, in wav.scp order, <OUT>/<set>/<seq>.npy (float32, (nframes, n_mels) or (nframes, n_fft // 2 + 1)) plus
 <OUT>/<set>/feats.scp ("<seq> <path.npy>") and <OUT>/<set>/len.scp ("<seq> <nframes>"); OUT is --np_dir or DATASET_DIR.
+
+With --vad the reference's AudioUtils.energy_vad (utils.py:275-300; features.energy_vad, th_ratio = --vad_th_ratio) decides for
+every frame whether it is voiced, on the GPU from the waveform the features are computed from.  Both modes write the
+decisions of every sequence over its ORIGINAL frames: <OUT>/<set>/<seq>.vad.npy (uint8 0 / 1, (nframes,)) plus vad.scp
+("<seq> <path.vad.npy>").  "mark" leaves the features, feats.scp and len.scp what a run without the flag writes; "drop" keeps
+the voiced rows only (selected on the GPU in front of the download; len.scp then holds the voiced count), skips a sequence
+without a voiced frame, naming it on stderr, and closes with one line that counts the skipped sequences and the share of
+frames dropped, as Kaldi's select-voiced-frames does.
 
 Differences from the reference:
   * wav.scp is read from DATASET_DIR even when --np_dir is given (the reference looks for it under the output directory,
@@ -23,6 +32,7 @@ from __future__ import annotations
 
 import argparse
 import concurrent.futures as cf
+import contextlib
 import os
 import sys
 import time
@@ -38,6 +48,7 @@ import features  # noqa: E402
 
 READ_THREADS = 8  # file reads overlapping the GPU work (of the 16 CPUs a job gets; not sized by os.cpu_count())
 CHUNK_FILES = 512  # files read ahead of the batch being computed
+VAD_MODES = (None, "mark", "drop")
 
 
 def read_wav_scp(path):
@@ -46,10 +57,14 @@ def read_wav_scp(path):
 
 
 def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank", sample_rate=None, win_t=0.025, hop_t=0.010,
-                  n_mels=80, timings=None, resample=False, verify_md5=False):
+                  n_mels=80, timings=None, resample=False, verify_md5=False, vad=None, vad_th_ratio=features.VAD_TH_RATIO):
     """prepare_numpy_data.py:50-129: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (wav_path, feat_path, len_path)).  `timings` (optional dict) receives seconds spent in "read", "gpu"
-    and "write".  `resample`: files whose rate differs from `sample_rate` (required then) are converted to it on the GPU."""
+    and "write".  `resample`: files whose rate differs from `sample_rate` (required then) are converted to it on the GPU.
+    `vad`: None, "mark" or "drop" (the module docstring); then the result's third entry is
+    (wav_path, feat_path, len_path, vad_path) and `count` counts the sequences written."""
+    if vad not in VAD_MODES:
+        raise ValueError("vad must be one of %s, got %r" % (", ".join(str(m) for m in VAD_MODES), vad))
     if resample and sample_rate is None:
         raise ValueError("--resample needs --sr, the target sample rate")
     wav_path = Path(dataset_dir) / set_name / "wav.scp"
@@ -57,7 +72,8 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
     if not os.path.exists(wav_path):
         raise ValueError(f"The wav.scp file at {wav_path} does not exist!")
     os.makedirs(set_path, exist_ok=True)
-    feat_path, len_path = set_path / "feats.scp", set_path / "len.scp"
+    feat_path, len_path, vad_path = set_path / "feats.scp", set_path / "len.scp", set_path / "vad.scp"
+    skipped = frames_in = frames_out = 0
     entries = read_wav_scp(wav_path)
     t = {"read": 0.0, "gpu": 0.0, "write": 0.0} if timings is None else timings
     for k in ("read", "gpu", "write"):
@@ -70,7 +86,8 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
         return [(seq, path, y, sr) for (seq, path), (y, sr) in zip(chunk, got)]
 
     chunks = [entries[i:i + CHUNK_FILES] for i in range(0, len(entries), CHUNK_FILES)]
-    with cf.ThreadPoolExecutor(max_workers=1) as pool, open(feat_path, "w") as featfile, open(len_path, "w") as lenfile:
+    with cf.ThreadPoolExecutor(max_workers=1) as pool, open(feat_path, "w") as featfile, open(len_path, "w") as lenfile, \
+            (open(vad_path, "w") if vad is not None else contextlib.nullcontext()) as vadfile:
         pending = pool.submit(load, chunks[0]) if chunks else None
         for ci in range(len(chunks)):
             t0 = time.time()
@@ -89,10 +106,23 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
             t0 = time.time()
             feats = features.compute_features([g[2] for g in got], sample_rate, ftype, win_t, hop_t, n_mels,
                                               names=["%s (%s)" % (g[0], g[1]) for g in got],
-                                              rates=[g[3] for g in got] if resample else None)
+                                              rates=[g[3] for g in got] if resample else None,
+                                              **({} if vad is None else {"vad": {"th_ratio": vad_th_ratio, "drop": vad == "drop"}}))
+            feats, vads = feats if vad is not None else (feats, [None] * len(got))
             t["gpu"] += time.time() - t0
             t0 = time.time()
-            for (seq, _, _, _), feat in zip(got, feats):
+            for (seq, path, _, _), feat, v in zip(got, feats, vads):
+                if v is not None:
+                    v_path = os.path.join(set_path, f"{seq}.vad.npy")
+                    with open(v_path, "wb") as numpyfile:
+                        np.save(numpyfile, v.astype(np.uint8))
+                    vadfile.write(f"{seq} {v_path}\n")
+                    frames_in += len(v)
+                    frames_out += len(feat)
+                    if vad == "drop" and len(feat) == 0:
+                        print(f"prepare_numpy_data: {seq} ({path}) has no voiced frame: skipped", file=sys.stderr)
+                        skipped += 1
+                        continue
                 np_path = os.path.join(set_path, f"{seq}.npy")
                 with open(np_path, "wb") as numpyfile:
                     np.save(numpyfile, feat)
@@ -103,6 +133,11 @@ def prepare_numpy(dataset, set_name, dataset_dir, output_dir=None, ftype="fbank"
                     print(f"{count} {set_name} files in {time.time() - start_time} seconds.")
             t["write"] += time.time() - t0
     print(f"Processed {count} files in {set_name} set over {time.time() - start_time} seconds.")
+    if vad == "drop":
+        print("Skipped %d of %d sequences without a voiced frame; dropped %d of %d frames (%.1f%%) in the %s set."
+              % (skipped, count + skipped, frames_in - frames_out, frames_in, 100.0 * (frames_in - frames_out) / max(frames_in, 1), set_name))
+    if vad is not None:
+        return count, (wav_path, feat_path, len_path, vad_path)
     return count, (wav_path, feat_path, len_path)
 
 
@@ -121,6 +156,10 @@ def build_parser():
     p.add_argument("--win_t", type=float, default=0.025, help="Window size in seconds")
     p.add_argument("--hop_t", type=float, default=0.010, help="Frame spacing in seconds")
     p.add_argument("--n_mels", type=int, default=80, help="Number of filter banks if choosing fbank")
+    p.add_argument("--vad", type=str, default=None, choices=["mark", "drop"],
+                   help="Energy VAD on the GPU: write every sequence's decisions (mark), or also keep the voiced frames only (drop)")
+    p.add_argument("--vad_th_ratio", type=float, default=None,
+                   help="With --vad: a frame is voiced above this ratio of the mean RMS energy (default 1.04 / 2)")
     return p
 
 
@@ -129,13 +168,18 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.resample and args.sr is None:
         parser.error("--resample needs --sr, the target sample rate")
+    if args.vad_th_ratio is not None and args.vad is None:
+        parser.error("--vad_th_ratio needs --vad {mark,drop}")
+    if args.vad_th_ratio is not None and not (args.vad_th_ratio == args.vad_th_ratio and abs(args.vad_th_ratio) != float("inf")):
+        parser.error("--vad_th_ratio must be finite")
     print(args)
     sets = ["train", "dev", "test"] if args.set_name is None else [args.set_name]
     t0 = time.time()
     total = 0
     for s in sets:
         total += prepare_numpy(args.dataset, s, args.dataset_dir, args.np_dir, args.ftype, args.sr, args.win_t, args.hop_t,
-                               args.n_mels, resample=args.resample, verify_md5=args.verify_md5)[0]
+                               args.n_mels, resample=args.resample, verify_md5=args.verify_md5, vad=args.vad,
+                               vad_th_ratio=features.VAD_TH_RATIO if args.vad_th_ratio is None else args.vad_th_ratio)[0]
     if len(sets) > 1:
         print(f"Processed {total} files in {time.time() - t0} seconds.")
     return 0

@@ -1,7 +1,7 @@
 """utils.py -- the parts of the reference's utils.py that touch the hot path's state (utils.py:14-152):
 checkpoint layout, args pickle, and the closed-form mu2 estimate (run naming, utils.py:20-42, is CLI plumbing: not built).  AudioUtils's
-feature extraction (stft / rstft / to_melspec, utils.py:155-272) is features.py and the fhvae_feats_fwd kernel; energy_vad
-(utils.py:275-300) is not built.
+feature extraction (stft / rstft / to_melspec, utils.py:155-272) is features.py and the fhvae_feats_fwd kernel; AudioUtils.energy_vad
+(utils.py:275-300) is here with the reference's signature, on features.energy_vad and the kernels of csrc/vad.hip.
 """
 from __future__ import annotations
 
@@ -71,6 +71,20 @@ def overlap_mean(segments, seg_len, seg_shift, nframes):
         k = torch.where(ok, k, last)
         acc = acc + torch.where(ok.unsqueeze(1), segments[k, t - k * seg_shift], torch.zeros_like(acc))
     return acc / (last - first + 1).to(acc.dtype).unsqueeze(1), covered
+
+
+class AudioUtils:
+    """The one AudioUtils function that is not a feature (those are features.py): utils.py:275-300."""
+
+    @staticmethod
+    def energy_vad(y, sr, hop_t=0.010, win_t=0.025, th_ratio=1.04 / 2):
+        """utils.py:275-300: energy-based voice activity detection of one waveform `y` (1-D, full scale 1.0) at rate `sr` ->
+        a (1, frames) integer array, 1 where the frame's RMS energy (librosa.feature.rms, centred frames of int(sr * win_t)
+        samples every int(sr * hop_t)) exceeds th_ratio times the utterance's mean.  Computed on the device
+        (features.energy_vad; include/fhvae_vad.h states the arithmetic)."""
+        import features
+
+        return features.energy_vad([np.asarray(y).reshape(-1)], sr, win_t, hop_t, th_ratio)[0].astype(int)[None, :]
 
 
 def save_args(exp_dir, args):
