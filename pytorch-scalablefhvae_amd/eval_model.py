@@ -31,6 +31,14 @@ the seed and the final KL divergence of both maps.  With the speakers known (--u
 importable, tsne_mu2.png and tsne_z1_mean.png are scatter plots with one colour per speaker: one island per speaker on mu2 and
 none on z1_mean is what a factorized model shows.
 
+With --abx-item FILE (a ZeroSpeech / ABXpy .item file, abx.read_items; needs --feat-scp data) the other half of the factorization
+is measured: the ABX phone discrimination error (abx.py) of the frame-level z1 -- frames.encode_frames over every utterance at
+shift 1, one row per frame -- and, as the baseline, of the normalised input features.  A token's frames are those whose time
+--abx-frame-offset + f * --abx-frame-shift lies in [onset, offset].  summary.json gains "abx": {"z1": {within, across,
+cells_within, cells_across, triples_within, triples_across}, "feats": {...}, "tokens", "dropped", "distance", "frame_shift",
+"frame_offset"} (--abx-on chooses which of the two), and abx_by_pair_<on>.tsv lists every ordered phone pair with its within-
+and across-speaker score.  A z1 that keeps the phone and loses the speaker scores below the features, most of all across speakers.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -84,6 +92,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tsne-perplexity", type=float, default=30.0, help="at most (sequences - 1) / 3")
     p.add_argument("--tsne-iters", type=int, default=1000)
     p.add_argument("--tsne-seed", type=int, default=0, help="seed of the initial map")
+    p.add_argument("--abx-item", default=None, metavar="FILE", help="ABX phone discriminability of the tokens this .item file lists (needs --feat-scp)")
+    p.add_argument("--abx-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to score: frame-level z1, the input features")
+    p.add_argument("--abx-distance", default="angular", choices=["angular", "cosine"], help="frame cost under the DTW")
+    p.add_argument("--abx-frame-shift", type=float, default=0.010, help="seconds between frames")
+    p.add_argument("--abx-frame-offset", type=float, default=0.0,
+                   help="time of frame 0 in seconds (0.0125 for Kaldi snip-edges frames of 25 ms, whose centres lie half a window in)")
+    p.add_argument("--abx-max-per-cell", type=int, default=20, help="tokens kept per (phone, context, speaker), the first in file order; 0: all")
     return p
 
 
@@ -102,6 +117,12 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--tsne-iters %d must be at least 1" % args.tsne_iters)
     if args.tsne_seed < 0 or args.tsne_seed >= 2 ** 32:
         p.error("--tsne-seed %d must lie in [0, 2^32)" % args.tsne_seed)
+    if args.abx_item is not None and args.feat_scp is None:
+        p.error("--abx-item lists tokens of --feat-scp data: give --feat-scp")
+    if not args.abx_frame_shift > 0:
+        p.error("--abx-frame-shift %g must be positive" % args.abx_frame_shift)
+    if args.abx_max_per_cell < 0:
+        p.error("--abx-max-per-cell %d must not be negative" % args.abx_max_per_cell)
     return args
 
 
@@ -162,6 +183,32 @@ def draw_tsne(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
             if not T.scatter_png(os.path.join(out_dir, "tsne_%s.png" % name), maps[name], labels, "t-SNE of %s by speaker" % name):
                 print("--tsne: matplotlib is not installed, no tsne_*.png (the maps are in tsne_*.npy and tsne.tsv)")
                 break
+    return block
+
+
+def measure_abx(args, model, T, out_dir, dev):
+    """--abx-item: abx_by_pair_<on>.tsv and the "abx" block of summary.json (see the module docstring)."""
+    import abx
+    import frames
+
+    pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
+    tokens = abx.tokens_from_items(abx.read_items(args.abx_item), pool.keys, pool.lengths, args.abx_frame_shift, args.abx_frame_offset,
+                                   max_per_cell=args.abx_max_per_cell)
+    block = {}
+    for on in dict.fromkeys(args.abx_on):
+        if on == "z1":
+            rows = frames.encode_frames(model, pool, args.batch_size)[0]  # (shift 1: row f is frame f)
+        else:
+            rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
+        if rows.shape[1] > abx.ABX_MAX_DIM:
+            raise ValueError("%s has %d values per frame, the DTW kernel takes at most %d" % (on, rows.shape[1], abx.ABX_MAX_DIM))
+        res = abx.evaluate(rows.contiguous(), tokens, args.abx_distance)
+        abx.write_by_pair(os.path.join(out_dir, "abx_by_pair_%s.tsv" % on), res, tokens["phones"])
+        block[on] = {k: (None if isinstance(res[k], float) and np.isnan(res[k]) else res[k])
+                     for k in ("within", "across", "cells_within", "cells_across", "triples_within", "triples_across")}
+        del rows
+    block.update({"tokens": int(tokens["start"].shape[0]), "dropped": tokens["dropped"], "distance": args.abx_distance,
+                  "frame_shift": args.abx_frame_shift, "frame_offset": args.abx_frame_offset})
     return block
 
 
@@ -337,6 +384,13 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("--tsne: %s" % e, file=sys.stderr)
             return 1
+    abx_block = None
+    if args.abx_item is not None:
+        try:
+            abx_block = measure_abx(args, model, T, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("--abx-item: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -354,6 +408,8 @@ def main(argv=None) -> int:
         summary["speaker_verification"] = sv
     if tsne_block is not None:
         summary["tsne"] = tsne_block
+    if abx_block is not None:
+        summary["abx"] = abx_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

@@ -125,14 +125,11 @@ def main(argv=None) -> int:
         return 1
     import frames
     import hip_binding as hb
-    from datasets import KaldiDataset, NumpyDataset
 
     dev = torch.device("cuda:0")
     model = model.to(dev)
-    Dataset = NumpyDataset if args.data_format == "numpy" else KaldiDataset
-    ds = Dataset(args.feat_scp, args.len_scp, 0, args.mvn_path, T, args.shift, False)  # min_len 0: no key is dropped
     try:
-        pool = frames.FramePool(ds, T, args.shift, device=dev)
+        pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, args.shift, dev)
     except ValueError as e:
         print("extract_latents: %s" % e, file=sys.stderr)
         return 1

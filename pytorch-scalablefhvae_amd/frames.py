@@ -279,6 +279,16 @@ class FramePool:
         return [rows[int(a):int(b)] for a, b in zip(self.win_ptr_host[:-1], self.win_ptr_host[1:])]
 
 
+def pool_from_scp(data_format: str, feat_scp, len_scp, mvn_path, T: int, shift: int = 1, device="cuda") -> FramePool:
+    """The corpus a --feat-scp / --len-scp pair names ("numpy" or "kaldi"), resident: every key kept (min_len 0), the MVN
+    statistics of mvn_path.  What extract_latents.py and eval_model.py --abx-item work on."""
+    from datasets import KaldiDataset, NumpyDataset
+
+    Dataset = NumpyDataset if data_format == "numpy" else KaldiDataset
+    ds = Dataset(feat_scp, len_scp, 0, mvn_path, T, shift, False)  # min_len 0: no key is dropped
+    return FramePool(ds, T, shift, device=device)
+
+
 # ------------------------------------------------------------------------------------------------------------ model drivers
 def _check_model(model, pool):
     T = int(getattr(model, "seg_len", pool.T))
