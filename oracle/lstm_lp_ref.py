@@ -4,8 +4,10 @@ Explicit forward and backward (no autograd: the backward rounds at points the fo
 documented LSTM equations, gate order (i, f, g, o):
     pre_t = [x_t | xc] W_ih^T + h_{t-1} W_hh^T + b_ih + b_hh,  c_t = f c_{t-1} + i g,  h_t = o tanh(c_t).
 
-rb(v) = v.float().bfloat16().double(): f32 first, then round to nearest even (f2bf, csrc/common.h).  With rounding=True the
-model is the one every bf16 schedule shares:
+rb(v) = v.float().bfloat16().double(): f32 first, then round to nearest even (f2bf, csrc/common.h).  The element-wise step
+between the contractions is the one definition every schedule calls, lstm_point_fwd / lstm_point_bwd (csrc/lstm_point.h), here
+in float64 (its f32 roundings are below what this oracle resolves).  With rounding=True the model is the one every bf16
+schedule shares:
   forward   the MFMA operands rb([x_t | xc]), rb(W_ih), rb(h_{t-1}), rb(W_hh) (csrc/lstm.hip cast_operands; the step cells and the
             persistent kernels store rb(h) as the next step's / layer's operand: lstm_cluster.hip pack4(h), lstm_fwd_wr.hip f2bf(h)),
             exact products, unrounded sums and biases; gates, c and h unrounded (hs_top / hn are the f32 h); the gates saved for
@@ -14,16 +16,17 @@ model is the one every bf16 schedule shares:
             dh = external + rb(dg^{l+1}) rb(W_ih^{l+1}) + rb(dg_{t+1}) rb(W_hh)  (from-above term: proj.hip / the generic engine);
             dW = rb(dg)^T rb(operand) (wgrad.hip over the bf16 dgates and saved bf16 states);
             time-constant input: dgsum = sum_t dg (f32, layer 0), dW_xc = dgsum^T xc and d_xc = dgsum W_xc with the f32 xc and
-            the f32 master weight (lstm.hip:836-838, 908, 930-955: launch_gemm(..., FHVAE_F32));
-            bias gradients: sums of the unrounded dg (lstm_bwd_rs.hip:220 and lstm_cluster.hip:752, 1174 add dp before pack4);
-            layer 0 with a time-constant input: the column sums of dgsum (lstm.hip:919-921).
-Schedule options (each cites the kernel lines that make it):
-  partial_dh_bf16        lstm_bwd_rs.hip:6-41, 184-187, 262: member m (units [64m, 64m+64)) multiplies its own 256 gate
+            the f32 master weight (lstm.hip lstm_param_grads, lstm_dxc: launch_gemm(..., FHVAE_F32));
+            bias gradients: sums of the unrounded dg (lstm_bwd_layer_rs_kernel, lstm_bwd_layer_kernel and lstm_bwd_ksplit_kernel
+            add lstm_point_bwd's dp to dgs before pack4);
+            layer 0 with a time-constant input: the column sums of dgsum (lstm.hip lstm_param_grads).
+Schedule options (each cites the code that makes it):
+  partial_dh_bf16        lstm_bwd_rs.hip (header comment; lstm_bwd_layer_rs_kernel): member m (units [64m, 64m+64)) multiplies its own 256 gate
                          columns of rb(dg_t) by rb(W_hh) for ALL units; the partials for the other members travel as bf16
                          (pack4(acc[rt][j]), j = 1..3), its own stays f32.
-  bias_from_rounded_dg   lstm.hip:922-923: the per-step and large-tile cells leave the bias gradients to launch_colsum over the
+  bias_from_rounded_dg   lstm.hip lstm_param_grads: the per-step and large-tile cells leave the bias gradients to launch_colsum over the
                          saved bf16 dgates: sums of rb(dg) (except layer 0 with a time-constant input, which sums dgsum).
-  dgsum_from_rounded_dg  lstm.hip:803 / lstm_cell.hip:310: the large-tile cells build dgsum from the saved bf16 dgates.
+  dgsum_from_rounded_dg  lstm.hip lstm_bwd_impl / lstm_cell.hip cell_dgsum_kernel: the large-tile cells build dgsum from the saved bf16 dgates.
 rounding=False is a plain float64 LSTM (the oracle of the f32 mode).
 
 `_fault` is for the comparator's own tests only (tests/test_lstm_lp_oracle_cpu.py): a deliberately wrong variant

@@ -16,6 +16,7 @@
 #include "gemm_launch.h"
 #include "lstm_cell.h"
 #include "lstm_cluster.h"
+#include "lstm_point.h"
 #include "wgrad.h"
 #include <algorithm>
 #include <vector>
@@ -133,19 +134,17 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_step_kernel(FwdJobs<T> jobs
         for (int g = 0; g < 4; ++g) pa[g] = fetch_add(row, g);
         cp = J.c_prev ? J.c_prev[(int64_t)row * H + unit] : 0.f;
       }
-      const float ig = sigmoidf_(acc[tm][0][r] + pa[0]), fg = sigmoidf_(acc[tm][1][r] + pa[1]);
-      const float gg = tanhf_(acc[tm][2][r] + pa[2]), og = sigmoidf_(acc[tm][3][r] + pa[3]);
-      const float c = __builtin_fmaf(fg, cp, ig * gg);
-      const float h = og * tanhf_(c);
-      J.c_out[(int64_t)row * H + unit] = c;
+      const LstmPointFwd pt = lstm_point_fwd(acc[tm][0][r] + pa[0], acc[tm][1][r] + pa[1], acc[tm][2][r] + pa[2], acc[tm][3][r] + pa[3], cp);
+      const float h = pt.h;
+      J.c_out[(int64_t)row * H + unit] = pt.c;
       store_h<T>(J.h_out + (int64_t)row * H + unit, h);
       if (J.h_out_f32) J.h_out_f32[(int64_t)row * H + unit] = h;
       if constexpr (kSave) {
         T* go = J.gates_out + (int64_t)row * 4 * H + unit;
-        store_h<T>(go, ig);
-        store_h<T>(go + H, fg);
-        store_h<T>(go + 2 * H, gg);
-        store_h<T>(go + 3 * H, og);
+        store_h<T>(go, pt.ig);
+        store_h<T>(go + H, pt.fg);
+        store_h<T>(go + 2 * H, pt.gg);
+        store_h<T>(go + 3 * H, pt.og);
       }
       if (J.hn_out) J.hn_out[(int64_t)row * J.hn_ld + unit] = h;
     }
@@ -197,22 +196,14 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_step_kernel(BwdJobs<T> jobs
         const T* gp = J.gates + (int64_t)row * 4 * H + unit;
         const float ig = load_h<T>(gp), fg = load_h<T>(gp + H), gg = load_h<T>(gp + 2 * H), og = load_h<T>(gp + 3 * H);
         const float cp = J.c_prev ? J.c_prev[o] : 0.f;
-        const float tc = tanhf_(J.c_cur[o]);
-        float dc = dh * og * (1.f - tc * tc);
-        if (!J.first) dc += J.dc[o];
-        const float d_o = dh * tc;
-        const float d_i = dc * gg, d_f = dc * cp, d_g = dc * ig;
-        J.dc[o] = dc * fg;
-        float dp[4];
-        dp[0] = d_i * ig * (1.f - ig);
-        dp[1] = d_f * fg * (1.f - fg);
-        dp[2] = d_g * (1.f - gg * gg);
-        dp[3] = d_o * og * (1.f - og);
+        const float dc_in = J.first ? 0.f : J.dc[o];
+        const LstmPointBwd pt = lstm_point_bwd(dh, ig, fg, gg, og, J.c_cur[o], cp, !J.first, dc_in);
+        J.dc[o] = pt.dc;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int64_t go = (int64_t)row * 4 * H + g * H + unit;
-          store_h<T>(J.dg_out + go, dp[g]);
-          if (J.dgsum) J.dgsum[go] = J.first ? dp[g] : J.dgsum[go] + dp[g];
+          store_h<T>(J.dg_out + go, pt.dp[g]);
+          if (J.dgsum) J.dgsum[go] = J.first ? pt.dp[g] : J.dgsum[go] + pt.dp[g];
         }
       }
   }

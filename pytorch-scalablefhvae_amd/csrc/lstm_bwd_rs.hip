@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "lstm_cluster_dev.h"
+#include "lstm_point.h"
 #include "trace.h"
 
 namespace fh {
@@ -202,16 +203,10 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_layer_rs_kernel(ClBwd p) {
       f32x4 dp[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float tc = tanhf_(ccur[rt][i]);
-        float dc = dh[rt][i] * og[i] * (1.f - tc * tc);
-        if (s > 0) dc += dcreg[rt][i];
-        const float d_o = dh[rt][i] * tc;
-        const float d_i = dc * gg[i], d_f = dc * cprev[rt][i], d_g = dc * ig[i];
-        dcreg[rt][i] = dc * fg[i];
-        dp[0][i] = d_i * ig[i] * (1.f - ig[i]);
-        dp[1][i] = d_f * fg[i] * (1.f - fg[i]);
-        dp[2][i] = d_g * (1.f - gg[i] * gg[i]);
-        dp[3][i] = d_o * og[i] * (1.f - og[i]);
+        const LstmPointBwd pt = lstm_point_bwd(dh[rt][i], ig[i], fg[i], gg[i], og[i], ccur[rt][i], cprev[rt][i], s > 0, dcreg[rt][i]);
+        dcreg[rt][i] = pt.dc;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dp[g][i] = pt.dp[g];
       }
       ccur[rt] = cprev[rt];
       const bool live = row[rt] < rend;

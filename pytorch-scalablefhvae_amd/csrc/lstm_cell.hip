@@ -11,6 +11,7 @@
 // (conflict-free, guide T2).  Semantics of the cells: lstm.hip (torch.nn.LSTM gate order i,f,g,o; stands where the FC layers of
 // simple_fhvae.py:160-164, :186-190, :240-244 stand).
 #include "lstm_cell_dev.h"
+#include "lstm_point.h"
 
 #include <cstddef>
 #include <cstdlib>
@@ -149,12 +150,11 @@ __global__ __launch_bounds__(kCellThreads, NS <= 2 ? 2 : 1) void cell_fwd_kernel
     float ig[8], fg[8], gg[8], og[8], c[8], h[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      ig[e] = sigmoidf_(x[0][e] + (has_pre ? pa[0][e] : 0.f));
-      fg[e] = sigmoidf_(x[1][e] + (has_pre ? pa[1][e] : 0.f));
-      gg[e] = tanhf_(x[2][e] + (has_pre ? pa[2][e] : 0.f));
-      og[e] = sigmoidf_(x[3][e] + (has_pre ? pa[3][e] : 0.f));
-      c[e] = __builtin_fmaf(fg[e], has_cp ? cp[e] : 0.f, ig[e] * gg[e]);
-      h[e] = og[e] * tanhf_(c[e]);
+      float pre[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pre[g] = x[g][e] + (has_pre ? pa[g][e] : 0.f);
+      const LstmPointFwd pt = lstm_point_fwd(pre[0], pre[1], pre[2], pre[3], has_cp ? cp[e] : 0.f);
+      ig[e] = pt.ig, fg[e] = pt.fg, gg[e] = pt.gg, og[e] = pt.og, c[e] = pt.c, h[e] = pt.h;
     }
     const unsigned o = row * uH + u;
     st8(J.c_out + o, c);
@@ -286,21 +286,14 @@ __global__ __launch_bounds__(kCellThreads, (BM + 64) * 128 * NS <= 80 * 1024 ? 2
     float dcn[8], dp[4][8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      // same order of operations as lstm_bwd_step_kernel (lstm.hip): ext, then ext2
+      // dh's terms are added in the order of lstm_bwd_step_kernel (lstm.hip): ext, then ext2
       float d = dh[e];
       d += has_e1 ? e1[e] : 0.f;
       d += has_e2 ? e2[e] : 0.f;
-      const float cpv = has_cp ? cp[e] : 0.f;
-      const float tc = tanhf_(cc[e]);
-      float dc = d * og[e] * (1.f - tc * tc);
-      dc += first ? 0.f : dcin[e];
-      const float d_o = d * tc;
-      const float d_i = dc * gg[e], d_f = dc * cpv, d_g = dc * ig[e];
-      dcn[e] = dc * fg[e];
-      dp[0][e] = d_i * ig[e] * (1.f - ig[e]);
-      dp[1][e] = d_f * fg[e] * (1.f - fg[e]);
-      dp[2][e] = d_g * (1.f - gg[e] * gg[e]);
-      dp[3][e] = d_o * og[e] * (1.f - og[e]);
+      const LstmPointBwd pt = lstm_point_bwd(d, ig[e], fg[e], gg[e], og[e], cc[e], has_cp ? cp[e] : 0.f, !first, dcin[e]);
+      dcn[e] = pt.dc;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) dp[g][e] = pt.dp[g];
     }
     st8(J.dc + o, dcn);
 #pragma unroll

@@ -34,6 +34,7 @@
 // tolerance of the model tests, and tests/test_lstm_cluster_gpu.py compares the two schedules directly).  f32 (parity
 // mode) stays on the per-step kernels.
 #include "lstm_cluster_dev.h"
+#include "lstm_point.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -403,11 +404,10 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_cluster_kernel(ClFwd p) {
           // chunk c = (tile c / 4, element c % 4) of layer 0's gate math: 10 transcendentals + the cell update of 1 (row, unit)
           auto g0_chunk = [&](int c) {
             const int tm = c >> 2, i = c & 3;
-            const float ig = sigmoidf_(g0v[tm][0][i]), fg = sigmoidf_(g0v[tm][1][i]), gg = tanhf_(g0v[tm][2][i]), og = sigmoidf_(g0v[tm][3][i]);
-            const float cn = __builtin_fmaf(fg, creg[0][tm][i], ig * gg);
-            creg[0][tm][i] = cn;
-            hreg[0][tm][i] = og * tanhf_(cn);
-            g0v[tm][0][i] = ig, g0v[tm][1][i] = fg, g0v[tm][2][i] = gg, g0v[tm][3][i] = og;
+            const LstmPointFwd pt = lstm_point_fwd(g0v[tm][0][i], g0v[tm][1][i], g0v[tm][2][i], g0v[tm][3][i], creg[0][tm][i]);
+            creg[0][tm][i] = pt.c;
+            hreg[0][tm][i] = pt.h;
+            g0v[tm][0][i] = pt.ig, g0v[tm][1][i] = pt.fg, g0v[tm][2][i] = pt.gg, g0v[tm][3][i] = pt.og;
           };
           auto second = [&](auto with_gates) {
             constexpr bool WG = decltype(with_gates)::value;
@@ -478,10 +478,10 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_cluster_kernel(ClFwd p) {
           for (int g = 0; g < 4; ++g) gv[g] = acc[ll][tm][g] + (ll == 0 ? padd[tm][g] : bias[ll][g]);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float ig = sigmoidf_(gv[0][i]), fg = sigmoidf_(gv[1][i]), gg = tanhf_(gv[2][i]), og = sigmoidf_(gv[3][i]);
-            c[i] = __builtin_fmaf(fg, creg[ll][tm][i], ig * gg);  // (explicit: see tanhf_)
-            h[i] = og * tanhf_(c[i]);
-            gv[0][i] = ig, gv[1][i] = fg, gv[2][i] = gg, gv[3][i] = og;
+            const LstmPointFwd pt = lstm_point_fwd(gv[0][i], gv[1][i], gv[2][i], gv[3][i], creg[ll][tm][i]);
+            c[i] = pt.c;
+            h[i] = pt.h;
+            gv[0][i] = pt.ig, gv[1][i] = pt.fg, gv[2][i] = pt.gg, gv[3][i] = pt.og;
           }
           creg[ll][tm] = c;
           hreg[ll][tm] = h;
@@ -738,16 +738,10 @@ __global__ __launch_bounds__(HW ? kThreads + 64 : kThreads) void lstm_bwd_layer_
           f32x4 dp[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float tc = tanhf_(ccur[tm][ut][i]);
-            float dc = dh[i] * og[i] * (1.f - tc * tc);
-            if (s > 0) dc += dcreg[tm][ut][i];
-            const float d_o = dh[i] * tc;
-            const float d_i = dc * gg[i], d_f = dc * cprev[tm][ut][i], d_g = dc * ig[i];
-            dcreg[tm][ut][i] = dc * fg[i];
-            dp[0][i] = d_i * ig[i] * (1.f - ig[i]);
-            dp[1][i] = d_f * fg[i] * (1.f - fg[i]);
-            dp[2][i] = d_g * (1.f - gg[i] * gg[i]);
-            dp[3][i] = d_o * og[i] * (1.f - og[i]);
+            const LstmPointBwd pt = lstm_point_bwd(dh[i], ig[i], fg[i], gg[i], og[i], ccur[tm][ut][i], cprev[tm][ut][i], s > 0, dcreg[tm][ut][i]);
+            dcreg[tm][ut][i] = pt.dc;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) dp[g][i] = pt.dp[g];
           }
           ccur[tm][ut] = cprev[tm][ut];
           if (row < rend) {
@@ -996,10 +990,10 @@ __global__ __launch_bounds__(kThreads) void lstm_fwd_ksplit_kernel(ClFwd p) {
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float ig = sigmoidf_(gv[0][i]), fg = sigmoidf_(gv[1][i]), gg = tanhf_(gv[2][i]), og = sigmoidf_(gv[3][i]);
-        c[i] = __builtin_fmaf(fg, creg[i], ig * gg);
-        hreg[i] = og * tanhf_(c[i]);
-        gv[0][i] = ig, gv[1][i] = fg, gv[2][i] = gg, gv[3][i] = og;
+        const LstmPointFwd pt = lstm_point_fwd(gv[0][i], gv[1][i], gv[2][i], gv[3][i], creg[i]);
+        c[i] = pt.c;
+        hreg[i] = pt.h;
+        gv[0][i] = pt.ig, gv[1][i] = pt.fg, gv[2][i] = pt.gg, gv[3][i] = pt.og;
       }
       creg = c;
 #pragma unroll
@@ -1165,16 +1159,10 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_ksplit_kernel(ClBwd p) {
       f32x4 dp[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float tc = tanhf_(ccur[i]);
-        float dc = dh[i] * og[i] * (1.f - tc * tc);
-        if (t != T - 1) dc += dcreg[i];
-        const float d_o = dh[i] * tc;
-        const float d_i = dc * gg[i], d_f = dc * cprev[i], d_g = dc * ig[i];
-        dcreg[i] = dc * fg[i];
-        dp[0][i] = d_i * ig[i] * (1.f - ig[i]);
-        dp[1][i] = d_f * fg[i] * (1.f - fg[i]);
-        dp[2][i] = d_g * (1.f - gg[i] * gg[i]);
-        dp[3][i] = d_o * og[i] * (1.f - og[i]);
+        const LstmPointBwd pt = lstm_point_bwd(dh[i], ig[i], fg[i], gg[i], og[i], ccur[i], cprev[i], t != T - 1, dcreg[i]);
+        dcreg[i] = pt.dc;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dp[g][i] = pt.dp[g];
       }
       ccur = cprev;
       if (row < rend) {

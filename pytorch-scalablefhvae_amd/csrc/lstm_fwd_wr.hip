@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "lstm_cluster_dev.h"
+#include "lstm_point.h"
 
 #include "trace.h"
 
@@ -347,14 +348,13 @@ __global__ __launch_bounds__(kFwThreads) void lstm_fwd_wr_kernel(ClFwd p) {
     auto cell = [&](auto l_c, int rt) {
       constexpr int l = decltype(l_c)::value;
       const f32x4 v = acc[l][rt] + (l == 0 ? add0 : add1);
-      const float ig = sigmoidf_(v[0]), fg = sigmoidf_(v[1]), gg = tanhf_(v[2]), og = sigmoidf_(v[3]);
-      const float c = __builtin_fmaf(fg, creg[l][rt], ig * gg);  // (explicit: see tanhf_)
-      const float h = og * tanhf_(c);
+      const LstmPointFwd pt = lstm_point_fwd(v[0], v[1], v[2], v[3], creg[l][rt]);
+      const float c = pt.c, h = pt.h;
       creg[l][rt] = c;
       char* st = stage_all + l * kStageL;
       const int row = rt * 16 + r;
       if constexpr (kSave) {
-        *(uint2*)(st + row * kGS + ul * 8) = pack4(f32x4{ig, fg, gg, og});
+        *(uint2*)(st + row * kGS + ul * 8) = pack4(f32x4{pt.ig, pt.fg, pt.gg, pt.og});
         *(float*)(st + ROWS * kGS + row * kCS + ul * 4) = c;
       }
       *(float*)(st + ROWS * (kGS + kCS) + row * kCS + ul * 4) = h;

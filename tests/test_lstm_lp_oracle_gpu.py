@@ -170,7 +170,7 @@ def test_switch_vs_rounding_oracle(hb, name, value, shape, sched):
 
 
 # saturated gates and a growing cell state (input weights and biases x4, inputs x3, T = 40): the fast tanhf_ / sigmoidf_ forms
-# (common.h) in their tails and the dc carry where training takes it.  W_hh keeps its scale: scaled x4 as well, the recurrence
+# (lstm_point.h) in their tails and the dc carry where training takes it.  W_hh keeps its scale: scaled x4 as well, the recurrence
 # stops damping the one-ulp flips of rb(h) (measured: gradient mean errors 2e-4 .. 6e-4 of scale on every schedule, the oracle
 # against itself with f32-level noise alike), and the comparison would measure that chaos instead of the kernels
 @pytest.mark.parametrize("shape,sched", [((1024, 40, 80, 0, 256, 2), "rs"), ((256, 40, 80, 32, 256, 2), "ks"),
