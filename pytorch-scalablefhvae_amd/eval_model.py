@@ -39,6 +39,13 @@ cells_within, cells_across, triples_within, triples_across}, "feats": {...}, "to
 "frame_offset"} (--abx-on chooses which of the two), and abx_by_pair_<on>.tsv lists every ordered phone pair with its within-
 and across-speaker score.  A z1 that keeps the phone and loses the speaker scores below the features, most of all across speakers.
 
+With --units K (needs --feat-scp data) the frames are turned into discrete units (units.py): a k-means codebook of K centroids
+fitted on the frame-level z1 and, as the baseline, on the normalised input features (--units-on chooses; --units-iters,
+--units-seed), one unit per frame.  units_<on>.txt holds one line `key u0 u1 ...` per utterance, units_centroids_<on>.npy the
+codebook, and summary.json gains "units": {"z1": {on, k, frames, iterations, converged, inertia, reseeded, seed, bitrate,
+bitrate_collapsed}, "feats": {...}}; with --units-item FILE (a .item phone alignment; the frame grid is --abx-frame-shift /
+--abx-frame-offset) every sub-block also holds cluster_purity, phone_purity, pnmi, labelled_frames, overlaps and phones.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -99,6 +106,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--abx-frame-offset", type=float, default=0.0,
                    help="time of frame 0 in seconds (0.0125 for Kaldi snip-edges frames of 25 ms, whose centres lie half a window in)")
     p.add_argument("--abx-max-per-cell", type=int, default=20, help="tokens kept per (phone, context, speaker), the first in file order; 0: all")
+    p.add_argument("--units", type=int, default=None, metavar="K", help="discrete units: a k-means codebook of K centroids, one unit per frame (needs --feat-scp)")
+    p.add_argument("--units-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to quantise: frame-level z1, the input features")
+    p.add_argument("--units-iters", type=int, default=100, help="Lloyd iterations, at most")
+    p.add_argument("--units-seed", type=int, default=0, help="seed of the rows the first centroids are copied from")
+    p.add_argument("--units-item", default=None, metavar="FILE", help="phone alignment (.item) to score the units against")
     return p
 
 
@@ -123,6 +135,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--abx-frame-shift %g must be positive" % args.abx_frame_shift)
     if args.abx_max_per_cell < 0:
         p.error("--abx-max-per-cell %d must not be negative" % args.abx_max_per_cell)
+    if args.units is not None and args.feat_scp is None:
+        p.error("--units quantises the frames of --feat-scp data: give --feat-scp")
+    if args.units is not None and args.units < 1:
+        p.error("--units %d must be at least 1" % args.units)
+    if args.units_iters < 1:
+        p.error("--units-iters %d must be at least 1" % args.units_iters)
+    if args.units_seed < 0 or args.units_seed >= 2 ** 32:
+        p.error("--units-seed %d must lie in [0, 2^32)" % args.units_seed)
     return args
 
 
@@ -209,6 +229,27 @@ def measure_abx(args, model, T, out_dir, dev):
         del rows
     block.update({"tokens": int(tokens["start"].shape[0]), "dropped": tokens["dropped"], "distance": args.abx_distance,
                   "frame_shift": args.abx_frame_shift, "frame_offset": args.abx_frame_offset})
+    return block
+
+
+def discover_units(args, model, T, out_dir, dev):
+    """--units: units_<on>.txt, units_centroids_<on>.npy and the "units" block of summary.json (see the module docstring)."""
+    import abx
+    import frames
+    import units
+
+    pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
+    items = abx.read_items(args.units_item) if args.units_item is not None else None
+    block = {}
+    for on in dict.fromkeys(args.units_on):
+        rows, width = units.corpus_rows(model, pool, on, args.batch_size)
+        info, cent, _, seqs = units.discover(rows, width, pool.keys, pool.lengths, on, k=args.units, iters=args.units_iters,
+                                             seed=args.units_seed, items=items, frame_shift=args.abx_frame_shift,
+                                             frame_offset=args.abx_frame_offset)
+        np.save(os.path.join(out_dir, "units_centroids_%s.npy" % on), cent)
+        units.write_units(os.path.join(out_dir, "units_%s.txt" % on), pool.keys, seqs)
+        block[on] = info
+        del rows
     return block
 
 
@@ -391,6 +432,13 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("--abx-item: %s" % e, file=sys.stderr)
             return 1
+    units_block = None
+    if args.units is not None:
+        try:
+            units_block = discover_units(args, model, T, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("--units: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -410,6 +458,8 @@ def main(argv=None) -> int:
         summary["tsne"] = tsne_block
     if abx_block is not None:
         summary["abx"] = abx_block
+    if units_block is not None:
+        summary["units"] = units_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))
