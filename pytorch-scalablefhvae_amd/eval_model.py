@@ -46,6 +46,12 @@ codebook, and summary.json gains "units": {"z1": {on, k, frames, iterations, con
 bitrate_collapsed}, "feats": {...}}; with --units-item FILE (a .item phone alignment; the frame grid is --abx-frame-shift /
 --abx-frame-offset) every sub-block also holds cluster_purity, phone_purity, pnmi, labelled_frames, overlaps and phones.
 
+With --baseline-feat-scp SCP [--baseline-name mfcc] a second Kaldi archive with the same keys and the same frame count per
+utterance (MFCC + deltas + CMVN from prepare_kaldi_data.py --mfcc_conf, the baseline the zero-resource literature quotes) is
+scored as one more entry "<name>" of the "abx" and "units" blocks, with abx_by_pair_<name>.tsv, units_<name>.txt and
+units_centroids_<name>.npy beside those of z1 and feats.  It is taken as it is (not normalised by --mvn-path); a key it lacks or
+another frame count is an error that names the key.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -111,6 +117,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--units-iters", type=int, default=100, help="Lloyd iterations, at most")
     p.add_argument("--units-seed", type=int, default=0, help="seed of the rows the first centroids are copied from")
     p.add_argument("--units-item", default=None, metavar="FILE", help="phone alignment (.item) to score the units against")
+    p.add_argument("--baseline-feat-scp", default=None, metavar="SCP",
+                   help="a second Kaldi archive (same keys, same frames per utterance) scored beside z1 and feats under --abx-item / --units")
+    p.add_argument("--baseline-name", default=None, help="the baseline's entry in summary.json and its files' suffix (default mfcc)")
     return p
 
 
@@ -143,6 +152,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--units-iters %d must be at least 1" % args.units_iters)
     if args.units_seed < 0 or args.units_seed >= 2 ** 32:
         p.error("--units-seed %d must lie in [0, 2^32)" % args.units_seed)
+    if args.baseline_name is not None and args.baseline_feat_scp is None:
+        p.error("--baseline-name needs --baseline-feat-scp")
+    if args.baseline_feat_scp is not None:
+        if args.abx_item is None and args.units is None:
+            p.error("--baseline-feat-scp is scored by --abx-item and --units: give one of them")
+        args.baseline_name = "mfcc" if args.baseline_name is None else args.baseline_name
+        if args.baseline_name in ("z1", "feats") or not args.baseline_name.replace("_", "").replace("-", "").isalnum():
+            p.error("--baseline-name %r: letters, digits, - and _, and neither z1 nor feats" % args.baseline_name)
     return args
 
 
@@ -206,6 +223,32 @@ def draw_tsne(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
     return block
 
 
+def baseline_rows(args, pool, dev):
+    """--baseline-feat-scp: the archive's matrices in the order of the pool's utterances, stacked on the device -> (frames, D)
+    f32.  A key the archive lacks, or a matrix whose row count is not the utterance's frame count, raises ValueError naming it."""
+    import kaldi_io_lite
+
+    specs = {}
+    with open(args.baseline_feat_scp) as fh:
+        for ln, line in enumerate(fh, 1):
+            parts = line.rstrip().split(None, 1)
+            if not parts:
+                continue
+            if len(parts) != 2:
+                raise ValueError("%s:%d: expected \"<key> <archive:offset>\"" % (args.baseline_feat_scp, ln))
+            specs[parts[0]] = parts[1]
+    mats = []
+    for key, n in zip(pool.keys, pool.lengths):
+        if key not in specs:
+            raise ValueError("%s has no entry for %s" % (args.baseline_feat_scp, key))
+        m = np.asarray(kaldi_io_lite.load_mat(specs[key]), dtype=np.float32)
+        if m.ndim != 2 or len(m) != int(n) or (mats and m.shape[1] != mats[0].shape[1]):
+            raise ValueError("%s: %s in %s, but %d frames in %s%s" % (key, "x".join(str(d) for d in m.shape), args.baseline_feat_scp, int(n), args.feat_scp,
+                                                                     "" if not mats else " and %d columns before" % mats[0].shape[1]))
+        mats.append(m)
+    return torch.from_numpy(np.concatenate(mats, axis=0)).to(dev)
+
+
 def measure_abx(args, model, T, out_dir, dev):
     """--abx-item: abx_by_pair_<on>.tsv and the "abx" block of summary.json (see the module docstring)."""
     import abx
@@ -215,9 +258,12 @@ def measure_abx(args, model, T, out_dir, dev):
     tokens = abx.tokens_from_items(abx.read_items(args.abx_item), pool.keys, pool.lengths, args.abx_frame_shift, args.abx_frame_offset,
                                    max_per_cell=args.abx_max_per_cell)
     block = {}
-    for on in dict.fromkeys(args.abx_on):
+    ons = list(dict.fromkeys(args.abx_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else [])
+    for on in ons:
         if on == "z1":
             rows = frames.encode_frames(model, pool, args.batch_size)[0]  # (shift 1: row f is frame f)
+        elif on == args.baseline_name:
+            rows = baseline_rows(args, pool, dev)
         else:
             rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
         if rows.shape[1] > abx.ABX_MAX_DIM:
@@ -241,8 +287,16 @@ def discover_units(args, model, T, out_dir, dev):
     pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
     items = abx.read_items(args.units_item) if args.units_item is not None else None
     block = {}
-    for on in dict.fromkeys(args.units_on):
-        rows, width = units.corpus_rows(model, pool, on, args.batch_size)
+    ons = list(dict.fromkeys(args.units_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else [])
+    for on in ons:
+        if on == args.baseline_name:
+            rows = baseline_rows(args, pool, dev)
+            width = int(rows.shape[1])
+            if width > units.KM_MAX_DIM:
+                raise ValueError("%s has %d values per frame, the k-means kernels take at most %d" % (on, width, units.KM_MAX_DIM))
+            rows = torch.nn.functional.pad(rows, (0, -width % 16)).contiguous()  # (as units.corpus_rows pads z1 and feats)
+        else:
+            rows, width = units.corpus_rows(model, pool, on, args.batch_size)
         info, cent, _, seqs = units.discover(rows, width, pool.keys, pool.lengths, on, k=args.units, iters=args.units_iters,
                                              seed=args.units_seed, items=items, frame_shift=args.abx_frame_shift,
                                              frame_offset=args.abx_frame_offset)

@@ -4,6 +4,8 @@ features.compute_kaldi_fbank on the MI355X and kaldi_io_lite; no Kaldi binary is
 
     python pytorch-scalablefhvae_amd/prepare_kaldi_data.py DATASET_DIR [--fbank_conf ./misc/fbank.conf] [--set_name train]
         [--seed 0] [--resample] [--compress [--compression-method auto]] [--verify-md5] [--vad {mark,drop} [--vad_conf FILE]]
+        [--mfcc_conf FILE] [--add-deltas [--delta-order 2] [--delta-window 2]]
+        [--cmvn-sliding [--cmn-window 300] [--cmn-min-window 100] [--no-cmn-center] [--cmn-norm-vars]]
 
 For every set (train, dev and test in turn unless --set_name is given) it reads <DATASET_DIR>/<set>/wav.scp ("<key> <path>"
 lines) and writes, in wav.scp order, <DATASET_DIR>/<set>/feats.ark (binary archive of float32 matrices), feats.scp
@@ -26,6 +28,13 @@ ORIGINAL frames as float vectors (1.0 / 0.0) to <DATASET_DIR>/<set>/vad.ark and 
 and len.scp what a run without the flag writes; "drop" keeps the voiced rows only (select-voiced-frames: selected on the GPU
 in front of the compression and the download; len.scp then holds the voiced count), skips an utterance without a voiced
 frame, naming it on stderr, and closes with one line that counts the skipped utterances and the share of frames dropped.
+
+With --mfcc_conf FILE the archive holds MFCCs instead (compute-mfcc-feats: kaldi_post.kaldi_mfcc_options lists what the file
+may hold; --fbank_conf is not read then).  --add-deltas appends delta and delta-delta features (add-deltas) and --cmvn-sliding
+subtracts the mean of a sliding window (apply-cmvn-sliding --center=true --cmn-window=300 unless --no-cmn-center /
+--cmn-window say otherwise; --cmn-norm-vars also divides by the window's standard deviation); both are valid with either
+configuration and are applied on the GPU in the order of Kaldi's recipes: deltas, CMVN, then --vad drop's row selection, then
+--compress.  Without these flags nothing changes.
 
 Differences from the reference:
   * --kaldi_root is accepted and ignored.
@@ -76,17 +85,26 @@ def read_wav_scp(path):
 
 
 def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_root=None, seed=0, resample=False, timings=None,
-                  compress=None, verify_md5=False, vad=None, vad_conf=None):
+                  compress=None, verify_md5=False, vad=None, vad_conf=None, mfcc_conf=None, deltas=None, cmvn=None):
     """prepare_kaldi_data.py:10-82: features of every sequence of <dataset_dir>/<set_name>/wav.scp.
     Returns (count, (dataset_dir, feats.ark, feats.scp, len.scp)).  `timings` (optional dict) receives seconds spent in
     "read", "gpu" and "write".  `compress`: None (float32 matrices) or a method of kaldi_io_lite.METHODS.  `vad`: None, "mark"
     or "drop" (the module docstring) with `vad_conf`, what features.kaldi_vad_options takes; then the result's second entry
-    also holds vad.ark and vad.scp, and `count` counts the utterances written."""
+    also holds vad.ark and vad.scp, and `count` counts the utterances written.  `mfcc_conf` (what kaldi_post.kaldi_mfcc_options
+    takes): MFCCs instead of fbank features, `fbank_conf` is not read; `deltas` / `cmvn` (kaldi_post.deltas_spec / cmvn_spec):
+    the two steps behind the features on the device.  With all three None the path is features.compute_kaldi_fbank's, as before."""
     if vad not in VAD_MODES:
         raise ValueError("vad must be one of %s, got %r" % (", ".join(str(m) for m in VAD_MODES), vad))
     if vad is None and vad_conf is not None:
         raise ValueError("--vad_conf needs --vad {mark,drop}")
-    opts = features.kaldi_fbank_options(fbank_conf)
+    post = mfcc_conf is not None or deltas is not None or cmvn is not None
+    if post:
+        import kaldi_post
+
+        opts = kaldi_post.kaldi_mfcc_options(mfcc_conf) if mfcc_conf is not None else features.kaldi_fbank_options(fbank_conf)
+    else:
+        opts = features.kaldi_fbank_options(fbank_conf)
+    conf_name = mfcc_conf if mfcc_conf is not None else fbank_conf
     vad_opts = features.kaldi_vad_options(vad_conf) if vad is not None else None
     sr = int(opts["sample-frequency"])
     set_dir = Path(dataset_dir) / set_name
@@ -122,13 +140,15 @@ def prepare_kaldi(dataset_dir, set_name, fbank_conf="./misc/fbank.conf", kaldi_r
                     for key, path, _, rate in got:
                         if rate != sr:
                             raise ValueError(f"{key} ({path}): sample rate {rate} differs from sample-frequency {sr} of "
-                                             f"{fbank_conf} (convert the file or pass --resample)")
+                                             f"{conf_name} (convert the file or pass --resample)")
                 t0 = time.time()
-                feats = features.compute_kaldi_fbank([g[2] for g in got], opts, seed=seed,
-                                                     stream_ids=[features.kaldi_stream_id(g[0]) for g in got],
-                                                     names=["%s (%s)" % (g[0], g[1]) for g in got],
-                                                     rates=[g[3] for g in got] if resample else None, compress=compress,
-                                                     **({} if vad is None else {"vad": {"opts": vad_opts, "drop": vad == "drop"}}))
+                more = {} if vad is None else {"vad": {"opts": vad_opts, "drop": vad == "drop"}}
+                if post:
+                    more.update(kind="mfcc" if mfcc_conf is not None else "fbank", deltas=deltas, cmvn=cmvn)
+                feats = (kaldi_post.compute_kaldi_feats if post else features.compute_kaldi_fbank)(
+                    [g[2] for g in got], opts, seed=seed, stream_ids=[features.kaldi_stream_id(g[0]) for g in got],
+                    names=["%s (%s)" % (g[0], g[1]) for g in got], rates=[g[3] for g in got] if resample else None,
+                    compress=compress, **more)
                 feats, vads = feats if vad is not None else (feats, [None] * len(got))
                 dt = time.time() - t0
                 t["gpu"] += dt
@@ -179,7 +199,49 @@ def build_parser():
                    help="Energy VAD on the GPU (compute-vad-decision): write vad.ark / vad.scp (mark), or also keep the voiced frames only (drop, select-voiced-frames)")
     p.add_argument("--vad_conf", type=str, default=None,
                    help="With --vad: Kaldi config file of --vad-energy-threshold, --vad-energy-mean-scale, --vad-frames-context, --vad-proportion-threshold")
+    p.add_argument("--mfcc_conf", type=str, default=None,
+                   help="Kaldi MFCC configuration (compute-mfcc-feats): write MFCCs instead of fbank features; --fbank_conf is not read")
+    add_post_arguments(p)
     return p
+
+
+def add_post_arguments(p):
+    """The --add-deltas / --cmvn-sliding arguments (shared with postprocess_kaldi_feats.py); post_specs reads them."""
+    p.add_argument("--add-deltas", action="store_true", help="Append delta features on the GPU (add-deltas)")
+    p.add_argument("--delta-order", type=int, default=None, help="With --add-deltas: 1 or 2 (default 2)")
+    p.add_argument("--delta-window", type=int, default=None, help="With --add-deltas: the window of one differentiation, 1 to 8 (default 2)")
+    p.add_argument("--cmvn-sliding", action="store_true", help="Sliding-window mean normalisation on the GPU (apply-cmvn-sliding)")
+    p.add_argument("--cmn-window", type=int, default=None, help="With --cmvn-sliding: frames in the window (default 300)")
+    p.add_argument("--cmn-min-window", type=int, default=None, help="With --cmvn-sliding --no-cmn-center: the least window at an utterance's start (default 100)")
+    p.add_argument("--no-cmn-center", action="store_true", help="With --cmvn-sliding: the window ends at the frame instead of being centred on it")
+    p.add_argument("--cmn-norm-vars", action="store_true", help="With --cmvn-sliding: also normalise the variance over the window")
+
+
+#: the arguments of the steps of kaldi_post.py; at their defaults main() prints the argument list without them, as it was
+POST_ARGS = ("mfcc_conf", "add_deltas", "delta_order", "delta_window", "cmvn_sliding", "cmn_window", "cmn_min_window", "no_cmn_center",
+             "cmn_norm_vars")
+
+
+def post_specs(parser, args):
+    """The --add-deltas / --cmvn-sliding arguments (shared with postprocess_kaldi_feats.py) -> (deltas_spec, cmvn_spec), None
+    for a step not asked for; contradictory arguments end in parser.error before any work."""
+    if not args.add_deltas and (args.delta_order is not None or args.delta_window is not None):
+        parser.error("--delta-order / --delta-window need --add-deltas")
+    if not args.cmvn_sliding and (args.cmn_window is not None or args.cmn_min_window is not None or args.no_cmn_center or args.cmn_norm_vars):
+        parser.error("--cmn-window / --cmn-min-window / --no-cmn-center / --cmn-norm-vars need --cmvn-sliding")
+    if not (args.add_deltas or args.cmvn_sliding):
+        return None, None
+    import kaldi_post
+
+    try:
+        deltas = kaldi_post.deltas_spec(2 if args.delta_order is None else args.delta_order,
+                                        2 if args.delta_window is None else args.delta_window) if args.add_deltas else None
+        cmvn = kaldi_post.cmvn_spec(300 if args.cmn_window is None else args.cmn_window,
+                                    100 if args.cmn_min_window is None else args.cmn_min_window, not args.no_cmn_center,
+                                    args.cmn_norm_vars) if args.cmvn_sliding else None
+    except ValueError as e:
+        parser.error(str(e))
+    return deltas, cmvn
 
 
 def main(argv=None):
@@ -187,7 +249,10 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.vad_conf is not None and args.vad is None:
         parser.error("--vad_conf needs --vad {mark,drop}")
-    print(args)
+    if args.mfcc_conf is not None and args.fbank_conf != parser.get_default("fbank_conf"):
+        parser.error("--mfcc_conf and --fbank_conf exclude each other")
+    deltas, cmvn = post_specs(parser, args)
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in POST_ARGS or v not in (None, False)}))
     if args.kaldi_root is not None:
         print("--kaldi_root is ignored: the features are computed on the GPU, no Kaldi binary is run")
     sets = ["train", "dev", "test"] if args.set_name is None else [args.set_name]
@@ -197,7 +262,7 @@ def main(argv=None):
         for s in sets:
             total += prepare_kaldi(args.dataset_dir, s, args.fbank_conf, args.kaldi_root, args.seed, args.resample,
                                    compress=args.compression_method if args.compress else None, verify_md5=args.verify_md5,
-                                   vad=args.vad, vad_conf=args.vad_conf)[0]
+                                   vad=args.vad, vad_conf=args.vad_conf, mfcc_conf=args.mfcc_conf, deltas=deltas, cmvn=cmvn)[0]
     except ValueError as e:
         print("prepare_kaldi_data: %s" % e, file=sys.stderr)
         return 1
