@@ -26,7 +26,7 @@
 
 #include "common.h"
 
-#include "../../include/fhvae_abx.h"
+#include "abx_cost.h"
 
 namespace fh {
 
@@ -184,15 +184,7 @@ __global__ void __launch_bounds__(kAbxLanes, LMAX <= 32 ? 2 : 1) abx_dtw_kernel(
     const int y = base + lane, j = y / ns, i = y - j * ns;
     const bool act = y < total && i < n;
     double c = 0.0;
-    if (act) {
-      const double na = nrm[i], nb = nrm[LMAX + j];
-      double cs = 0.0;
-      if (na != 0.0 && nb != 0.0) {
-        cs = dots[y] / (na * nb);
-        cs = cs > 1.0 ? 1.0 : (cs < -1.0 ? -1.0 : cs);
-      }
-      c = metric == FHVAE_ABX_ANGULAR ? acos(cs) / M_PI : 1.0 - cs;
-    }
+    if (act) c = abx_frame_cost(dots[y], nrm[i], nrm[LMAX + j], metric);
     __syncthreads();  // every dot of this round is read before a cost lands on one (round 0; later rounds write behind)
     if (act) cost[y] = (float)c;
   }

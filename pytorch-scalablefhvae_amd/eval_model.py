@@ -46,9 +46,15 @@ codebook, and summary.json gains "units": {"z1": {on, k, frames, iterations, con
 bitrate_collapsed}, "feats": {...}}; with --units-item FILE (a .item phone alignment; the frame grid is --abx-frame-shift /
 --abx-frame-offset) every sub-block also holds cluster_purity, phone_purity, pnmi, labelled_frames, overlaps and phones.
 
+With --qbe-queries ITEM --qbe-item ITEM (needs --feat-scp data) spoken terms are searched for by example (qbe.py): the queries are
+the first --qbe-max-per-term tokens of every term of ITEM (the #phone column is the term; tokens of at most 64 frames), each is
+aligned against every other utterance by subsequence DTW under --qbe-distance, and the ranking is scored against the term tokens
+of --qbe-item.  summary.json gains "qbe": {"z1": {map, p_at_n, p_at_10, located, no_target}, "feats": {...}, "queries", "dropped",
+"distance", "frame_shift", "frame_offset"} (--qbe-on chooses; the frame grid is --abx-frame-shift / --abx-frame-offset).
+
 With --baseline-feat-scp SCP [--baseline-name mfcc] a second Kaldi archive with the same keys and the same frame count per
 utterance (MFCC + deltas + CMVN from prepare_kaldi_data.py --mfcc_conf, the baseline the zero-resource literature quotes) is
-scored as one more entry "<name>" of the "abx" and "units" blocks, with abx_by_pair_<name>.tsv, units_<name>.txt and
+scored as one more entry "<name>" of the "abx", "units" and "qbe" blocks, with abx_by_pair_<name>.tsv, units_<name>.txt and
 units_centroids_<name>.npy beside those of z1 and feats.  It is taken as it is (not normalised by --mvn-path); a key it lacks or
 another frame count is an error that names the key.
 
@@ -117,8 +123,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--units-iters", type=int, default=100, help="Lloyd iterations, at most")
     p.add_argument("--units-seed", type=int, default=0, help="seed of the rows the first centroids are copied from")
     p.add_argument("--units-item", default=None, metavar="FILE", help="phone alignment (.item) to score the units against")
+    p.add_argument("--qbe-queries", default=None, metavar="ITEM",
+                   help="query-by-example search: the examples (.item, the #phone column is the term) cut from and searched in --feat-scp data")
+    p.add_argument("--qbe-item", default=None, metavar="ITEM", help="the term tokens of the corpus the search is scored against")
+    p.add_argument("--qbe-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to search on: frame-level z1, the input features")
+    p.add_argument("--qbe-distance", default="angular", choices=["angular", "cosine"], help="frame cost under the subsequence DTW")
+    p.add_argument("--qbe-max-per-term", type=int, default=5, help="queries kept per term, the first in file order; 0: all")
     p.add_argument("--baseline-feat-scp", default=None, metavar="SCP",
-                   help="a second Kaldi archive (same keys, same frames per utterance) scored beside z1 and feats under --abx-item / --units")
+                   help="a second Kaldi archive (same keys, same frames per utterance) scored beside z1 and feats under --abx-item / --units / --qbe-queries")
     p.add_argument("--baseline-name", default=None, help="the baseline's entry in summary.json and its files' suffix (default mfcc)")
     return p
 
@@ -152,11 +164,17 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--units-iters %d must be at least 1" % args.units_iters)
     if args.units_seed < 0 or args.units_seed >= 2 ** 32:
         p.error("--units-seed %d must lie in [0, 2^32)" % args.units_seed)
+    if (args.qbe_queries is None) != (args.qbe_item is None):
+        p.error("--qbe-queries and --qbe-item come together")
+    if args.qbe_queries is not None and args.feat_scp is None:
+        p.error("--qbe-queries lists tokens of --feat-scp data: give --feat-scp")
+    if args.qbe_max_per_term < 0:
+        p.error("--qbe-max-per-term %d must not be negative" % args.qbe_max_per_term)
     if args.baseline_name is not None and args.baseline_feat_scp is None:
         p.error("--baseline-name needs --baseline-feat-scp")
     if args.baseline_feat_scp is not None:
-        if args.abx_item is None and args.units is None:
-            p.error("--baseline-feat-scp is scored by --abx-item and --units: give one of them")
+        if args.abx_item is None and args.units is None and args.qbe_queries is None:
+            p.error("--baseline-feat-scp is scored by --abx-item, --units and --qbe-queries: give one of them")
         args.baseline_name = "mfcc" if args.baseline_name is None else args.baseline_name
         if args.baseline_name in ("z1", "feats") or not args.baseline_name.replace("_", "").replace("-", "").isalnum():
             p.error("--baseline-name %r: letters, digits, - and _, and neither z1 nor feats" % args.baseline_name)
@@ -274,6 +292,28 @@ def measure_abx(args, model, T, out_dir, dev):
                      for k in ("within", "across", "cells_within", "cells_across", "triples_within", "triples_across")}
         del rows
     block.update({"tokens": int(tokens["start"].shape[0]), "dropped": tokens["dropped"], "distance": args.abx_distance,
+                  "frame_shift": args.abx_frame_shift, "frame_offset": args.abx_frame_offset})
+    return block
+
+
+def search_terms(args, model, T, out_dir, dev):
+    """--qbe-queries: the "qbe" block of summary.json (see the module docstring)."""
+    import abx
+    import frames
+    import qbe
+
+    pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
+    queries = qbe.queries_from_items(abx.read_items(args.qbe_queries), pool.keys, pool.lengths, args.abx_frame_shift, args.abx_frame_offset,
+                                     max_per_term=args.qbe_max_per_term)
+    truth = qbe.truth_from_items(abx.read_items(args.qbe_item), pool.keys, pool.lengths, args.abx_frame_shift, args.abx_frame_offset)
+    block = {}
+    ons = list(dict.fromkeys(args.qbe_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else [])
+    for on in ons:
+        rows = qbe.checked_rows(baseline_rows(args, pool, dev), on) if on == args.baseline_name else qbe.corpus_rows(model, pool, on, args.batch_size)
+        res, _ = qbe.evaluate(rows, queries, rows, qbe.utt_ptr_of(pool.lengths), truth, args.qbe_distance)
+        block[on] = {k: res[k] for k in ("map", "p_at_n", "p_at_10", "located", "no_target")}
+        del rows
+    block.update({"queries": len(queries["id"]), "dropped": queries["dropped"], "distance": args.qbe_distance,
                   "frame_shift": args.abx_frame_shift, "frame_offset": args.abx_frame_offset})
     return block
 
@@ -493,6 +533,13 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("--units: %s" % e, file=sys.stderr)
             return 1
+    qbe_block = None
+    if args.qbe_queries is not None:
+        try:
+            qbe_block = search_terms(args, model, T, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("--qbe-queries: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -514,6 +561,8 @@ def main(argv=None) -> int:
         summary["abx"] = abx_block
     if units_block is not None:
         summary["units"] = units_block
+    if qbe_block is not None:
+        summary["qbe"] = qbe_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

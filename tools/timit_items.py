@@ -1,12 +1,15 @@
 """An ABX item file (abx.read_items' format) from TIMIT's phone transcriptions.
 
-    python tools/timit_items.py RAW_DIR OUT.item [--sample-rate 16000]
+    python tools/timit_items.py RAW_DIR OUT.item [--sample-rate 16000] [--tier phn|wrd]
 
 Every .PHN / .phn file below RAW_DIR holds one `start_sample end_sample phone` line per phone, at 16 kHz.  Each phone becomes one
 item: onset and offset in seconds, the phone, the phones in front of and behind it in the file as its context, the speaker (the
 directory the file lies in, in lower case) and the utterance key `<speaker>_<name>` that preprocess_timit.py gives the .WAV next
 to it.  The silence marker h# and the first and the last phone of a file (they have one neighbour only) are no tokens; h# may
 be a context.  Files are walked in sorted order.  A malformed line is an error naming the file and the line.
+
+With --tier wrd the .WRD / .wrd files are read instead (the same line format, a word in place of the phone): every word is one
+item, the word stands in the #phone column as the term (qbe.queries_from_items) and both context columns hold `-`.
 """
 import argparse
 import os
@@ -38,17 +41,21 @@ def read_phn(path):
     return rows
 
 
-def timit_items(raw_dir, sample_rate=16000):
-    """The items of every .PHN file below raw_dir, as abx.read_items returns them."""
+def timit_items(raw_dir, sample_rate=16000, tier="phn"):
+    """The items of every .PHN (tier "phn") or .WRD (tier "wrd") file below raw_dir, as abx.read_items returns them."""
     items = []
+    exts = (".PHN", ".phn") if tier == "phn" else (".WRD", ".wrd")
     for root, dirs, names in os.walk(raw_dir):
         dirs.sort()
         spk = os.path.basename(os.path.normpath(root)).lower()
         for name in sorted(names):
             stem, ext = os.path.splitext(name)
-            if ext not in (".PHN", ".phn"):
+            if ext not in exts:
                 continue
             rows = read_phn(os.path.join(root, name))
+            if tier == "wrd":
+                items += [("%s_%s" % (spk, stem), a / sample_rate, b / sample_rate, word, "-", "-", spk) for a, b, word in rows]
+                continue
             for k in range(1, len(rows) - 1):
                 a, b, phone = rows[k]
                 if phone == SILENCE:
@@ -64,9 +71,10 @@ def main(argv=None):
     ap.add_argument("raw_dir")
     ap.add_argument("out_item")
     ap.add_argument("--sample-rate", type=int, default=16000)
+    ap.add_argument("--tier", default="phn", choices=["phn", "wrd"], help="phones with their contexts (ABX), or words as search terms")
     args = ap.parse_args(argv)
     try:
-        items = timit_items(args.raw_dir, args.sample_rate)
+        items = timit_items(args.raw_dir, args.sample_rate, args.tier)
     except ValueError as e:
         print("timit_items: %s" % e, file=sys.stderr)
         return 1
