@@ -125,7 +125,8 @@ def test_persistent_table_trains(hb):
 
 def test_fhvae_bf16_tracks_f32(hb):
     """bf16 MFMA operands (compute_dtype='bf16') against the f32 oracle: the bound and the loss agree to 1e-2
-    relative ("matched ELBO" tolerance for the bf16 configs)."""
+    relative ("matched ELBO" tolerance for the bf16 configs).  Its gradients are only checked to be finite
+    here: tests/test_step_oracle_gpu.py compares every one of them with the composed float64 oracle of the bf16 step."""
     from fhvae import FHVAE
     from train_model import loss_function
 
