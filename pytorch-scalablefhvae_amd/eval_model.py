@@ -58,6 +58,14 @@ scored as one more entry "<name>" of the "abx", "units" and "qbe" blocks, with a
 units_centroids_<name>.npy beside those of z1 and feats.  It is taken as it is (not normalised by --mvn-path); a key it lacks or
 another frame count is an error that names the key.
 
+With --probe-item FILE (needs --feat-scp data) a linear probe (probe.py: softmax regression, L-BFGS, --probe-l2, --probe-iters) is
+trained on the frames of all but the last ceil(--probe-holdout U) utterances of RandomState(--probe-seed).permutation(U) to predict
+each frame's phone and its speaker (--probe-target), on frame-level z1 and on the normalised input (--probe-on) and on the
+--baseline-feat-scp archive, and scored on the held-out utterances.  summary.json gains "probe": {"phone": {"z1": {classes,
+train_frames, test_frames, accuracy, balanced_accuracy, majority, train_accuracy, loss, iterations, converged, l2, unlabelled,
+overlaps}, "feats": {...}}, "speaker": {...}, "holdout", "seed", "frame_shift", "frame_offset"} (the frame grid is
+--abx-frame-shift / --abx-frame-offset).  Without --probe-item every output is what it was.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -132,6 +140,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--baseline-feat-scp", default=None, metavar="SCP",
                    help="a second Kaldi archive (same keys, same frames per utterance) scored beside z1 and feats under --abx-item / --units / --qbe-queries")
     p.add_argument("--baseline-name", default=None, help="the baseline's entry in summary.json and its files' suffix (default mfcc)")
+    p.add_argument("--probe-item", default=None, metavar="FILE",
+                   help="frame probes: a softmax regression on the frames of --feat-scp data predicts the phone / speaker this .item alignment gives")
+    p.add_argument("--probe-target", nargs="+", default=["phone", "speaker"], choices=["phone", "speaker"], help="what the probe predicts")
+    p.add_argument("--probe-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to probe: frame-level z1, the input features")
+    p.add_argument("--probe-holdout", type=float, default=0.2, help="share of the utterances held out as the probe's test set")
+    p.add_argument("--probe-seed", type=int, default=0, help="seed of the held-out utterances")
+    p.add_argument("--probe-l2", type=float, default=1e-4)
+    p.add_argument("--probe-iters", type=int, default=200, help="L-BFGS iterations, at most")
     return p
 
 
@@ -170,10 +186,18 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--qbe-queries lists tokens of --feat-scp data: give --feat-scp")
     if args.qbe_max_per_term < 0:
         p.error("--qbe-max-per-term %d must not be negative" % args.qbe_max_per_term)
+    if args.probe_item is not None and args.feat_scp is None:
+        p.error("--probe-item labels the frames of --feat-scp data: give --feat-scp")
+    if not 0.0 < args.probe_holdout < 1.0:
+        p.error("--probe-holdout %g must lie in (0, 1)" % args.probe_holdout)
+    if args.probe_seed < 0 or args.probe_seed >= 2 ** 32:
+        p.error("--probe-seed %d must lie in [0, 2^32)" % args.probe_seed)
+    if args.probe_iters < 0 or not args.probe_l2 >= 0:
+        p.error("--probe-iters and --probe-l2 must not be negative")
     if args.baseline_name is not None and args.baseline_feat_scp is None:
         p.error("--baseline-name needs --baseline-feat-scp")
     if args.baseline_feat_scp is not None:
-        if args.abx_item is None and args.units is None and args.qbe_queries is None:
+        if args.abx_item is None and args.units is None and args.qbe_queries is None and args.probe_item is None:
             p.error("--baseline-feat-scp is scored by --abx-item, --units and --qbe-queries: give one of them")
         args.baseline_name = "mfcc" if args.baseline_name is None else args.baseline_name
         if args.baseline_name in ("z1", "feats") or not args.baseline_name.replace("_", "").replace("-", "").isalnum():
@@ -344,6 +368,37 @@ def discover_units(args, model, T, out_dir, dev):
         units.write_units(os.path.join(out_dir, "units_%s.txt" % on), pool.keys, seqs)
         block[on] = info
         del rows
+    return block
+
+
+def probe_frames(args, model, T, out_dir, dev):
+    """--probe-item: the "probe" block of summary.json (see the module docstring)."""
+    import abx
+    import frames
+    import probe
+    from fit_gmm import corpus_rows
+    from probe_latents import split_rows
+
+    pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
+    items = abx.read_items(args.probe_item)
+    block = {}
+    ons = list(dict.fromkeys(args.probe_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else [])
+    for target in dict.fromkeys(args.probe_target):
+        labels, names, overlaps = probe.frame_labels(items, pool.keys, pool.lengths, target, args.abx_frame_shift, args.abx_frame_offset)
+        if not names:
+            raise ValueError("no frame lies under a token of %s" % args.probe_item)
+        block[target] = {}
+        for on in ons:
+            rows = baseline_rows(args, pool, dev) if on == args.baseline_name else corpus_rows(model, pool, on, args.batch_size)
+            if rows.shape[1] > probe.PROBE_MAX_W:
+                raise ValueError("%s has %d values per frame, the probe kernels take at most %d" % (on, rows.shape[1], probe.PROBE_MAX_W))
+            split = split_rows(rows.contiguous(), labels, pool.lengths, args.probe_holdout, args.probe_seed)
+            _, report, _ = probe.run(*split, names, l2=args.probe_l2, iters=args.probe_iters)
+            report.update({"unlabelled": int((labels < 0).sum()), "overlaps": int(overlaps)})
+            block[target][on] = report
+            del rows
+    block.update({"holdout": args.probe_holdout, "seed": args.probe_seed, "frame_shift": args.abx_frame_shift,
+                  "frame_offset": args.abx_frame_offset})
     return block
 
 
@@ -540,6 +595,13 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("--qbe-queries: %s" % e, file=sys.stderr)
             return 1
+    probe_block = None
+    if args.probe_item is not None:
+        try:
+            probe_block = probe_frames(args, model, T, args.out, dev)
+        except (ValueError, OSError) as e:
+            print("--probe-item: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -563,6 +625,8 @@ def main(argv=None) -> int:
         summary["units"] = units_block
     if qbe_block is not None:
         summary["qbe"] = qbe_block
+    if probe_block is not None:
+        summary["probe"] = probe_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))
