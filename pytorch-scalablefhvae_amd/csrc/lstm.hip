@@ -935,8 +935,10 @@ static int lstm_seq_bwd_t(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl, con
   if (rec) {
     e = lstm_bwd_impl<T>(bd, pl, op, st);
     if (e) return e;
-    e = lstm_dxc(bd, st, pl.bwd_zeroes_dxc);
-    if (e) return e;
+    if (!pl.bwd_folds_dxc) {  // (else the layer-0 launch of the recurrence has computed it)
+      e = lstm_dxc(bd, st, pl.bwd_zeroes_dxc);
+      if (e) return e;
+    }
   }
   if (!par) return FHVAE_OK;
   std::vector<WgProblemT<T>> wq;

@@ -288,7 +288,74 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_layer_rs_kernel(ClBwd p) {
       dg_store(3, v3);
     }
   }
-  if (p.d_xc_zero && me == 0 && wave == 0) {  // one wave per cluster clears its rows of d_xc for the contraction that follows
+  // ---- layer 0: d_xc[row, :] = sum over t of dg_t[row, :] . W_ih0[:, I:] for this cluster's rows, in the launch (ClBwd::d_xc).
+  // The sum over t, dgs, is in registers, and in the lane layout of a 16x16x4 f32 A operand: lane (q, r) holds, for row r, gate
+  // g of unit uq + j -- one k of the four that lane quads q = 0..3 supply -- so wave w of member me multiplies its 64 gate
+  // columns {g H + 64 me + 16 w + 4 q + j} with 16 MFMAs per (row tile, 16 columns), no LDS shuffle, f32 throughout.  The B
+  // values (f32 master weights, columns past Ic masked) are requested here, behind the loop: nothing new is live inside it.
+  // Waves: through the image (free now), in fixed order (0 + 2) + (1 + 3).  Members: 1..3 leave their sums in the exchange
+  // buffer -- the parity the last step did not use: every member has read it before anybody passed the wait of step T - 1 --
+  // and everybody publishes one further epoch, T; member 0 waits for it and adds own + 1 + 2 + 3, plain stores: no zeroing, no
+  // atomics, the same bits on every run.  Members 1..3 never wait here, so nobody waits for a member that has left.
+  f32x4 ms[RT];  // this member's sum: 16-byte piece tid + 256 i of the cluster's [RT * 16 rows][64 columns]
+#pragma unroll
+  for (int i = 0; i < RT; ++i) ms[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (p.d_xc) {
+    const int Ic = p.Ic;
+    f32x4 xacc[RT][4];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) xacc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      if (ct * 16 < Ic) {  // (uniform)
+        const int col = ct * 16 + r;
+        const float* wp = p.w_xc + (col < Ic ? col : Ic - 1);
+        float bv[4][4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float v = wp[(int64_t)(g * H + uq + j) * p.ldw_xc];
+            bv[g][j] = col < Ic ? v : 0.f;
+          }
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) xacc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(dgs[rt][g][j], bv[g][j], xacc[rt][ct], 0, 0, 0);
+      }
+    }
+    // result lane (q, c), element v: row 4 q + v of the tile, column 16 ct + c.  Image: [2 halves][RT * 16 rows][64 columns] f32
+    float* S = (float*)Img;
+    constexpr int HS = RT * 16 * 64;
+    auto xsum = [&](bool add) {
+      float* sh = S + (wave & 1) * HS;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            float* e = sh + (rt * 16 + 4 * q + v) * 64 + ct * 16 + r;
+            *e = add ? *e + xacc[rt][ct][v] : xacc[rt][ct][v];
+          }
+    };
+    if (wave < 2) xsum(false);
+    __syncthreads();
+    if (wave >= 2) xsum(true);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RT; ++i) ms[i] = *(const f32x4*)(S + (tid + 256 * i) * 4) + *(const f32x4*)(S + HS + (tid + 256 * i) * 4);
+    const int par = (T - 1) & 1;
+    if (me != 0) {
+#pragma unroll
+      for (int i = 0; i < RT; ++i) *(f32x4*)((char*)p.xch + rs_xoff<RT>(par, cluster, me, 1, 0, 0) + (tid + 256 * i) * 16) = ms[i];
+    }
+    cluster_publish(flags, me, ep0 + (unsigned)T);
+  } else if (p.d_xc_zero && me == 0 && wave == 0) {  // one wave per cluster clears its rows of d_xc for the contraction that follows
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
       if (row[rt] < rend)
@@ -303,6 +370,28 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_layer_rs_kernel(ClBwd p) {
       if (p.dgsum && row[rt] < rend) *(f32x4*)(p.dgsum + (int64_t)row[rt] * G + g * H + uq) = dgs[rt][g];
     }
     if (p.db_ih[0] || p.db_hh[0]) db_reduce_add(vs, p.db_ih[0], p.db_hh[0], g * H + uq, lane);
+  }
+  if (p.d_xc && me == 0) {  // (behind the stores above: they pass under the members' hand-off)
+    const int Ic = p.Ic, par = (T - 1) & 1;
+    if (!cluster_wait(p.sync, flags, kNU, ep0 + (unsigned)T)) return;
+    u32x4 pv[RT][3];
+#pragma unroll
+    for (int m = 1; m < kNU; ++m)
+#pragma unroll
+      for (int i = 0; i < RT; ++i)
+        pv[i][m - 1] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, rs_xoff<RT>(par, cluster, m, 1, 0, 0) + (tid + 256 * i) * 16, 0, kSc1);
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+      f32x4 v = ms[i];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) v += __builtin_bit_cast(f32x4, pv[i][m]);
+      const int pc = tid + 256 * i, rw = r0 + (pc >> 4), c0 = (pc & 15) * 4;
+      if (rw < rend) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (c0 + k < Ic) p.d_xc[(int64_t)rw * Ic + c0 + k] = v[k];
+      }
+    }
   }
   CL_TLOG((T - 1) * 8 + 7);
 }

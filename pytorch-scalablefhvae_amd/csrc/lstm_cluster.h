@@ -38,8 +38,8 @@ struct ClusterWeights {  // bf16 operand copies in the workspace
 
 // The schedule of a recurrence and its variants, decided ONCE per C call from the descriptor's scalar fields, `lp != NULL`, the
 // (cached) device check and the environment: every schedule switch (FHVAE_NO_CLUSTER, _NO_FOLD, _NO_XC_FOLD, _NO_FWD_WR, _NO_RS,
-// _BIG_CELLS, _NO_WGRAD, _CLUSTER_TLOG) is read in lstm_plan and nowhere else, on every call (the tests flip them between calls).
-// Forward, backward and the size queries of the C ABI all read the same fields, so what a forward saves (gates unit-major or not,
+// _NO_DXC_FOLD, _BIG_CELLS, _NO_WGRAD, _CLUSTER_TLOG) is read in lstm_plan and nowhere else, on every call (the tests flip them
+// between calls).  Forward, backward and the size queries of the C ABI all read the same fields, so what a forward saves (gates unit-major or not,
 // ws_below, pre) is what the backward of the same descriptor and environment expects.
 struct LstmPlan {
   int form;  // 0: one launch per wavefront step (lstm.hip); persistent (bf16, gfx950 with 256 CUs, H in {128, 256}, L <= 2, ...):
@@ -52,6 +52,7 @@ struct LstmPlan {
   bool fwd_wr;          // ... two layers, the inputs folded: the forward with register-stationary weights (lstm_fwd_wr.hip); it
                         // saves the gates unit-major, which the partial-dh backward then reads (gates_um of ClFwd and ClBwd)
   bool bwd_zeroes_dxc;  // the backward recurrence leaves bd->d_xc zeroed: lstm.hip's split-K contraction into it needs no zeroing launch
+  bool bwd_folds_dxc;   // ... and, partial-dh backward with Ic <= 64 and T >= 2, computes d_xc itself: that contraction is not launched
   bool needs_ws_below;  // rows form, L >= 2: the layer-by-layer backward hands the from-above gradient down through bd->ws_below
   bool wgrad;           // the long weight-gradient contractions go to wgrad.hip's grouped launch
   bool tlog;            // the persistent kernels log their phase clocks into the last quarter of the sync block

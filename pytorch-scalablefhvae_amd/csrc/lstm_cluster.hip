@@ -1249,6 +1249,7 @@ LstmPlan lstm_plan(const fhvae_lstm_desc* d) {
   p.fwd_wr = p.bwd_rs && d->L == 2 && !getenv("FHVAE_NO_FWD_WR") && (I == 0 || p.fold) && (Ic == 0 || p.xc_in) &&
              2 * T * B * H * 2 < (1LL << 31) && T * B * I * 2 < (1LL << 31) && I + Ic > 0;  // (32-bit buffer offsets)
   p.bwd_zeroes_dxc = p.bwd_rs || p.form == 2;  // their layer-0 epilogue covers every row once
+  p.bwd_folds_dxc = p.bwd_rs && Ic > 0 && Ic <= 64 && T >= 2 && !getenv("FHVAE_NO_DXC_FOLD");
   p.needs_ws_below = p.form == 1 && d->L >= 2;
   // fwd_wr: 8 members with up to 64 rows; bwd_rs: 64 units per member, 32 rows; the other rows-form backward: 32 units per member
   p.fwd = p.fwd_wr ? LstmPlan::Geo{8, kGrid / 8, (int64_t)(kGrid / 8) * 64} : LstmPlan::Geo{NU, NC, (int64_t)NC * 128};
@@ -1424,7 +1425,13 @@ static int cluster_bwd_layers(const fhvae_lstm_bwd_desc* bd, const LstmPlan& pl,
       p.tlog_slot = l == L - 1;
       p.nt = 1;  // streaming hints on its once-read operands: HBM reads 202 -> 175 MB per launch (1.04x algorithmic), 0.5 % of a step
       p.gates_um = pl.fwd_wr;
-      if (rs && l == 0 && bd->d_xc && d->Ic > 0) p.d_xc_zero = bd->d_xc, p.Ic = (int)d->Ic;  // (LstmPlan::bwd_zeroes_dxc)
+      if (rs && l == 0 && bd->d_xc && d->Ic > 0) {
+        p.Ic = (int)d->Ic;
+        if (pl.bwd_folds_dxc)
+          p.d_xc = bd->d_xc, p.w_xc = d->w_ih[0] + d->I, p.ldw_xc = (int)(d->I + d->Ic);
+        else
+          p.d_xc_zero = bd->d_xc;  // (LstmPlan::bwd_zeroes_dxc)
+      }
       const int ts = trace_begin(st, kTraceBwdCell, 2.0 * p.nrows * H * (T - 1) * 4.0 * H);
       const int e = rs ? cluster_bwd_layer_rs(p, st) : (H == 256 ? launch_bwd_layer_rb<256>(p, RB, st) : launch_bwd_layer_rb<128>(p, RB, st));
       trace_end(st, ts);

@@ -179,6 +179,11 @@ struct ClBwd {
   int nt;                // lstm_bwd_rs.hip: streaming (non-temporal) hints on the once-read operands and the once-written dg
   float* d_xc_zero;      // lstm_bwd_rs.hip, layer 0: (B,Ic) f32 to ZERO for the rows of this launch (the split-K contraction that
   int Ic;                // follows adds into it: the zeroing launch in front of it is gone), or NULL
+  // lstm_bwd_rs.hip, layer 0, Ic <= 64, T >= 2 (LstmPlan::bwd_folds_dxc): the launch computes d_xc (B,Ic) = dgsum . w_xc itself in
+  // its tail, plain stores (d_xc_zero is then NULL and no contraction follows); w_xc = the f32 master W_ih[0][:, I:], row stride ldw_xc
+  float* d_xc;
+  const float* w_xc;
+  int ldw_xc;
 };
 
 __device__ __forceinline__ f32x4 unpack4(uint2 v) {
