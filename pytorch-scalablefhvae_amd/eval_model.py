@@ -66,6 +66,14 @@ train_frames, test_frames, accuracy, balanced_accuracy, majority, train_accuracy
 overlaps}, "feats": {...}}, "speaker": {...}, "holdout", "seed", "frame_shift", "frame_offset"} (the frame grid is
 --abx-frame-shift / --abx-frame-offset).  Without --probe-item every output is what it was.
 
+With --per-item FILE (needs --feat-scp data) phones are recognised (phonerec.py: the phone probe's scores, a Viterbi pass under a
+frame-level phone bigram, the phone error rate against the alignment read in onset order) on the held-out utterances of the
+probe's split (--probe-holdout, --probe-seed, --probe-l2, --probe-iters), on frame-level z1 and on the normalised input (--per-on)
+and on the --baseline-feat-scp archive.  summary.json gains "per": {"z1": {per, sub, del, ins, cor, ref_tokens, utterances,
+per_argmax, frame_accuracy, frame_accuracy_argmax, classes, ...}, "feats": {...}, "holdout", "seed", "frame_shift",
+"frame_offset", "phone_penalty"}; --per-phone-map folds both sides, --per-phone-penalty is the insertion penalty.  Without
+--per-item every output is what it was.
+
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
 """
@@ -148,6 +156,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--probe-seed", type=int, default=0, help="seed of the held-out utterances")
     p.add_argument("--probe-l2", type=float, default=1e-4)
     p.add_argument("--probe-iters", type=int, default=200, help="L-BFGS iterations, at most")
+    p.add_argument("--per-item", default=None, metavar="FILE",
+                   help="phone recognition: the phone error rate of a Viterbi pass over the phone probe's scores against this .item alignment")
+    p.add_argument("--per-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to recognise on: frame-level z1, the input features")
+    p.add_argument("--per-phone-map", default=None, metavar="FILE", help="lines `phone target` (`-` deletes) applied to both sides")
+    p.add_argument("--per-phone-penalty", type=float, default=0.0, help="subtracted from every transition between different phones")
     return p
 
 
@@ -194,10 +207,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--probe-seed %d must lie in [0, 2^32)" % args.probe_seed)
     if args.probe_iters < 0 or not args.probe_l2 >= 0:
         p.error("--probe-iters and --probe-l2 must not be negative")
+    if args.per_item is not None and args.feat_scp is None:
+        p.error("--per-item transcribes the utterances of --feat-scp data: give --feat-scp")
+    if not np.isfinite(args.per_phone_penalty):
+        p.error("--per-phone-penalty must be finite")
     if args.baseline_name is not None and args.baseline_feat_scp is None:
         p.error("--baseline-name needs --baseline-feat-scp")
     if args.baseline_feat_scp is not None:
-        if args.abx_item is None and args.units is None and args.qbe_queries is None and args.probe_item is None:
+        if args.abx_item is None and args.units is None and args.qbe_queries is None and args.probe_item is None and args.per_item is None:
             p.error("--baseline-feat-scp is scored by --abx-item, --units and --qbe-queries: give one of them")
         args.baseline_name = "mfcc" if args.baseline_name is None else args.baseline_name
         if args.baseline_name in ("z1", "feats") or not args.baseline_name.replace("_", "").replace("-", "").isalnum():
@@ -402,6 +419,36 @@ def probe_frames(args, model, T, out_dir, dev):
     return block
 
 
+def per_phones(args, model, T, dev):
+    """--per-item: the "per" block of summary.json (see the module docstring)."""
+    import abx
+    import frames
+    import phonerec
+    import probe
+    from fit_gmm import corpus_rows
+    from recognise_phones import reference_ids, split_corpus
+
+    pool = frames.pool_from_scp(args.data_format, args.feat_scp, args.len_scp, args.mvn_path, T, 1, dev)
+    items = abx.read_items(args.per_item)
+    labels, names, _ = probe.frame_labels(items, pool.keys, pool.lengths, "phone", args.abx_frame_shift, args.abx_frame_offset)
+    if not names:
+        raise ValueError("no frame lies under a token of %s" % args.per_item)
+    refs = reference_ids(phonerec.references(items, pool.keys), names)
+    table = phonerec.read_phone_map(args.per_phone_map, names)[0] if args.per_phone_map is not None else None
+    block = {}
+    for on in list(dict.fromkeys(args.per_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else []):
+        rows = baseline_rows(args, pool, dev) if on == args.baseline_name else corpus_rows(model, pool, on, args.batch_size)
+        if rows.shape[1] > probe.PROBE_MAX_W:
+            raise ValueError("%s has %d values per frame, the probe kernels take at most %d" % (on, rows.shape[1], probe.PROBE_MAX_W))
+        train, test = split_corpus(rows.contiguous(), labels, pool.lengths, refs, pool.keys, args.probe_holdout, args.probe_seed)
+        block[on] = phonerec.recognise(train[0], train[1], train[2], test[0], test[2], test[3], names, l2=args.probe_l2, iters=args.probe_iters,
+                                       penalty=args.per_phone_penalty, phone_table=table, test_y=test[1])[1]
+        del rows
+    block.update({"holdout": args.probe_holdout, "seed": args.probe_seed, "frame_shift": args.abx_frame_shift,
+                  "frame_offset": args.abx_frame_offset, "phone_penalty": args.per_phone_penalty})
+    return block
+
+
 def feature_width(model, seg_len):
     """Features per frame the checkpoint was trained on."""
     if hasattr(model, "n_feat"):
@@ -602,6 +649,13 @@ def main(argv=None) -> int:
         except (ValueError, OSError) as e:
             print("--probe-item: %s" % e, file=sys.stderr)
             return 1
+    per_block = None
+    if args.per_item is not None:
+        try:
+            per_block = per_phones(args, model, T, dev)
+        except (ValueError, OSError, RuntimeError) as e:
+            print("--per-item: %s" % e, file=sys.stderr)
+            return 1
     wavs = None
     if args.wav_out is not None:
         if args.convert_to is not None and args.convert_to not in mu2:
@@ -627,6 +681,8 @@ def main(argv=None) -> int:
         summary["qbe"] = qbe_block
     if probe_block is not None:
         summary["probe"] = probe_block
+    if per_block is not None:
+        summary["per"] = per_block
     with open(os.path.join(args.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

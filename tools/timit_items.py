@@ -1,6 +1,6 @@
 """An ABX item file (abx.read_items' format) from TIMIT's phone transcriptions.
 
-    python tools/timit_items.py RAW_DIR OUT.item [--sample-rate 16000] [--tier phn|wrd]
+    python tools/timit_items.py RAW_DIR OUT.item [--sample-rate 16000] [--tier phn|wrd|phn-all]
 
 Every .PHN / .phn file below RAW_DIR holds one `start_sample end_sample phone` line per phone, at 16 kHz.  Each phone becomes one
 item: onset and offset in seconds, the phone, the phones in front of and behind it in the file as its context, the speaker (the
@@ -10,6 +10,10 @@ be a context.  Files are walked in sorted order.  A malformed line is an error n
 
 With --tier wrd the .WRD / .wrd files are read instead (the same line format, a word in place of the phone): every word is one
 item, the word stands in the #phone column as the term (qbe.queries_from_items) and both context columns hold `-`.
+
+With --tier phn-all every phone of a .PHN file is a token, h# and the first and the last included; the context is `-` where a
+neighbour is missing.  That is the transcription phone recognition is scored against (recognise_phones.py): an alignment without
+those tokens would make every hypothesis phone over them an insertion.
 """
 import argparse
 import os
@@ -44,7 +48,7 @@ def read_phn(path):
 def timit_items(raw_dir, sample_rate=16000, tier="phn"):
     """The items of every .PHN (tier "phn") or .WRD (tier "wrd") file below raw_dir, as abx.read_items returns them."""
     items = []
-    exts = (".PHN", ".phn") if tier == "phn" else (".WRD", ".wrd")
+    exts = (".WRD", ".wrd") if tier == "wrd" else (".PHN", ".phn")
     for root, dirs, names in os.walk(raw_dir):
         dirs.sort()
         spk = os.path.basename(os.path.normpath(root)).lower()
@@ -55,6 +59,10 @@ def timit_items(raw_dir, sample_rate=16000, tier="phn"):
             rows = read_phn(os.path.join(root, name))
             if tier == "wrd":
                 items += [("%s_%s" % (spk, stem), a / sample_rate, b / sample_rate, word, "-", "-", spk) for a, b, word in rows]
+                continue
+            if tier == "phn-all":
+                items += [("%s_%s" % (spk, stem), a / sample_rate, b / sample_rate, phone, rows[k - 1][2] if k > 0 else "-",
+                           rows[k + 1][2] if k + 1 < len(rows) else "-", spk) for k, (a, b, phone) in enumerate(rows)]
                 continue
             for k in range(1, len(rows) - 1):
                 a, b, phone = rows[k]
@@ -71,7 +79,8 @@ def main(argv=None):
     ap.add_argument("raw_dir")
     ap.add_argument("out_item")
     ap.add_argument("--sample-rate", type=int, default=16000)
-    ap.add_argument("--tier", default="phn", choices=["phn", "wrd"], help="phones with their contexts (ABX), or words as search terms")
+    ap.add_argument("--tier", default="phn", choices=["phn", "wrd", "phn-all"],
+                    help="phones with their contexts (ABX), words as search terms, or every phone of a file (the transcription for PER)")
     args = ap.parse_args(argv)
     try:
         items = timit_items(args.raw_dir, args.sample_rate, args.tier)
