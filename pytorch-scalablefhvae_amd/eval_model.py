@@ -72,7 +72,9 @@ probe's split (--probe-holdout, --probe-seed, --probe-l2, --probe-iters), on fra
 and on the --baseline-feat-scp archive.  summary.json gains "per": {"z1": {per, sub, del, ins, cor, ref_tokens, utterances,
 per_argmax, frame_accuracy, frame_accuracy_argmax, classes, ...}, "feats": {...}, "holdout", "seed", "frame_shift",
 "frame_offset", "phone_penalty"}; --per-phone-map folds both sides, --per-phone-penalty is the insertion penalty.  Without
---per-item every output is what it was.
+--per-item every output is what it was.  With --per-ctc every entry of --per-on gains "ctc": {per, sub, del, ins, cor, objective,
+iterations, converged, context, dropped_infeasible, ...}: the same linear model trained by CTC (ctc.py) on the transcriptions of
+the training utterances alone, decoded greedily; --per-ctc-context K splices K frames per side.
 
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
@@ -161,6 +163,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--per-on", nargs="+", default=["z1", "feats"], choices=["z1", "feats"], help="what to recognise on: frame-level z1, the input features")
     p.add_argument("--per-phone-map", default=None, metavar="FILE", help="lines `phone target` (`-` deletes) applied to both sides")
     p.add_argument("--per-phone-penalty", type=float, default=0.0, help="subtracted from every transition between different phones")
+    p.add_argument("--per-ctc", action="store_true", help="with --per-item: also train by CTC on the transcriptions alone, decode greedily")
+    p.add_argument("--per-ctc-context", type=int, default=0, metavar="K", help="frames spliced per side for --per-ctc")
     return p
 
 
@@ -209,6 +213,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--probe-iters and --probe-l2 must not be negative")
     if args.per_item is not None and args.feat_scp is None:
         p.error("--per-item transcribes the utterances of --feat-scp data: give --feat-scp")
+    if args.per_ctc and args.per_item is None:
+        p.error("--per-ctc needs --per-item")
+    if args.per_ctc_context < 0 or (args.per_ctc_context != 0 and not args.per_ctc):
+        p.error("--per-ctc-context must not be negative and needs --per-ctc")
     if not np.isfinite(args.per_phone_penalty):
         p.error("--per-phone-penalty must be finite")
     if args.baseline_name is not None and args.baseline_feat_scp is None:
@@ -443,6 +451,12 @@ def per_phones(args, model, T, dev):
         train, test = split_corpus(rows.contiguous(), labels, pool.lengths, refs, pool.keys, args.probe_holdout, args.probe_seed)
         block[on] = phonerec.recognise(train[0], train[1], train[2], test[0], test[2], test[3], names, l2=args.probe_l2, iters=args.probe_iters,
                                        penalty=args.per_phone_penalty, phone_table=table, test_y=test[1])[1]
+        if args.per_ctc:
+            import ctc
+
+            train_refs = [refs[u] for u in probe.split_utterances(len(pool.lengths), args.probe_holdout, args.probe_seed)[0]]
+            block[on]["ctc"] = ctc.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, l2=args.probe_l2,
+                                             iters=args.probe_iters, context=args.per_ctc_context, phone_table=table)[1]
         del rows
     block.update({"holdout": args.probe_holdout, "seed": args.probe_seed, "frame_shift": args.abx_frame_shift,
                   "frame_offset": args.abx_frame_offset, "phone_penalty": args.per_phone_penalty})

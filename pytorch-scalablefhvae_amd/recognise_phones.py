@@ -7,7 +7,7 @@ sequence, which is scored against the transcription by the phone error rate (pho
         [--data-format numpy|kaldi] [--mvn-path P] [--on z1|feats] [--probe FILE.npz] [--phone-map FILE]
         [--acoustic-scale 1] [--prior-scale 1] [--phone-penalty 0] [--smooth 1]
         [--l2 1e-4] [--iters 200] [--gtol 1e-5] [--frame-shift 0.010] [--frame-offset 0.0] [--batch-size B]
-        [--compute-dtype f32|bf16]
+        [--compute-dtype f32|bf16] [--ctc [--ctc-context K] [--ctc-init zero|probe]]
 
   --checkpoint CK  optional.  Without it only --on feats is allowed: the archive's rows as read (the MFCC baseline)
   --item ITEM      the alignment (abx.read_items): it labels the training frames and, in onset order, is the transcription.  An
@@ -17,11 +17,17 @@ sequence, which is scored against the transcription by the phone error rate (pho
   --phone-map FILE lines `phone target`, a target `-` deletes: both the reference and the hypothesis are mapped after decoding
                    (TIMIT: the 61 -> 39 fold with q deleted); two neighbours that fold together stay two tokens
   --phone-penalty P  subtracted from every transition between two different phones (the insertion penalty)
+  --ctc            beside everything above, train the same linear model by CTC (ctc.py) on the transcriptions of
+                   the training utterances alone (phonerec.references: the token order; the item's times play no part) and decode
+                   the test utterances greedily.  --ctc-context K splices K frames per side; --ctc-init probe starts from the
+                   frame probe's rows (context 0 only).  At most 127 phones; an utterance without an alignment is dropped
   At most 128 phones and 128 values per frame; a reference of at most 256 tokens.
 
 It writes under --out: probe.npz, hyp.txt and ref.txt (`key p1 p2 ...`, folded) and phonerec.json: on, per, sub, del, ins, cor,
 ref_tokens, utterances, per_argmax (the collapsed per-frame arg-max instead of the Viterbi path), frame_accuracy,
 frame_accuracy_argmax, classes, folded_classes, train_frames, test_frames, iterations, converged and the settings.
+With --ctc also ctc.npz and hyp_ctc.txt, and a "ctc" block in phonerec.json: per, sub, del, ins, cor, objective, iterations,
+converged, context, dropped_infeasible (and ref_tokens, utterances, l2, init).
 """
 from __future__ import annotations
 
@@ -61,6 +67,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--frame-offset", type=float, default=0.0, help="time of frame 0 in seconds")
     p.add_argument("--batch-size", type=int, default=16384, help="windows per forward")
     p.add_argument("--compute-dtype", default=None, choices=["f32", "bf16"], help="default: the checkpoint's")
+    p.add_argument("--ctc", action="store_true", help="also train by CTC on the transcriptions alone and decode greedily")
+    p.add_argument("--ctc-context", type=int, default=0, metavar="K", help="frames spliced per side")
+    p.add_argument("--ctc-init", default="zero", choices=["zero", "probe"], help="start from zero or from the frame probe's rows")
     return p
 
 
@@ -91,6 +100,10 @@ def parse_args(argv=None):
         p.error("--frame-shift %g must be positive" % args.frame_shift)
     if args.compute_dtype is not None and args.checkpoint is None:
         p.error("--compute-dtype needs --checkpoint")
+    if not args.ctc and (args.ctc_context != 0 or args.ctc_init != "zero"):
+        p.error("--ctc-context and --ctc-init need --ctc")
+    if args.ctc_context < 0 or (args.ctc_init == "probe" and args.ctc_context != 0):
+        p.error("--ctc-context must not be negative, and --ctc-init probe needs --ctc-context 0")
     return p, args
 
 
@@ -166,8 +179,10 @@ def main(argv=None) -> int:
         if not names:
             raise ValueError("no frame of --feat-scp lies under a token of %s" % args.item)
         refs = reference_ids(phonerec.references(items, pool.keys), names)
+        train_refs = refs
         if args.test_feat_scp is None:
             train, test = split_corpus(rows, labels, pool.lengths, refs, pool.keys, args.holdout, args.seed)
+            train_refs = [refs[u] for u in probe.split_utterances(len(pool.lengths), args.holdout, args.seed)[0]]
         else:
             test_items = abx.read_items(args.test_item) if args.test_item is not None else items
             tpool = frames.pool_from_scp(args.data_format, args.test_feat_scp, args.test_len_scp, args.mvn_path, T, 1, dev)
@@ -185,6 +200,13 @@ def main(argv=None) -> int:
                                                       iters=args.iters, gtol=args.gtol, model=fitted, smooth=args.smooth,
                                                       penalty=args.phone_penalty, acoustic_scale=args.acoustic_scale,
                                                       prior_scale=args.prior_scale, phone_table=table, test_y=test[1])
+        ctc_out = None
+        if args.ctc:
+            import ctc
+
+            ctc_out = ctc.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, l2=args.l2, iters=args.iters,
+                                    gtol=args.gtol, context=args.ctc_context, init=fitted if args.ctc_init == "probe" else None,
+                                    phone_table=table)
     except (ValueError, OSError, RuntimeError) as e:
         print("recognise_phones: %s" % e, file=sys.stderr)
         return 1
@@ -199,6 +221,10 @@ def main(argv=None) -> int:
     probe.save(os.path.join(args.out, "probe.npz"), fitted)
     write_tokens(os.path.join(args.out, "hyp.txt"), test[4], hyp, folded)
     write_tokens(os.path.join(args.out, "ref.txt"), test[4], ref, folded)
+    if ctc_out is not None:
+        info["ctc"] = dict(ctc_out[1], init=args.ctc_init)
+        ctc.save(os.path.join(args.out, "ctc.npz"), ctc_out[0])
+        write_tokens(os.path.join(args.out, "hyp_ctc.txt"), test[4], ctc_out[2], folded)
     with open(os.path.join(args.out, "phonerec.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps(info))
