@@ -418,3 +418,72 @@ def test_memory_depends_on_k_not_s(hb):
         peaks.append(torch.cuda.max_memory_allocated() - base0 - pool_bytes)
         del tr, opt, m, pool
     assert abs(peaks[1] - peaks[2]) <= 1 << 20, peaks
+
+
+# ---- run lengths on the thresholds of mu2_acc_sorted_kernel (64-row probe, 256-row short / long split, 32-row pieces), at
+# ---- D that leave lanes of a workgroup idle (G D < 256) and at D = 256 (G = 1); select tiles with empty sequences at their edges
+def _accumulate_guarded(hb, idx, z, K):
+    """_accumulate in one call, with zsum / count as sub-ranges of sentinel buffers and z in front of NaN rows"""
+    dev, D, N = torch.device("cuda"), z.shape[1], len(idx)
+    zfull = torch.full((K + 4, D), -12345.0, device=dev)
+    cfull = torch.full((K + 4,), -12345.0, device=dev)
+    zs, cnt = zfull[2:K + 2], cfull[2:K + 2]
+    zs.zero_()
+    cnt.zero_()
+    zt = torch.full((N + 3, D), float("nan"), device=dev)
+    zt[:N] = torch.from_numpy(z).to(dev)
+    it = torch.full((N + 3,), 1 << 62, dtype=torch.int64, device=dev)
+    it[:N] = torch.from_numpy(idx).to(dev)
+    st = torch.zeros(1, dtype=torch.int32, device=dev)
+    hb.mu2_accumulate_sorted(zt[:N], it[:N], zs, cnt, st)
+    for full in (zfull, cfull):
+        assert (full[:2] == -12345.0).all() and (full[K + 2:] == -12345.0).all()
+    return zs.clone(), cnt.clone(), int(st.item())
+
+
+def _check_sorted(hb, lengths, D, seed):
+    idx, z = _runs(lengths, D, seed)
+    K = len(lengths)
+    zs, cnt, st = _accumulate_guarded(hb, idx, z, K)
+    assert st == 0
+    want, absum = np.zeros((K, D)), np.zeros((K, D))
+    np.add.at(want, idx, z.astype(np.float64))
+    np.add.at(absum, idx, np.abs(z.astype(np.float64)))
+    assert np.array_equal(cnt.cpu().numpy(), np.asarray(lengths, np.float32))
+    err = np.abs(zs.cpu().double().numpy() - want)
+    bound = (np.asarray(lengths)[:, None] + 2) * 2.0 ** -24 * absum + 1e-30  # as test_accumulate_sorted_oracle_and_bitwise
+    share = float((err / bound).max())
+    assert (err <= bound).all(), share
+    zs2, cnt2, _ = _accumulate_guarded(hb, idx, z, K)
+    assert torch.equal(zs, zs2) and torch.equal(cnt, cnt2)  # bitwise, run to run
+    return share
+
+
+@pytest.mark.parametrize("D", [24, 48, 100, 200, 256])
+def test_accumulate_sorted_run_lengths_on_the_thresholds(hb, D):
+    from glue_cases import sorted_run_lengths
+
+    lengths = sorted_run_lengths()
+    shares = [_check_sorted(hb, lengths, D, D),
+              _check_sorted(hb, [1], D, D + 1),      # N = 1
+              _check_sorted(hb, [0, 257, 0], D, D + 2)]  # N = 257 rows that all carry one index
+    print("measured mu2_accumulate_sorted D=%d: worst share of the bound %.3f" % (D, max(shares)))
+
+
+@pytest.mark.parametrize("K", [1024, 1025, 2049])
+def test_select_empty_sequences_at_tile_edges(hb, K):
+    S = 6000
+    counts, ptr = _csr(S, K)
+    rng = np.random.default_rng(K + 1)
+    full, empty = np.flatnonzero(counts > 0), np.flatnonzero(counts == 0)
+    block = rng.choice(full, size=K, replace=False)
+    edges = sorted({p for p in (0, 1023, 1024, K - 1) if p < K})
+    block[edges] = empty[:len(edges)]  # sequences with no segments first and last in a tile of 1024, and in the block
+    want_seg = np.concatenate([np.arange(ptr[s], ptr[s + 1]) for s in block])
+    want_loc = np.concatenate([np.full(counts[s], i) for i, s in enumerate(block)])
+    cap = len(want_seg) + 5
+    seg, loc, n, st = _select(hb, ptr, block, cap)
+    assert st == 0 and n == len(want_seg)
+    assert np.array_equal(seg[:n], want_seg) and np.array_equal(loc[:n], want_loc)
+    assert (seg[n:] == -7).all() and (loc[n:] == -7).all()
+    assert not np.isin(edges, loc[:n]).any()
