@@ -16,6 +16,8 @@ import ctypes as C
 
 import numpy as np
 
+import hip_ext
+
 #: metric of fhvae_abx_dtw, the bits of its int32 device status word and its limits (include/fhvae_abx.h, FHVAE_ABX_*)
 ABX_ANGULAR, ABX_COSINE = 0, 1
 ABX_BAD_TOKEN, ABX_BAD_PTR = 1, 2
@@ -24,11 +26,14 @@ METRICS = {"angular": ABX_ANGULAR, "cosine": ABX_COSINE}
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry point of include/fhvae_abx.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so it is bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so it is bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 ABX_SIGNATURES = {
     "fhvae_abx_dtw": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
 }
-_bound = []
+
+#: the messages of the status bits, in the order they are named (hip_ext.check_status)
+STATUS_BITS = ((ABX_BAD_TOKEN, "a token lies outside the features or is longer than %d frames" % ABX_MAX_LEN),
+               (ABX_BAD_PTR, "grp_ptr / out_ptr / pair_ptr are inconsistent"))
 
 ITEM_HEADER = "#file onset offset #phone prev-phone next-phone speaker"
 #: times are compared with the frame grid to this many frames: 0.10 s is frame 10 of a 10 ms grid although 0.10 / 0.01 > 10
@@ -38,15 +43,7 @@ DROP_REASONS = ("unknown_utterance", "no_frames", "too_long", "over_cell_cap")
 
 def load_library():
     """hip_binding.load_library() with the ABX entry point bound (argtypes from ABX_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in ABX_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(ABX_SIGNATURES)
 
 
 def group_ptrs(grp_ptr):
@@ -188,11 +185,7 @@ def tokens_from_items(items, keys, lengths, frame_shift=0.010, frame_offset=0.0,
 # --------------------------------------------------------------------------------------------------------------- distances
 def check_status(status):
     """Reads the status word (one host sync) and raises on what the kernels refused."""
-    st = int(status.item())
-    if st:
-        what = [m for bit, m in ((ABX_BAD_TOKEN, "a token lies outside the features or is longer than %d frames" % ABX_MAX_LEN),
-                                 (ABX_BAD_PTR, "grp_ptr / out_ptr / pair_ptr are inconsistent")) if st & bit]
-        raise RuntimeError("fhvae_abx_dtw: %s (status %d)" % ("; ".join(what), st))
+    hip_ext.check_status("fhvae_abx_dtw", status, STATUS_BITS)
 
 
 def pair_distances(feats_dev, tokens, metric="angular", max_block_elems=2 ** 26):
@@ -215,7 +208,7 @@ def pair_distances(feats_dev, tokens, metric="angular", max_block_elems=2 ** 26)
     host_len = np.asarray(tokens["len"], dtype=np.int32)[order]
     length = torch.from_numpy(host_len).to(dev)
     first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)  # (the groups' first tokens in `order`)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = hip_ext.status_word(dev)
     g0, G = 0, len(ids)
     while g0 < G:
         g1, elems = g0, 0

@@ -20,6 +20,9 @@ import ctypes as C
 
 import numpy as np
 
+import hip_ext
+from probe import _host_objective  # (the frame probe's, with the frames of the utterances used in place of its labelled rows)
+
 #: include/fhvae_ctc.h
 CTC_MAX_CLASSES = 128
 CTC_MAX_LABELS = 256
@@ -27,36 +30,21 @@ CTC_BAD_PTR, CTC_BAD_LABEL, CTC_INFEASIBLE = 1, 2, 4
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_ctc.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 CTC_SIGNATURES = {
     "fhvae_ctc_ws_bytes": (_i64, [_i64]),
     "fhvae_ctc_loss": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
-_bound = []
 
 
 def load_library():
     """hip_binding.load_library() with the entry points of include/fhvae_ctc.h bound (argtypes from CTC_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in CTC_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(CTC_SIGNATURES)
 
 
 # ----------------------------------------------------------------------------------------------------------------- raw call
 def _device(op, name, t, dtype, dim):
-    import torch
-
-    if t is None or not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s: %s must be a device tensor: the CTC pass runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype != dtype or t.dim() != dim:
-        raise RuntimeError("%s: %s must be %d-D %s (got %s %s)" % (op, name, dim, dtype, t.dtype, tuple(t.shape)))
-    return t
+    return hip_ext.device_tensor(op, name, t, "the CTC pass", dtype, dim)
 
 
 def _host_ptr(op, name, p):
@@ -145,7 +133,7 @@ def _padded_rows(op, logits):
     n_classes = int(logits.shape[1])
     if n_classes < 2 or n_classes > CTC_MAX_CLASSES:
         raise RuntimeError("%s: %d classes, the CTC kernel takes 2 to %d (the blank included)" % (op, n_classes, CTC_MAX_CLASSES))
-    if logits.shape[0] and (logits.stride(1) != 1 or logits.stride(0) < n_classes or logits.stride(0) % 4 or logits.data_ptr() % 16):
+    if logits.shape[0] and not hip_ext.rows_dense(logits, n_classes):
         logits = torch.nn.functional.pad(logits, (0, -n_classes % 4)) if n_classes % 4 else logits.contiguous()
     return logits
 
@@ -179,7 +167,7 @@ def loss(logits, utt_ptr, labels, lab_ptr, blank, want_grad=True, ws_limit=1 << 
     grad = torch.empty(N, (n_classes + 3) // 4 * 4, dtype=torch.float32, device=dev) if want_grad else None
     if plan.U == 0:
         return nll, (grad[:, :n_classes] if want_grad else None), 0
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = hip_ext.status_word(dev)
     _enqueue(lib, plan, logits, n_classes, labels, blank, nll, grad, status)
     bits = int(status.item())
     if bits & CTC_BAD_PTR:
@@ -209,21 +197,6 @@ def splice(x, utt_ptr, context):
 
 
 # ---------------------------------------------------------------------------------------------------------------- objective
-def _host_objective(total_nll, frames, G, params, l2, mean, std):
-    """The objective and its gradient from the device's sums: G (C, D + 1) = sum over rows of r [x_raw, 1] (bias column last);
-    probe._host_objective with the frames of the utterances used in place of the labelled rows."""
-    D = params.shape[1] - 1
-    w = params[:, :D]
-    if frames == 0:
-        return 0.0, np.zeros_like(params)
-    value = total_nll / frames + 0.5 * l2 * float(np.sum(w * w))
-    grad = np.empty_like(params)
-    # the chain rule through z = (x - mean) / std: sum r z[d] = (sum r x[d] - mean[d] sum r) / std[d]
-    grad[:, :D] = (G[:, :D] - mean[None, :] * G[:, D:]) / std[None, :] / frames + l2 * w
-    grad[:, D] = G[:, D] / frames
-    return float(value), grad
-
-
 class _Prepared:
     """Rows, labels and the plan of a training set, built once per fit."""
 
@@ -267,7 +240,7 @@ def _objective_prepared(prep, params, blank, l2, mean, std, chunk=65536):
     z = logits_of(x, tab, cst, ld, chunk)
     nll = torch.empty(plan.U, dtype=torch.float64, device=dev)
     r = torch.empty(N, ld, dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = hip_ext.status_word(dev)
     if plan.U:
         _enqueue(lib, plan, z, n_classes, prep.labels, int(blank), nll, r, status)
     out = torch.zeros(2 + n_classes * (D + 1), dtype=torch.float64, device=dev)

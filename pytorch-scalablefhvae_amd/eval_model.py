@@ -327,12 +327,7 @@ def measure_abx(args, model, T, out_dir, dev):
     block = {}
     ons = list(dict.fromkeys(args.abx_on)) + ([args.baseline_name] if args.baseline_feat_scp is not None else [])
     for on in ons:
-        if on == "z1":
-            rows = frames.encode_frames(model, pool, args.batch_size)[0]  # (shift 1: row f is frame f)
-        elif on == args.baseline_name:
-            rows = baseline_rows(args, pool, dev)
-        else:
-            rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
+        rows = baseline_rows(args, pool, dev) if on == args.baseline_name else frames.corpus_rows(model, pool, on, "ABX", args.batch_size)
         if rows.shape[1] > abx.ABX_MAX_DIM:
             raise ValueError("%s has %d values per frame, the DTW kernel takes at most %d" % (on, rows.shape[1], abx.ABX_MAX_DIM))
         res = abx.evaluate(rows.contiguous(), tokens, args.abx_distance)

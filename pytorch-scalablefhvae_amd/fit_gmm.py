@@ -86,11 +86,7 @@ def corpus_rows(model, pool, on, batch_size):
     normalised input."""
     import frames
 
-    if on == "z1":
-        rows = frames.encode_frames(model, pool, batch_size)[0]
-    else:
-        rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
-    return rows.contiguous()
+    return frames.corpus_rows(model, pool, on, "the mixture", batch_size).contiguous()
 
 
 def main(argv=None) -> int:

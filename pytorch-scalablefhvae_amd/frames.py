@@ -20,30 +20,23 @@ import ctypes as C
 
 import numpy as np
 
+import hip_ext
+
 #: bits of the int32 device status word the two kernels set (include/fhvae_frames.h, FHVAE_FRAMES_*)
 FRAMES_BAD_PTR, FRAMES_BAD_RANGE = 1, 2
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_frames.h: name -> (restype, argtypes).  They are exported from libfhvae_hip.so but are
-#: not part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: not part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 FRAMES_SIGNATURES = {
     "fhvae_frames_gather": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fhvae_frames_overlap_mean": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
-_bound = []
 
 
 def load_library():
     """hip_binding.load_library() with the frames entry points bound (argtypes from FRAMES_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in FRAMES_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(FRAMES_SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------------------ host geometry
@@ -168,7 +161,7 @@ class FramePool:
         self.F = int(self.pool.shape[1])
         dev = self.pool.device
         self.utt_ptr, self.win_ptr = torch.from_numpy(utt_ptr).to(dev), torch.from_numpy(win_ptr).to(dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.status = hip_ext.status_word(dev)
         if (mean is None) != (std is None):
             raise ValueError("mean and std come together")
         self.mean = self.std = self.inv_std = None
@@ -264,11 +257,8 @@ class FramePool:
 
     def check(self):
         """Reads the status word (one host sync) and raises on what the kernels refused."""
-        st = int(self.status.item())
-        if st:
-            what = [m for bit, m in ((FRAMES_BAD_PTR, "utt_ptr / win_ptr are inconsistent"),
-                                     (FRAMES_BAD_RANGE, "a frame's covering window lies outside the windows given")) if st & bit]
-            raise RuntimeError("frame kernels: %s (status %d)" % ("; ".join(what), st))
+        hip_ext.check_status("frame kernels", self.status, ((FRAMES_BAD_PTR, "utt_ptr / win_ptr are inconsistent"),
+                                                            (FRAMES_BAD_RANGE, "a frame's covering window lies outside the windows given")))
 
     def split_frames(self, rows):
         """(total frames, X) -> one (n_u, X) view per utterance."""
@@ -327,6 +317,16 @@ def encode_frames(model, pool: FramePool, batch_size: int = 16384):
     est.check()
     pool.check()
     return z1, z2, mu2
+
+
+def corpus_rows(model, pool: FramePool, on, what, batch_size: int = 16384):
+    """The (total frames, D) rows of a shift-1 pool that a corpus-level feature works on: "z1", encode_frames' frame-level z1
+    (shift 1: row f is frame f); "feats", the normalised input.  `what` names the feature in the ValueError for any other `on`."""
+    if on == "z1":
+        return encode_frames(model, pool, batch_size)[0]
+    if on == "feats":
+        return pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
+    raise ValueError("%s on %r: one of z1, feats" % (what, on))
 
 
 def convert_frames(model, pool: FramePool, z2=None, batch_size: int = 16384):

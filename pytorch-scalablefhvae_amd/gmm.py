@@ -20,6 +20,8 @@ import math
 
 import numpy as np
 
+import hip_ext
+
 #: include/fhvae_gmm.h, FHVAE_GMM_*
 GMM_SLICE = 1024
 GMM_MAX_DP = 64
@@ -27,28 +29,18 @@ GMM_MAX_ROWS, GMM_MAX_COMP = 1 << 30, 1 << 20
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_gmm.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 GMM_SIGNATURES = {
     "fhvae_gmm_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "fhvae_gmm_loglik": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "fhvae_gmm_post": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
     "fhvae_gmm_stats": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp]),
 }
-_bound = []
-_workspaces = {}
 
 
 def load_library():
     """hip_binding.load_library() with the mixture entry points bound (argtypes from GMM_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in GMM_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(GMM_SIGNATURES)
 
 
 def padded(width):
@@ -65,32 +57,14 @@ def ws_bytes(N, K, Dp):
 def _rows(op, name, t):
     """The (N, D) f32 rows of a call -> (rows (N, Dp), D): a device tensor with dense rows; a width that is no multiple of 8 is
     zero-padded on the device (every value of the header is unchanged), so is a view the kernels cannot take as it is."""
-    import torch
-
-    if t is None or not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise RuntimeError("%s: %s must be a 2-D tensor with at least one row and one column" % (op, name))
-    if not t.is_cuda:
-        raise RuntimeError("%s: %s is a CPU tensor: the mixture runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s: %s must be float32 (got %s)" % (op, name, t.dtype))
-    D = int(t.shape[1])
-    if D > GMM_MAX_DP:
-        raise RuntimeError("%s: %s has %d columns, the mixture kernels take at most %d" % (op, name, D, GMM_MAX_DP))
-    if t.shape[0] > GMM_MAX_ROWS:
-        raise RuntimeError("%s: %s has %d rows, the mixture kernels take at most %d" % (op, name, t.shape[0], GMM_MAX_ROWS))
-    if D % 8:
-        t = torch.nn.functional.pad(t, (0, 8 - D % 8))
-    elif t.stride(1) != 1 or t.stride(0) < D or t.stride(0) % 4 or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t, D
+    return hip_ext.padded_rows(op, name, t, "the mixture", 8, GMM_MAX_DP, GMM_MAX_ROWS)
 
 
 def _device_f32(op, name, t, shape):
     import torch
 
-    if t is None or not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s: %s must be a device tensor: the mixture runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+    hip_ext.device_tensor(op, name, t, "the mixture")
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):  # (this module's wording: "float32", not "torch.float32")
         raise RuntimeError("%s: %s must be float32 of shape %s (got %s %s)" % (op, name, tuple(shape), t.dtype, tuple(t.shape)))
     return t
 
@@ -195,22 +169,17 @@ def posteriors(x, tab, cst, loglik, out=None):
 
 def _post_rows(op, name, t, N, K):
     _device_f32(op, name, t, (N, K))
-    if t.stride(1) != 1 or t.stride(0) < K or t.stride(0) % 4 or t.data_ptr() % 16:
+    if not hip_ext.rows_dense(t, K):
         raise RuntimeError("%s: %s needs dense rows, a row stride that is a multiple of 4 and a 16-byte aligned start (strides %s)"
                            % (op, name, tuple(t.stride())))
 
 
 def _workspace(dev, N, K, Dp):
-    import torch
-
     need = int(load_library().fhvae_gmm_ws_bytes(N, K, Dp))
     if need <= 0:
         raise RuntimeError("accumulate: %d rows / %d components / %d columns lie outside the kernels' limits (%d rows, %d components)"
                            % (N, K, Dp, GMM_MAX_ROWS, GMM_MAX_COMP))
-    ws = _workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _workspaces[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
+    return hip_ext.workspace("gmm", dev, need)
 
 
 def accumulate(x, post, stats=None):

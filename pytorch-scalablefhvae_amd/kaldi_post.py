@@ -19,35 +19,28 @@ import math
 
 import numpy as np
 
+import hip_ext
+
 #: the bit of the int32 device status word and the limits (include/fhvae_kaldi_post.h, FHVAE_KPOST_*)
 KPOST_BAD_PTR = 1
 KPOST_MAX_BINS, KPOST_MAX_WINDOW, KPOST_MAX_COLS, KPOST_CHUNK = 128, 8, 1024, 256
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_kaldi_post.h: name -> (restype, argtypes).  They are exported from libfhvae_hip.so but are
-#: not part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: not part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 KPOST_SIGNATURES = {
     "fhvae_kaldi_cepstra": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, C.c_float, _vp, _vp]),
     "fhvae_kaldi_add_deltas": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_kaldi_post_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "fhvae_kaldi_cmvn_sliding": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp]),
 }
-_bound = []
 
 KPOST_WHAT = "fhvae_kaldi_add_deltas / fhvae_kaldi_cmvn_sliding: status %s (inconsistent frame_ptr)"
 
 
 def load_library():
     """hip_binding.load_library() with the entry points above bound (argtypes from KPOST_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in KPOST_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(KPOST_SIGNATURES)
 
 
 # ------------------------------------------------------------------------------------------------------------ host side
@@ -230,13 +223,8 @@ def cmvn_spec(cmn_window=300, min_window=100, center=True, norm_vars=False):
 
 
 # ------------------------------------------------------------------------------------------------------ device batches
-def _status(device):
-    import torch
-
-    return torch.zeros(1, dtype=torch.int32, device=device)
-
-
 def _check_status(status):
+    """(KPOST_WHAT is the wording of features._download's status errors, which the batches below also raise through)"""
     st = int(status.cpu().item())
     if st:
         raise RuntimeError(KPOST_WHAT % st)
@@ -291,7 +279,7 @@ def add_deltas(x, frame_ptr, order=2, window=2, status=None):
 
     load_library()
     own = status is None
-    status = _status(x.device) if own else status
+    status = hip_ext.status_word(x.device) if own else status
     hb._need_gpu(x, frame_ptr, status)
     op = "kaldi_add_deltas"
     hb._want(op, "x", x, torch.float32, ndim=2)
@@ -316,7 +304,7 @@ def cmvn_sliding(x, frame_ptr, cmn_window=600, min_window=100, center=False, nor
 
     lib = load_library()
     own = status is None
-    status = _status(x.device) if own else status
+    status = hip_ext.status_word(x.device) if own else status
     hb._need_gpu(x, frame_ptr, status)
     op = "kaldi_cmvn_sliding"
     hb._want(op, "x", x, torch.float32, ndim=2)
@@ -375,7 +363,7 @@ def _feats_batch(hb, waves, ids, fb, mfcc, sizes, seed, bases, consts, device, c
     dither = float(fb["dither"])
     ids_d = torch.from_numpy(np.asarray(ids, dtype=np.uint64).view(np.int64).copy()).to(device) if dither != 0.0 else None
     x = torch.empty((n, n_mels), dtype=torch.float32, device=device)
-    status, vstatus, kstatus = _status(device), _status(device), _status(device)
+    status, vstatus, kstatus = hip_ext.status_word(device), hip_ext.status_word(device), hip_ext.status_word(device)
     flags = (hb.KALDI_REMOVE_DC if fb["remove-dc-offset"] else 0) | hb.KALDI_USE_LOG | hb.KALDI_USE_POWER if mfcc is not None else (
         (hb.KALDI_REMOVE_DC if fb["remove-dc-offset"] else 0) | (hb.KALDI_USE_LOG if fb["use-log-fbank"] else 0)
         | (hb.KALDI_USE_POWER if fb["use-power"] else 0))
@@ -494,7 +482,7 @@ def post_process(mats, deltas=None, cmvn=None, device="cuda", max_frames=1 << 20
         frame_ptr = F._ptr([len(m) for m in mats[a:b]])
         x = F._upload(mats[a:b], device)
         ptr_d = torch.from_numpy(frame_ptr).to(device)
-        status = _status(device)
+        status = hip_ext.status_word(device)
         x = apply_post(x, ptr_d, deltas, cmvn, status)
         if compress is None:
             out.extend(F._download(x, (status,), KPOST_WHAT, frame_ptr))

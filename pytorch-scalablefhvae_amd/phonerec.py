@@ -17,6 +17,8 @@ import ctypes as C
 
 import numpy as np
 
+import hip_ext
+
 #: include/fhvae_viterbi.h
 VIT_MAX_STATES = 128
 EDIT_MAX_REF = 256
@@ -25,43 +27,28 @@ EDIT_BAD_PTR, EDIT_BAD_REF = 1, 2
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_viterbi.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 PHONEREC_SIGNATURES = {
     "fhvae_vit_ws_bytes": (_i64, [_i64, _i64]),
     "fhvae_vit_decode": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fhvae_edit_align": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
-_bound = []
 
 
 def load_library():
     """hip_binding.load_library() with the entry points of include/fhvae_viterbi.h bound (argtypes from PHONEREC_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in PHONEREC_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(PHONEREC_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------- raw calls
-def _device(op, name, t, dtypes, dim):
-    import torch
-
-    if t is None or not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s: %s must be a device tensor: phone recognition runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype not in dtypes or t.dim() != dim:
-        raise RuntimeError("%s: %s must be %d-D %s (got %s %s)" % (op, name, dim, " or ".join(str(d) for d in dtypes), t.dtype, tuple(t.shape)))
-    return t
+def _device(op, name, t, dtype, dim):
+    return hip_ext.device_tensor(op, name, t, "phone recognition", dtype, dim)
 
 
 def _ptr(op, name, t):
     import torch
 
-    t = _device(op, name, t, (torch.int64,), 1)
+    t = _device(op, name, t, torch.int64, 1)
     if t.shape[0] < 1:
         raise RuntimeError("%s: %s must hold U + 1 entries" % (op, name))
     return t.contiguous()
@@ -76,12 +63,12 @@ def viterbi(emit, utt_ptr, trans, init, fin=None):
     import hip_binding as hb
 
     op = "viterbi"
-    emit = _device(op, "emit", emit, (torch.float32,), 2)
+    emit = _device(op, "emit", emit, torch.float32, 2)
     utt_ptr = _ptr(op, "utt_ptr", utt_ptr)
-    trans = _device(op, "trans", trans, (torch.float32,), 2).contiguous()
-    init = _device(op, "init", init, (torch.float32,), 1).contiguous()
+    trans = _device(op, "trans", trans, torch.float32, 2).contiguous()
+    init = _device(op, "init", init, torch.float32, 1).contiguous()
     if fin is not None:
-        fin = _device(op, "fin", fin, (torch.float32,), 1).contiguous()
+        fin = _device(op, "fin", fin, torch.float32, 1).contiguous()
     N, n_states = int(emit.shape[0]), int(emit.shape[1])
     if n_states < 1 or n_states > VIT_MAX_STATES:
         raise RuntimeError("%s: %d states, the decoder takes 1 to %d" % (op, n_states, VIT_MAX_STATES))
@@ -91,14 +78,14 @@ def viterbi(emit, utt_ptr, trans, init, fin=None):
     dev = emit.device
     if N == 0:
         emit = torch.zeros(1, 4, dtype=torch.float32, device=dev)
-    elif emit.stride(1) != 1 or emit.stride(0) < n_states or emit.stride(0) % 4 or emit.data_ptr() % 16:  # (else: taken as it is)
+    elif not hip_ext.rows_dense(emit, n_states):  # (else: taken as it is)
         emit = torch.nn.functional.pad(emit, (0, -n_states % 4)) if n_states % 4 else emit.contiguous()
     U = int(utt_ptr.shape[0]) - 1
     path = torch.empty(N, dtype=torch.int32, device=dev)
     score = torch.empty(U, dtype=torch.float32, device=dev)
     if U == 0:
         return path, score
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = hip_ext.status_word(dev)
     need = int(lib.fhvae_vit_ws_bytes(N, n_states))
     ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
     out = path if N else torch.empty(1, dtype=torch.int32, device=dev)
@@ -117,8 +104,8 @@ def align(ref, ref_ptr, hyp, hyp_ptr):
     import hip_binding as hb
 
     op = "align"
-    ref = _device(op, "ref", ref, (torch.int32,), 1).contiguous()
-    hyp = _device(op, "hyp", hyp, (torch.int32,), 1).contiguous()
+    ref = _device(op, "ref", ref, torch.int32, 1).contiguous()
+    hyp = _device(op, "hyp", hyp, torch.int32, 1).contiguous()
     ref_ptr, hyp_ptr = _ptr(op, "ref_ptr", ref_ptr), _ptr(op, "hyp_ptr", hyp_ptr)
     if ref_ptr.shape != hyp_ptr.shape:
         raise RuntimeError("%s: ref_ptr holds %d entries, hyp_ptr %d" % (op, ref_ptr.shape[0], hyp_ptr.shape[0]))
@@ -130,7 +117,7 @@ def align(ref, ref_ptr, hyp, hyp_ptr):
     if int(ref_ptr[-1]) > ref.shape[0] or int(hyp_ptr[-1]) > hyp.shape[0]:
         raise RuntimeError("%s: the pointers run past the %d / %d tokens" % (op, ref.shape[0], hyp.shape[0]))
     one = torch.zeros(1, dtype=torch.int32, device=ref.device)  # (an empty token array has no address)
-    status = torch.zeros(1, dtype=torch.int32, device=ref.device)
+    status = hip_ext.status_word(ref.device)
     hb._call("fhvae_edit_align", hb._p(ref if ref.numel() else one), hb._p(ref_ptr), hb._p(hyp if hyp.numel() else one), hb._p(hyp_ptr), U,
              hb._p(counts), hb._p(status))
     bits = int(status.item())

@@ -21,34 +21,27 @@ import math
 
 import numpy as np
 
+import hip_ext
+
 #: include/fhvae_probe.h, FHVAE_PROBE_*
 PROBE_SLICE = 1024
 PROBE_MAX_W = 128
 PROBE_MAX_ROWS, PROBE_MAX_CLASSES = 1 << 30, 1 << 16
+NOUN = "the probe"  # (in the messages of hip_ext's checks)
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_probe.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 PROBE_SIGNATURES = {
     "fhvae_probe_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "fhvae_probe_rows": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fhvae_probe_grad": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
-_bound = []
-_workspaces = {}
 
 
 def load_library():
     """hip_binding.load_library() with the probe entry points bound (argtypes from PROBE_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in PROBE_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(PROBE_SIGNATURES)
 
 
 def padded(width):
@@ -67,34 +60,11 @@ def ws_bytes(N, n_classes, W):
 def _rows(op, name, t):
     """The (N, D) f32 rows of a call -> (rows (N, W), D): a device tensor with dense rows; a width that is no multiple of 16 is
     zero-padded on the device (every value of the header is unchanged), so is a view the kernels cannot take as it is."""
-    import torch
-
-    if t is None or not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise RuntimeError("%s: %s must be a 2-D tensor with at least one row and one column" % (op, name))
-    if not t.is_cuda:
-        raise RuntimeError("%s: %s is a CPU tensor: the probe runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s: %s must be float32 (got %s)" % (op, name, t.dtype))
-    D = int(t.shape[1])
-    if D > PROBE_MAX_W:
-        raise RuntimeError("%s: %s has %d columns, the probe kernels take at most %d" % (op, name, D, PROBE_MAX_W))
-    if t.shape[0] > PROBE_MAX_ROWS:
-        raise RuntimeError("%s: %s has %d rows, the probe kernels take at most %d" % (op, name, t.shape[0], PROBE_MAX_ROWS))
-    if D % 16:
-        t = torch.nn.functional.pad(t, (0, 16 - D % 16))
-    elif t.stride(1) != 1 or t.stride(0) < D or t.stride(0) % 4 or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t, D
+    return hip_ext.padded_rows(op, name, t, NOUN, 16, PROBE_MAX_W, PROBE_MAX_ROWS)
 
 
 def _device(op, name, t, dtype, shape):
-    import torch
-
-    if t is None or not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s: %s must be a device tensor: the probe runs on a MI355X only (no CPU fallback)" % (op, name))
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise RuntimeError("%s: %s must be contiguous %s of shape %s (got %s %s)" % (op, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-    return t
+    return hip_ext.device_tensor(op, name, t, NOUN, dtype, shape=shape, contiguous=True)
 
 
 def _labels(op, y, N, n_classes):
@@ -102,8 +72,7 @@ def _labels(op, y, N, n_classes):
     'unlabelled')."""
     import torch
 
-    if y is None or not isinstance(y, torch.Tensor) or not y.is_cuda:
-        raise RuntimeError("%s: y must be a device tensor: the probe runs on a MI355X only (no CPU fallback)" % op)
+    hip_ext.device_tensor(op, "y", y, NOUN)
     if y.dim() != 1 or int(y.shape[0]) != N or y.dtype not in (torch.int32, torch.int64):
         raise RuntimeError("%s: y must be (%d,) int32 or int64 (got %s %s)" % (op, N, y.dtype, tuple(y.shape)))
     top = int(y.max())
@@ -154,16 +123,11 @@ def _pass_args(op, x, y, tab, cst):
 
 
 def _workspace(op, dev, N, n_classes, W):
-    import torch
-
     need = int(load_library().fhvae_probe_ws_bytes(N, n_classes, W))
     if need <= 0:
         raise RuntimeError("%s: %d rows / %d classes / %d columns lie outside the kernels' limits (%d rows, %d classes)"
                            % (op, N, n_classes, W, PROBE_MAX_ROWS, PROBE_MAX_CLASSES))
-    ws = _workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _workspaces[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
+    return hip_ext.workspace("probe", dev, need)
 
 
 def _enqueue_rows(x, y, tab, cst, W, n_classes, totals):

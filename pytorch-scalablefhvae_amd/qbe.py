@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 import abx
+import hip_ext
 
 #: metric of fhvae_qbe_sdtw (abx.METRICS' codes), the bits of its int32 device status word and its limits (include/fhvae_qbe.h)
 QBE_ANGULAR, QBE_COSINE = 0, 1
@@ -28,26 +29,20 @@ METRICS = {"angular": QBE_ANGULAR, "cosine": QBE_COSINE}
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry point of include/fhvae_qbe.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so it is bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so it is bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 QBE_SIGNATURES = {
     "fhvae_qbe_sdtw": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-_bound = []
 
+#: the messages of the status bits, in the order they are named (hip_ext.check_status)
+STATUS_BITS = ((QBE_BAD_QUERY, "a query lies outside the features or is longer than its bound (at most %d frames)" % QBE_MAX_QLEN),
+               (QBE_BAD_PTR, "utt_ptr is not monotone from 0 to the number of frames"))
 DROP_REASONS = ("unknown_utterance", "no_frames", "too_long", "over_term_cap")
 
 
 def load_library():
     """hip_binding.load_library() with the search entry point bound (argtypes from QBE_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in QBE_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(QBE_SIGNATURES)
 
 
 def sdtw(qfeats, q_start, q_len, feats, utt_ptr, metric, status, max_qlen=QBE_MAX_QLEN, profile=False, out=None):
@@ -91,11 +86,7 @@ def sdtw(qfeats, q_start, q_len, feats, utt_ptr, metric, status, max_qlen=QBE_MA
 
 def check_status(status):
     """Reads the status word (one host sync) and raises on what the kernels refused."""
-    st = int(status.item())
-    if st:
-        what = [m for bit, m in ((QBE_BAD_QUERY, "a query lies outside the features or is longer than its bound (at most %d frames)" % QBE_MAX_QLEN),
-                                 (QBE_BAD_PTR, "utt_ptr is not monotone from 0 to the number of frames")) if st & bit]
-        raise RuntimeError("fhvae_qbe_sdtw: %s (status %d)" % ("; ".join(what), st))
+    hip_ext.check_status("fhvae_qbe_sdtw", status, STATUS_BITS)
 
 
 # ------------------------------------------------------------------------------------------------------------------- items
@@ -192,7 +183,7 @@ def search(qfeats_dev, queries, feats_dev, utt_ptr, metric="angular", profile=Fa
     order = np.argsort(host_len, kind="stable")
     start, length = torch.from_numpy(host_start[order]).to(dev), torch.from_numpy(host_len[order]).to(dev)
     ptr = torch.from_numpy(utt_ptr).to(dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = hip_ext.status_word(dev)
     names = ("best_cost", "best_start", "best_end", "end_cost", "end_start")
     sorted_len = host_len[order]
     a = 0
@@ -302,13 +293,7 @@ def corpus_rows(model, pool, on, batch_size=16384):
     "feats", the normalised input.  More than QBE_MAX_DIM values per frame raise ValueError."""
     import frames
 
-    if on == "z1":
-        rows = frames.encode_frames(model, pool, batch_size)[0]  # (shift 1: row f is frame f)
-    elif on == "feats":
-        rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
-    else:
-        raise ValueError("search on %r: one of z1, feats" % (on,))
-    return checked_rows(rows, on)
+    return checked_rows(frames.corpus_rows(model, pool, on, "search", batch_size), on)
 
 
 def checked_rows(rows, on):

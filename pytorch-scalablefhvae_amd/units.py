@@ -18,6 +18,8 @@ import ctypes as C
 
 import numpy as np
 
+import hip_ext
+
 #: the bits of fhvae_km_update's int32 device status word and the limits (include/fhvae_kmeans.h, FHVAE_KM_*)
 KM_BAD_PTR, KM_BAD_PERM = 1, 2
 KM_PIECE = 256
@@ -26,29 +28,17 @@ KM_MAX_DIM = 128  # (csrc/allpairs_f32.h: D a multiple of 16 in [16, 128])
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_kmeans.h: name -> (restype, argtypes).  Exported from libfhvae_hip.so but not part of
-#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 KM_SIGNATURES = {
     "fhvae_km_ws_bytes": (_i64, [_i64, _i64, _i64]),
     "fhvae_km_assign": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "fhvae_km_update": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
-_bound = []
-_workspaces = {}
-
-ON = ("z1", "feats")
 
 
 def load_library():
     """hip_binding.load_library() with the k-means entry points bound (argtypes from KM_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in KM_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(KM_SIGNATURES)
 
 
 # ---------------------------------------------------------------------------------------------------------------- raw calls
@@ -63,23 +53,18 @@ def _rows(op, name, t, width=None):
     if D < 16 or D > KM_MAX_DIM or D % 16 or (width is not None and D != width):
         raise ValueError("%s: %s has %d columns; the kernels take a multiple of 16 in [16, %d]%s"
                          % (op, name, D, KM_MAX_DIM, "" if width is None else ", here %d" % width))
-    if t.stride(1) != 1 or t.stride(0) < D or t.stride(0) % 4 or t.data_ptr() % 16:
+    if not hip_ext.rows_dense(t, D):
         raise RuntimeError("%s: %s needs dense rows, a row stride that is a multiple of 4 and a 16-byte aligned start "
                            "(strides %s)" % (op, name, tuple(t.stride())))
     return t
 
 
 def _workspace(dev, N, K, D):
-    import torch
-
     need = int(load_library().fhvae_km_ws_bytes(N, K, D))
     if need <= 0:
         raise ValueError("k-means: %d rows / %d centroids / %d columns lie outside the kernels' limits (%d rows, %d centroids)"
                          % (N, K, D, KM_MAX_ROWS, KM_MAX_CENT))
-    ws = _workspaces.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _workspaces[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
+    return hip_ext.workspace("units", dev, need)
 
 
 def assign(x, cent, want_dist=True):
@@ -138,21 +123,16 @@ def members(labels, K):
 
 def check_status(status):
     """Reads the status word (one host sync) and raises on what the kernels refused."""
-    st = int(status.item())
-    if st:
-        what = [m for bit, m in ((KM_BAD_PTR, "cl_ptr is not monotone from 0 to N (a label outside [0, K)?)"),
-                                 (KM_BAD_PERM, "a perm entry lies outside [0, N)")) if st & bit]
-        raise RuntimeError("fhvae_km_update: %s (status %d)" % ("; ".join(what), st))
+    hip_ext.check_status("fhvae_km_update", status, ((KM_BAD_PTR, "cl_ptr is not monotone from 0 to N (a label outside [0, K)?)"),
+                                                    (KM_BAD_PERM, "a perm entry lies outside [0, N)")))
 
 
 def update(x, labels, cent, dist=None):
     """The centroid update for `labels` (N,) int32 on the device: cent (K, D) becomes, in place, the mean of every cluster's rows
     (include/fhvae_kmeans.h: two-level float64 sums in row order; a cluster without rows keeps its centroid).  -> (count (K,)
     int64, cl_inertia (K,) float64: the clusters' sums of dist, 0 without dist).  One host sync, for the status word."""
-    import torch
-
     perm, cl_ptr = members(labels, int(cent.shape[0]))
-    status = torch.zeros(1, dtype=torch.int32, device=x.device)
+    status = hip_ext.status_word(x.device)
     out = update_members(x, perm, cl_ptr, cent, status, dist)
     check_status(status)
     return out
@@ -178,8 +158,6 @@ def reseed(labels, dist, counts):
 
 
 def _lloyd(x, cent, iters, tol):
-    import torch
-
     K = int(cent.shape[0])
     prev, prev_inertia, reseeded, converged = None, None, 0, False
     for it in range(1, iters + 1):
@@ -190,7 +168,7 @@ def _lloyd(x, cent, iters, tol):
             reseeded += 1
             perm, cl_ptr = members(labels, K)
         changed = True if prev is None else bool((labels != prev).any())
-        status = torch.zeros(1, dtype=torch.int32, device=x.device)
+        status = hip_ext.status_word(x.device)
         counts, cl_inertia = update_members(x, perm, cl_ptr, cent, status, dist)
         inertia = float(np.sum(cl_inertia.cpu().numpy(), dtype=np.float64))
         check_status(status)
@@ -371,12 +349,7 @@ def corpus_rows(model, pool, on, batch_size=16384):
 
     import frames
 
-    if on == "z1":
-        rows = frames.encode_frames(model, pool, batch_size)[0]
-    elif on == "feats":
-        rows = pool.pool if pool.mean is None else (pool.pool - pool.mean) * pool.inv_std
-    else:
-        raise ValueError("units on %r: one of %s" % (on, ", ".join(ON)))
+    rows = frames.corpus_rows(model, pool, on, "units", batch_size)
     width = int(rows.shape[1])
     if width > KM_MAX_DIM:
         raise ValueError("%s has %d values per frame, the k-means kernels take at most %d" % (on, width, KM_MAX_DIM))

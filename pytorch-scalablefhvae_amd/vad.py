@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+import hip_ext
+
 #: mode of fhvae_vad_energy, its flag, and the bits of the int32 device status word (include/fhvae_vad.h, FHVAE_VAD_*)
 VAD_RMS_CENTER, VAD_LOGE_SNIP = 0, 1
 VAD_REMOVE_DC = 1
@@ -21,27 +23,18 @@ VAD_MAX_FRAME, VAD_MAX_CTX, VAD_CHUNK, VAD_TILE = 4096, 1024, 1024, 1024
 
 _vp, _i64 = C.c_void_p, C.c_int64
 #: the entry points of include/fhvae_vad.h: name -> (restype, argtypes).  They are exported from libfhvae_hip.so but are not
-#: part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound here and not in hip_binding.SIGNATURES
+#: part of include/fhvae_hip.h (ABI 12 is unchanged), so they are bound from this table (hip_ext.load) and not in hip_binding.SIGNATURES
 VAD_SIGNATURES = {
     "fhvae_vad_energy": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp]),
     "fhvae_vad_ws_bytes": (_i64, [_i64, _i64]),
     "fhvae_vad_decide": (C.c_int, [_vp, _vp, _i64, _i64, C.c_double, C.c_double, _i64, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp]),
     "fhvae_vad_select": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
 }
-_bound = []
 
 
 def load_library():
     """hip_binding.load_library() with the VAD entry points bound (argtypes from VAD_SIGNATURES)."""
-    import hip_binding as hb
-
-    lib = hb.load_library()
-    if not _bound:
-        for name, (res, args) in VAD_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks the symbol
-            fn.restype, fn.argtypes = res, args
-        _bound.append(lib)
-    return lib
+    return hip_ext.load(VAD_SIGNATURES)
 
 
 def energy(wave, wave_ptr, frame_ptr, n_frames, frame_len, frame_shift, mode, flags, status):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import abx_ref as R
+import ext_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -192,13 +193,8 @@ def test_signature_matches_the_header():
     import abx
     import hip_binding as hb
 
-    text = open(os.path.join(ROOT, "include", "fhvae_abx.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_abx_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_abx.h")
+    found = ext_abi.declared("fhvae_abx.h", "fhvae_abx_")
     assert found == abx.ABX_SIGNATURES and sorted(found) == ["fhvae_abx_dtw"]
     assert not set(found) & set(hb.SIGNATURES)
     for name, value in (("MAX_DIM", abx.ABX_MAX_DIM), ("MAX_LEN", abx.ABX_MAX_LEN)):

@@ -3,7 +3,6 @@ against brute-force enumeration and against finite differences; the infeasible a
 ctc.objective's host side against torch autograd, ctc.greedy on hand-written rows, save / load; CTC_SIGNATURES against
 include/fhvae_ctc.h and the built library, fhvae_ctc_ws_bytes and the argument errors of fhvae_ctc_loss (they return before any
 launch)."""
-import ctypes
 import os
 import re
 
@@ -12,6 +11,8 @@ import pytest
 import torch
 
 import ctc_ref as R
+import ext_abi
+from ext_abi import swap as _swap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
@@ -238,13 +239,8 @@ def test_signatures_match_the_header():
     import ctc
     import hip_binding as hb
 
-    text = open(os.path.join(ROOT, "include", "fhvae_ctc.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_ctc.h")
+    found = ext_abi.declared("fhvae_ctc.h", "fhvae_")
     assert found == ctc.CTC_SIGNATURES and sorted(found) == ["fhvae_ctc_loss", "fhvae_ctc_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
     assert int(re.search(r"#define FHVAE_CTC_MAX_CLASSES (\d+)", text).group(1)) == ctc.CTC_MAX_CLASSES == 128
@@ -272,10 +268,6 @@ def test_workspace_bytes(lib):
         v = f(cells)
         assert v >= last and v % 256 == 0 and 8 * cells <= v < 8 * cells + 256
         last = v
-
-
-def _swap(good, i, v):
-    return [v if j == i else a for j, a in enumerate(good)]
 
 
 def test_loss_errors_before_any_launch(lib):

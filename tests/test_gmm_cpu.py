@@ -1,7 +1,6 @@
 """The mixture without a GPU: the oracle (tests/gmm_ref.py) against itself, gmm.mstep against the oracle's, save / load, the
 chunking of estep, GMM_SIGNATURES against include/fhvae_gmm.h, the entry points' argument errors (they return before any
 launch), the workspace size, the refusals of the raw calls and fit_gmm.py's argument errors."""
-import ctypes
 import os
 import re
 
@@ -10,6 +9,8 @@ import pytest
 import torch
 
 import gmm_ref as R
+import ext_abi
+from ext_abi import aligned as _aligned, swap as _swap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
@@ -151,13 +152,8 @@ def test_signatures_match_the_header():
     import gmm
     import hip_binding as hb
 
-    text = open(os.path.join(ROOT, "include", "fhvae_gmm.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_gmm_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_gmm.h")
+    found = ext_abi.declared("fhvae_gmm.h", "fhvae_gmm_")
     assert found == gmm.GMM_SIGNATURES
     assert sorted(found) == ["fhvae_gmm_loglik", "fhvae_gmm_post", "fhvae_gmm_stats", "fhvae_gmm_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
@@ -175,16 +171,6 @@ def test_symbols_exported_and_the_main_header_untouched(lib):
     assert lib.fhvae_abi_version() == 12 and len(hb.SIGNATURES) == 81  # include/fhvae_hip.h is untouched
     header = open(os.path.join(ROOT, "include", "fhvae_hip.h")).read()
     assert "fhvae_gmm_" not in header and "gmm" not in header.lower()
-
-
-def _aligned():
-    """(keep-alive, a 16-byte aligned host address): the calls below return before anything would read it"""
-    buf = np.zeros(4096 + 16, dtype=np.uint8)
-    return buf, (buf.ctypes.data + 15) & ~15
-
-
-def _swap(good, i, v):
-    return [v if j == i else a for j, a in enumerate(good)]
 
 
 def test_loglik_errors_before_any_launch(lib):

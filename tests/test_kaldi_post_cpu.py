@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import kaldi_post_ref as R
+import ext_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,16 +29,8 @@ def test_signatures_match_the_header():
     import hip_binding as hb
     import kaldi_post as KP
 
-    text = open(os.path.join(ROOT, "include", "fhvae_kaldi_post.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_kaldi_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            types.append(ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]])
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_kaldi_post.h")
+    found = ext_abi.declared("fhvae_kaldi_post.h", "fhvae_kaldi_")
     assert found == KP.KPOST_SIGNATURES
     assert sorted(found) == ["fhvae_kaldi_add_deltas", "fhvae_kaldi_cepstra", "fhvae_kaldi_cmvn_sliding", "fhvae_kaldi_post_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
@@ -69,8 +62,7 @@ def test_symbols_exported_and_errors_before_any_launch(lib):
     NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
     inf = float("inf")
 
-    def swap(good, i, v):
-        return [v if j == i else a for j, a in enumerate(good)]
+    swap = ext_abi.swap
 
     ce = lib.fhvae_kaldi_cepstra
     #       logmel ld  n  B   dct C  lifter energy floor out stream

@@ -2,7 +2,6 @@
 argument errors (they return before any launch), the oracles of tests/viterbi_ref.py against brute force, the host pieces of
 phonerec.py (transitions, collapse, fold, read_phone_map, references, error_rate), tools/timit_items.py --tier phn-all, the
 command lines' argument errors and the margin of the generator's corpus."""
-import ctypes
 import itertools
 import os
 import re
@@ -12,6 +11,8 @@ import pytest
 import torch
 
 import viterbi_ref as R
+import ext_abi
+from ext_abi import aligned as _aligned, swap as _swap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
@@ -32,13 +33,8 @@ def test_signatures_match_the_header():
     import hip_binding as hb
     import phonerec
 
-    text = open(os.path.join(ROOT, "include", "fhvae_viterbi.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_viterbi.h")
+    found = ext_abi.declared("fhvae_viterbi.h", "fhvae_")
     assert found == phonerec.PHONEREC_SIGNATURES
     assert sorted(found) == ["fhvae_edit_align", "fhvae_vit_decode", "fhvae_vit_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
@@ -58,16 +54,6 @@ def test_symbols_exported_and_the_main_header_untouched(lib):
     assert lib.fhvae_abi_version() == 12 and len(hb.SIGNATURES) == 81  # include/fhvae_hip.h is untouched
     main = open(os.path.join(ROOT, "include", "fhvae_hip.h")).read().lower()
     assert "viterbi" not in main and "fhvae_vit" not in main and "fhvae_edit" not in main
-
-
-def _aligned():
-    """(keep-alive, a 16-byte aligned host address): the calls below return before anything would read it"""
-    buf = np.zeros(4096 + 16, dtype=np.uint8)
-    return buf, (buf.ctypes.data + 15) & ~15
-
-
-def _swap(good, i, v):
-    return [v if j == i else a for j, a in enumerate(good)]
 
 
 def test_decode_errors_before_any_launch(lib):

@@ -2,7 +2,6 @@
 driven by the oracle's objective, PROBE_SIGNATURES against include/fhvae_probe.h, the entry points' argument errors (they return
 before any launch), the workspace size, the refusals of the raw calls, frame_labels, split_utterances, save / load and both
 command lines' argument errors."""
-import ctypes
 import os
 import re
 
@@ -11,6 +10,8 @@ import pytest
 import torch
 
 import probe_ref as R
+import ext_abi
+from ext_abi import aligned as _aligned, swap as _swap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
@@ -129,13 +130,8 @@ def test_signatures_match_the_header():
     import hip_binding as hb
     import probe
 
-    text = open(os.path.join(ROOT, "include", "fhvae_probe.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_probe_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_probe.h")
+    found = ext_abi.declared("fhvae_probe.h", "fhvae_probe_")
     assert found == probe.PROBE_SIGNATURES
     assert sorted(found) == ["fhvae_probe_grad", "fhvae_probe_rows", "fhvae_probe_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
@@ -153,16 +149,6 @@ def test_symbols_exported_and_the_main_header_untouched(lib):
         assert hasattr(lib, name) and name not in hb.SIGNATURES
     assert lib.fhvae_abi_version() == 12 and len(hb.SIGNATURES) == 81  # include/fhvae_hip.h is untouched
     assert "probe" not in open(os.path.join(ROOT, "include", "fhvae_hip.h")).read().lower()
-
-
-def _aligned():
-    """(keep-alive, a 16-byte aligned host address): the calls below return before anything would read it"""
-    buf = np.zeros(4096 + 16, dtype=np.uint8)
-    return buf, (buf.ctypes.data + 15) & ~15
-
-
-def _swap(good, i, v):
-    return [v if j == i else a for j, a in enumerate(good)]
 
 
 def test_rows_errors_before_any_launch(lib):

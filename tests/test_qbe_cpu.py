@@ -11,6 +11,7 @@ import pytest
 
 import abx_ref
 import qbe_ref as R
+import ext_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,13 +32,8 @@ def test_signature_matches_the_header():
     import hip_binding as hb
     import qbe
 
-    text = open(os.path.join(ROOT, "include", "fhvae_qbe.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_qbe_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_qbe.h")
+    found = ext_abi.declared("fhvae_qbe.h", "fhvae_qbe_")
     assert found == qbe.QBE_SIGNATURES and sorted(found) == ["fhvae_qbe_sdtw"]
     assert not set(found) & set(hb.SIGNATURES) and not set(found) & set(abx.ABX_SIGNATURES)
     for name, value in (("MAX_DIM", qbe.QBE_MAX_DIM), ("MAX_QLEN", qbe.QBE_MAX_QLEN)):

@@ -1,7 +1,6 @@
 """Units without a GPU: KM_SIGNATURES against include/fhvae_kmeans.h, the entry points' export and their argument errors (they
 return before any launch), the workspace size, the oracle (tests/kmeans_ref.py) on cases worked by hand, units.unit_quality /
 bitrate / frame_phones / write_units, and the command lines' argument errors."""
-import ctypes
 import math
 import os
 import re
@@ -10,6 +9,8 @@ import numpy as np
 import pytest
 
 import kmeans_ref as R
+import ext_abi
+from ext_abi import aligned as _aligned, swap as _swap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
@@ -30,13 +31,8 @@ def test_signatures_match_the_header():
     import hip_binding as hb
     import units
 
-    text = open(os.path.join(ROOT, "include", "fhvae_kmeans.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_km_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = [ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in args.split(",")]
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_kmeans.h")
+    found = ext_abi.declared("fhvae_kmeans.h", "fhvae_km_")
     assert found == units.KM_SIGNATURES and sorted(found) == ["fhvae_km_assign", "fhvae_km_update", "fhvae_km_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
     for name, value in (("PIECE", units.KM_PIECE), ("MAX_ROWS", units.KM_MAX_ROWS), ("MAX_CENT", units.KM_MAX_CENT)):
@@ -55,16 +51,6 @@ def test_symbols_exported_and_the_main_header_untouched(lib):
     assert lib.fhvae_abi_version() == 12 and len(hb.SIGNATURES) == 81  # include/fhvae_hip.h is untouched
     header = open(os.path.join(ROOT, "include", "fhvae_hip.h")).read()
     assert "fhvae_km_" not in header and "kmeans" not in header.lower()
-
-
-def _aligned():
-    """(keep-alive, a 16-byte aligned host address): the calls below return before anything would read it"""
-    buf = np.zeros(4096 + 16, dtype=np.uint8)
-    return buf, (buf.ctypes.data + 15) & ~15
-
-
-def _swap(good, i, v):
-    return [v if j == i else a for j, a in enumerate(good)]
 
 
 def test_assign_errors_before_any_launch(lib):

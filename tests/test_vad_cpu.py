@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import vad_ref as R
+import ext_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,16 +82,8 @@ def test_signatures_match_the_header():
     import hip_binding as hb
     import vad as V
 
-    text = open(os.path.join(ROOT, "include", "fhvae_vad.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    kinds = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float}
-    found = {}
-    for res, name, args in re.findall(r"\b(int|int64_t)\s+(fhvae_vad_\w+)\s*\(([^)]*)\)\s*;", text):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            types.append(ctypes.c_void_p if "*" in a else kinds[a.replace("const ", "").split()[0]])
-        found[name] = (kinds[res], types)
+    text = ext_abi.header_text("fhvae_vad.h")
+    found = ext_abi.declared("fhvae_vad.h", "fhvae_vad_")
     assert found == V.VAD_SIGNATURES
     assert sorted(found) == ["fhvae_vad_decide", "fhvae_vad_energy", "fhvae_vad_select", "fhvae_vad_ws_bytes"]
     assert not set(found) & set(hb.SIGNATURES)
@@ -112,8 +105,7 @@ def test_symbols_exported_and_errors_before_any_launch(lib):
     p = ctypes.cast(buf, ctypes.c_void_p)
     NULL, SHAPE, ALIGN, LIMIT = -1, -2, -4, -5
 
-    def swap(good, i, v):
-        return [v if j == i else a for j, a in enumerate(good)]
+    swap = ext_abi.swap
 
     en = lib.fhvae_vad_energy
     #       wave n  wptr fptr U  nfr L    hop  mode flags energy status stream

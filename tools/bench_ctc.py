@@ -23,8 +23,9 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd"), os.path.join(ROOT, "tests")]
+from bench_common import ROOT  # (importing it sets the package's import path)
+
+sys.path.insert(2, os.path.join(ROOT, "tests"))
 
 PEAK_F64 = 78.6e12
 OPS_PER_CELL = 9 * 30 + 20
@@ -43,7 +44,7 @@ def timed(fn, sync):
     return out, (time.perf_counter() - t) * 1e3
 
 
-def alternate(fns, sync, reps):
+def host_rounds(fns, sync, reps):
     """fns: name -> callable (or None).  -> (name -> times in ms, name -> last output); a side that raises is dropped and named."""
     times, outs, errors = {k: [] for k in fns}, {}, {}
     for k, fn in list(fns.items()):  # the warm-up
@@ -94,7 +95,7 @@ def loss_cases(reps, out):
                    "hip_grad": lambda: ctc.loss(z, ptr, flat, lab_ptr, C - 1),
                    "torch_f32": lambda: torch_ctc(z, padded, U, T, L_of, torch.float32),
                    "torch_f64": lambda: torch_ctc(z, padded, U, T, L_of, torch.float64)}
-            times, outs, errors = alternate(fns, torch.cuda.synchronize, reps)
+            times, outs, errors = host_rounds(fns, torch.cuda.synchronize, reps)
             cells = int(T * (2 * lens + 1).sum())
             line = {"case": "ctc_" + name, "C": C, "utterances": U, "frames": U * T, "labels": int(lens.sum()), "cells": cells,
                     "ws_groups": len(ctc.groups(ctc.cells(ptr.cpu().numpy(), lab_ptr.cpu().numpy()), 1 << 30))}
@@ -127,7 +128,7 @@ def fit_case(reps, out):
     dev = torch.device("cuda:0")
     x = torch.from_numpy(c["x"]).to(dev)
     ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(c["lengths"])]).astype(np.int64)).to(dev)
-    times, outs, _ = alternate({"fit": lambda: ctc.fit(x, ptr, c["refs"], 20, iters=100)}, torch.cuda.synchronize, min(reps, 3))
+    times, outs, _ = host_rounds({"fit": lambda: ctc.fit(x, ptr, c["refs"], 20, iters=100)}, torch.cuda.synchronize, min(reps, 3))
     model, hist = outs["fit"]
     out({"case": "ctc_fit", "utterances": 2000, "frames": int(x.shape[0]), "phones": 20, "width": 16, "fit_ms": stats(times["fit"]),
          "iterations": int(hist["iterations"]), "evaluations": int(hist["evaluations"]), "converged": bool(hist["converged"]),

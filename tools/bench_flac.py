@@ -22,9 +22,9 @@ import wave
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "pytorch-scalablefhvae_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import bench_common  # (importing it sets the package's import path)
+
+sys.path.insert(0, os.path.join(bench_common.ROOT, "tests"))
 
 SR, UTT, BLOCK = 16000, 160000, 4096
 
@@ -52,8 +52,8 @@ def encode(x):
                            subs=lambda fi, ch: R.Sub("lpc", coefs=coefs, precision=12, shift=10, part_order=4 if fi < n_full else 0))
 
 
-def spread(ts):
-    return {"median": round(float(np.median(ts)), 4), "min": round(float(np.min(ts)), 4), "max": round(float(np.max(ts)), 4)}
+def spread4(ts):
+    return {k: round(v, 4) for k, v in bench_common.spread(ts).items()}
 
 
 def timed(fn):
@@ -129,7 +129,7 @@ def bench_kernels(minutes, blobs, pcm, reps):
     med = {k: float(np.median(v)) for k, v in ts.items()}
     return {"bench": "flac_kernels", "audio_min": minutes, "utterances": U, "flac_bytes": int(buf.numel()), "pcm16_bytes": 2 * U * UTT,
             "candidates": int(nc), "frames": int(chain.numel()), "reps": reps, "decoded_equals_pcm": exact,
-            "ms": {k: spread(v) for k, v in ts.items()},
+            "ms": {k: spread4(v) for k, v in ts.items()},
             "flac_total_over_feats_fwd": round((med["scan"] + med["parse"] + med["decode"]) / med["feats_fwd"], 2)}
 
 
@@ -167,8 +167,8 @@ def bench_cli(minutes, blobs, pcm, reps, root):
                 split[kind] = {k: round(v, 3) for k, v in t.items()}
     a = np.load(os.path.join(root, "flac_np", "train", "u00000.npy"))
     b = np.load(os.path.join(root, "wav_np", "train", "u00000.npy"))
-    return {"bench": "prepare_numpy_data_flac_vs_wav", "audio_min": minutes, "files": U, "reps": reps, "s_flac": spread(wall["flac"]),
-            "s_wav": spread(wall["wav"]), "flac_over_wav": round(float(np.median(wall["flac"]) / np.median(wall["wav"])), 3),
+    return {"bench": "prepare_numpy_data_flac_vs_wav", "audio_min": minutes, "files": U, "reps": reps, "s_flac": spread4(wall["flac"]),
+            "s_wav": spread4(wall["wav"]), "flac_over_wav": round(float(np.median(wall["flac"]) / np.median(wall["wav"])), 3),
             "last_split_flac": split["flac"], "last_split_wav": split["wav"], "features_bitwise_equal": bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)))}
 
 

@@ -15,15 +15,11 @@
     python tools/bench_frames.py [--reps 10] [--minutes 1 10 60] [--model-minutes 60] [--out profiles/bench_frames.jsonl]
 """
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import alternate, open_sink, require_gpu, spread  # (importing it sets the package's import path)
 
 PEAK_HBM = 8.0e12
 T, F, UTT = 20, 80, 998
@@ -33,30 +29,6 @@ def corpus(minutes, seed=0):
     rng = np.random.default_rng(seed)
     level = rng.uniform(-10, 6, size=(1, F))
     return [np.clip(level + rng.standard_normal((UTT, F)) * 2.0, -16, 12).astype(np.float32) for _ in range(max(1, minutes * 6))]
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
-
-
-def alternate(fns, reps, warmup=2):
-    """{name: [ms]}: the functions in turn, `reps` rounds, device events around every call."""
-    import torch
-
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts[name].append(e0.elapsed_time(e1))
-    return ts
 
 
 def torch_gather(pool, lo, hi):
@@ -105,7 +77,7 @@ def bench_kernels(minutes, shift, reps, emit):
     def t_gather():
         keep["t"] = torch_gather(pool, 0, W)
 
-    ts = alternate({"kernel": k_gather, "torch": t_gather}, reps)
+    ts = alternate({"kernel": k_gather, "torch": t_gather}, reps, warmup=2)
     same = bool(torch.equal(keep["k"].view(torch.int32), keep["t"].view(torch.int32)))
     need = 4.0 * F * (N + W * T)
     mk = float(np.median(ts["kernel"]))
@@ -124,7 +96,7 @@ def bench_kernels(minutes, shift, reps, emit):
     def t_overlap():
         keep["t"] = torch_overlap(pool, seg)
 
-    ts = alternate({"kernel": k_overlap, "torch": t_overlap}, reps)
+    ts = alternate({"kernel": k_overlap, "torch": t_overlap}, reps, warmup=2)
     same = bool(torch.equal(keep["k"].view(torch.int32), keep["t"].view(torch.int32)))
     close = bool(torch.allclose(keep["k"], keep["t"], rtol=1e-6, atol=1e-6))
     need = 4.0 * F * (N + W * T)
@@ -190,16 +162,8 @@ def main():
     args = ap.parse_args()
     import torch
 
-    if not torch.cuda.is_available():
-        sys.exit("bench_frames.py measures on a MI355X: no GPU, no number")
-    sink = open(args.out, "a") if args.out else None
-
-    def emit(res):
-        line = json.dumps(res)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
+    require_gpu("bench_frames.py")
+    emit = open_sink(args.out)
 
     for minutes in args.minutes:
         for shift in args.shifts:

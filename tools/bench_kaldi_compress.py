@@ -17,14 +17,12 @@ import argparse
 import json
 import os
 import shutil
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "pytorch-scalablefhvae_amd"))
+from bench_common import spread  # (importing it sets the package's import path)
 
 PEAK_HBM = 8.0e12
 F, UTT = 80, 998
@@ -37,10 +35,6 @@ def corpus(minutes, seed=0, one_utterance=False):
     level = rng.uniform(-10, 6, size=(1, F))
     mats = [np.clip(level + rng.standard_normal((UTT, F)) * 2.0, -16, 12).astype(np.float32) for _ in range(U)]
     return [np.concatenate(mats)] if one_utterance else mats
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
 
 
 def bench(minutes, reps, pool_reps, one_utterance=False):

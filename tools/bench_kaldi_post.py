@@ -15,46 +15,19 @@ line per measurement.
     python tools/bench_kaldi_post.py [--reps 10] [--minutes 1 10 60] [--cli-minutes 60] [--cli-reps 3] [--out profiles/bench_kaldi_post.jsonl]
 """
 import argparse
-import json
 import os
 import shutil
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import alternate, open_sink, require_gpu, spread  # (importing it sets the package's import path)
 
 PEAK_HBM = 8.0e12
 SR, FPS = 16000, 100
 UTT_FRAMES = 10 * FPS
 CMN_WINDOW = 300
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
-
-
-def alternate(fns, reps, warmup=2):
-    """{name: [ms]}: the functions in turn, `reps` rounds, device events around every call."""
-    import torch
-
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts[name].append(e0.elapsed_time(e1))
-    return ts
 
 
 def torch_deltas(x3, kernels, order, window):
@@ -110,7 +83,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
         def t_cep():
             keep["t"] = (m @ dct_t) * lf
 
-        ts = alternate({"kernel": k_cep, "torch": t_cep}, reps)
+        ts = alternate({"kernel": k_cep, "torch": t_cep}, reps, warmup=2)
         report(emit, base, "kaldi_cepstra", ts, 4.0 * n * (B + C), float((keep["k"] - keep["t"]).abs().max()), B=B, C=C)
         del m
         keep.clear()
@@ -125,7 +98,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
         def t_del():
             keep["t"] = torch_deltas(x.view(U, T, D), kernels, 2, 2)
 
-        ts = alternate({"kernel": k_del, "torch": t_del}, reps)
+        ts = alternate({"kernel": k_del, "torch": t_del}, reps, warmup=2)
         report(emit, base, "kaldi_add_deltas", ts, 4.0 * n * D * 4, float((keep["k"] - keep["t"].reshape(n, 3 * D)).abs().max()), D=D,
                order=2, window=2)
         del x
@@ -142,7 +115,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
     def t_cmvn():
         keep["t"] = torch_cmvn(x.view(U, T, D), b, e)
 
-    ts = alternate({"kernel": k_cmvn, "torch": t_cmvn}, reps)
+    ts = alternate({"kernel": k_cmvn, "torch": t_cmvn}, reps, warmup=2)
     report(emit, base, "kaldi_cmvn_sliding", ts, 4.0 * n * D * 2, float((keep["k"] - keep["t"].reshape(n, D)).abs().max()), D=D,
            cmn_window=CMN_WINDOW, center=True, norm_vars=False)
     assert int(status.item()) == 0
@@ -196,16 +169,8 @@ def main():
     args = ap.parse_args()
     import torch
 
-    if not torch.cuda.is_available():
-        sys.exit("bench_kaldi_post.py measures on a MI355X: no GPU, no number")
-    sink = open(args.out, "a") if args.out else None
-
-    def emit(res):
-        line = json.dumps(res)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
+    require_gpu("bench_kaldi_post.py")
+    emit = open_sink(args.out)
 
     for minutes in args.minutes:
         bench_kernels(minutes, False, args.reps, emit)

@@ -14,42 +14,14 @@
         [--out profiles/bench_kmeans.jsonl]
 """
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import alternate, open_sink, require_gpu, spread  # (importing it sets the package's import path)
 
 PEAK_F32_MFMA = 157e12
 SCORE_CHUNK_BYTES = 1 << 30
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
-
-
-def alternate(fns, reps, warmup=1):
-    """{name: [ms]}: the functions in turn, `reps` rounds, device events around every call."""
-    import torch
-
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts[name].append(e0.elapsed_time(e1))
-    return ts
 
 
 def torch_assign(x, c):
@@ -156,16 +128,8 @@ def main():
     args = ap.parse_args()
     import torch
 
-    if not torch.cuda.is_available():
-        sys.exit("bench_kmeans.py measures on a MI355X: no GPU, no number")
-    sink = open(args.out, "a") if args.out else None
-
-    def emit(res):
-        line = json.dumps(res)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
+    require_gpu("bench_kmeans.py")
+    emit = open_sink(args.out)
 
     for D in args.dims:
         for N in args.rows:

@@ -16,44 +16,14 @@
         [--out profiles/bench_qbe.jsonl]
 """
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import alternate, open_sink, require_gpu, spread  # (importing it sets the package's import path)
 
 UTTS, UTT_LEN, QMIN, QMAX, QPOOL = 360, 1000, 20, 60, 1 << 16
 F64_PEAK_FMA = 39.3e12  # the float64 vector peak, multiply-adds per second
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
-
-
-def alternate(fns, reps, warmup=1):
-    """{name: [ms]}: the functions in turn, reps[name] rounds each, device events around every call."""
-    import torch
-
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in fns}
-    for r in range(max(reps.values())):
-        for name, fn in fns.items():
-            if r >= reps[name]:
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts[name].append(e0.elapsed_time(e1))
-    return ts
 
 
 def torch_sdtw(qfeats, q_start, q_len, feats, U, m):
@@ -204,16 +174,8 @@ def main():
     args = ap.parse_args()
     import torch
 
-    if not torch.cuda.is_available():
-        sys.exit("bench_qbe.py measures on a MI355X: no GPU, no number")
-    sink = open(args.out, "a") if args.out else None
-
-    def emit(res):
-        line = json.dumps(res)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
+    require_gpu("bench_qbe.py")
+    emit = open_sink(args.out)
 
     for D in args.dims:
         for Q in args.queries:

@@ -14,17 +14,14 @@
     python tools/bench_vad.py [--reps 10] [--minutes 1 10 60] [--cli-minutes 60] [--cli-reps 3] [--out profiles/bench_vad.jsonl]
 """
 import argparse
-import json
 import os
 import shutil
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import alternate, open_sink, require_gpu, spread  # (importing it sets the package's import path)
 
 PEAK_HBM = 8.0e12
 SR, L, HOP, F = 16000, 400, 160, 80
@@ -37,30 +34,6 @@ def signal(n, seed):
     rng = np.random.default_rng(seed)
     amp = np.where((np.arange(n) // (SR // 10)) % 2 == 0, np.float32(0.3), np.float32(0.003))
     return rng.standard_normal(n, dtype=np.float32) * amp
-
-
-def spread(ts):
-    return {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}
-
-
-def alternate(fns, reps, warmup=2):
-    """{name: [ms]}: the functions in turn, `reps` rounds, device events around every call."""
-    import torch
-
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ts = {k: [] for k in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ts[name].append(e0.elapsed_time(e1))
-    return ts
 
 
 def torch_energy(wave2d):
@@ -115,7 +88,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
     def k_feats():
         hb.feats_fwd(wave, ptrs[0], ptrs[1], bases.dft, bases.mel, L, HOP, F, "fbank", feats, status)
 
-    ts = alternate({"kernel": k_energy, "torch": t_energy, "feats_fwd": k_feats}, reps)
+    ts = alternate({"kernel": k_energy, "torch": t_energy, "feats_fwd": k_feats}, reps, warmup=2)
     rel = float(((keep["ke"].double() - keep["te"].double()).abs() / keep["te"].double().abs().clamp_min(1e-30)).max())
     need = 4.0 * (n + N)
     mk = float(np.median(ts["kernel"]))
@@ -133,7 +106,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
     def t_decide():
         keep["td"] = torch_decide(energy, lengths_d)
 
-    ts = alternate({"kernel": k_decide, "torch": t_decide}, reps)
+    ts = alternate({"kernel": k_decide, "torch": t_decide}, reps, warmup=2)
     same = bool(torch.equal(keep["kd"][0].bool(), keep["td"][0]) and torch.equal(keep["kd"][1], keep["td"][1]))
     mk = float(np.median(ts["kernel"]))
     vad, rank = keep["kd"]
@@ -149,7 +122,7 @@ def bench_kernels(minutes, one_utterance, reps, emit):
     def t_select():
         keep["ts"] = feats[mask]
 
-    ts = alternate({"kernel": k_select, "torch": t_select}, reps)
+    ts = alternate({"kernel": k_select, "torch": t_select}, reps, warmup=2)
     same = bool(torch.equal(keep["ks"].view(torch.int32), keep["ts"].view(torch.int32)))
     need = 4.0 * F * 2 * n_out
     mk = float(np.median(ts["kernel"]))
@@ -201,16 +174,8 @@ def main():
     args = ap.parse_args()
     import torch
 
-    if not torch.cuda.is_available():
-        sys.exit("bench_vad.py measures on a MI355X: no GPU, no number")
-    sink = open(args.out, "a") if args.out else None
-
-    def emit(res):
-        line = json.dumps(res)
-        print(line, flush=True)
-        if sink:
-            sink.write(line + "\n")
-            sink.flush()
+    require_gpu("bench_vad.py")
+    emit = open_sink(args.out)
 
     for minutes in args.minutes:
         bench_kernels(minutes, False, args.reps, emit)

@@ -22,8 +22,7 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "pytorch-scalablefhvae_amd")]
+from bench_common import ROOT  # (importing it sets the package's import path)
 
 FRAMES_PER_UTT = 1000  # 10 s of 10 ms frames
 
@@ -32,7 +31,7 @@ def stats(ms):
     return {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms)), "runs": len(ms)}
 
 
-def alternate(ours, base, sync, reps):
+def host_pair(ours, base, sync, reps):
     """-> (our times, baseline times, our output, the baseline's output), milliseconds."""
     def timed(fn):
         sync()
@@ -87,7 +86,7 @@ def viterbi_cases(reps, out):
             init = torch.log_softmax(torch.randn(C, generator=g, device=dev), dim=0)
             ptr = (torch.arange(U + 1, dtype=torch.int64) * T).to(dev)
             flat = emit.reshape(U * T, C)
-            ta, tb, a, b = alternate(lambda: phonerec.viterbi(flat, ptr, trans, init), lambda: torch_viterbi(emit, trans, init),
+            ta, tb, a, b = host_pair(lambda: phonerec.viterbi(flat, ptr, trans, init), lambda: torch_viterbi(emit, trans, init),
                                      torch.cuda.synchronize, reps)
             same = bool((a[0].reshape(U, T) == b[0]).all()) and bool((a[1].view(torch.int32) == b[1].view(torch.int32)).all())
             line = {"case": "viterbi_" + name, "C": C, "utterances": U, "frames": U * T, "hip_ms": stats(ta), "torch_ms": stats(tb),
@@ -130,7 +129,7 @@ def edit_cases(reps, out):
     for U in (360, 3600, 36000):
         refs, hyps = edit_pairs(U, U)
         (r, rp), (h, hp) = phonerec.csr(refs, "cuda:0"), phonerec.csr(hyps, "cuda:0")
-        ta, tb, a, b = alternate(lambda: phonerec.align(r, rp, h, hp), lambda: np.array([numpy_levenshtein(x, y) for x, y in zip(refs, hyps)]),
+        ta, tb, a, b = host_pair(lambda: phonerec.align(r, rp, h, hp), lambda: np.array([numpy_levenshtein(x, y) for x, y in zip(refs, hyps)]),
                                  torch.cuda.synchronize, reps)
         counts = a.cpu().numpy().astype(np.int64)
         out({"case": "align", "pairs": U, "ref_tokens": int(sum(len(x) for x in refs)), "hip_ms": stats(ta), "numpy_ms": stats(tb),
