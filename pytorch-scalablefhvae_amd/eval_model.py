@@ -74,7 +74,10 @@ per_argmax, frame_accuracy, frame_accuracy_argmax, classes, ...}, "feats": {...}
 "frame_offset", "phone_penalty"}; --per-phone-map folds both sides, --per-phone-penalty is the insertion penalty.  Without
 --per-item every output is what it was.  With --per-ctc every entry of --per-on gains "ctc": {per, sub, del, ins, cor, objective,
 iterations, converged, context, dropped_infeasible, ...}: the same linear model trained by CTC (ctc.py) on the transcriptions of
-the training utterances alone, decoded greedily; --per-ctc-context K splices K frames per side.
+the training utterances alone, decoded greedily; --per-ctc-context K splices K frames per side.  With --per-ctc-beam W
+[--per-ctc-lm-scale S --per-ctc-bonus B | --per-ctc-lm-tune] [--per-ctc-class-beam G] [--per-ctc-lm-smooth A] every entry also gains
+"ctc_beam" beside "ctc": the same model decoded by prefix beam search with a phone bigram (ctcbeam.py): the error rate's keys, beam,
+lm_scale, bonus, class_beam, smooth and the tuning grid.
 
 Real features (--feat-scp / --len-scp) are written un-normalised (NumpyDataset.undo_mvn); without them the data is the synthetic
 split of train_model.py (its dev split for the same --seed).
@@ -165,6 +168,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--per-phone-penalty", type=float, default=0.0, help="subtracted from every transition between different phones")
     p.add_argument("--per-ctc", action="store_true", help="with --per-item: also train by CTC on the transcriptions alone, decode greedily")
     p.add_argument("--per-ctc-context", type=int, default=0, metavar="K", help="frames spliced per side for --per-ctc")
+    p.add_argument("--per-ctc-beam", type=int, default=None, metavar="W", help="with --per-ctc: also decode by prefix beam search of this width with a phone bigram")
+    p.add_argument("--per-ctc-lm-scale", type=float, default=None, metavar="S", help="the bigram's weight (default 1)")
+    p.add_argument("--per-ctc-bonus", type=float, default=None, metavar="B", help="added per phone put out (default 0)")
+    p.add_argument("--per-ctc-lm-tune", action="store_true", help="choose the weight and the bonus on the training utterances instead")
+    p.add_argument("--per-ctc-class-beam", type=float, default=float("inf"), metavar="G", help="classes further than this below the frame's best are not extended into")
+    p.add_argument("--per-ctc-lm-smooth", type=float, default=1.0, metavar="A", help="added to every bigram count")
     return p
 
 
@@ -217,6 +226,19 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--per-ctc needs --per-item")
     if args.per_ctc_context < 0 or (args.per_ctc_context != 0 and not args.per_ctc):
         p.error("--per-ctc-context must not be negative and needs --per-ctc")
+    beam_flags = (args.per_ctc_lm_scale is not None or args.per_ctc_bonus is not None or args.per_ctc_lm_tune
+                  or args.per_ctc_class_beam != float("inf") or args.per_ctc_lm_smooth != 1.0)
+    if args.per_ctc_beam is None and beam_flags:
+        p.error("--per-ctc-lm-scale, --per-ctc-bonus, --per-ctc-lm-tune, --per-ctc-class-beam and --per-ctc-lm-smooth need --per-ctc-beam")
+    if args.per_ctc_beam is not None and (not args.per_ctc or not 1 <= args.per_ctc_beam <= 64):
+        p.error("--per-ctc-beam needs --per-ctc and a width from 1 to 64")
+    if args.per_ctc_lm_tune and (args.per_ctc_lm_scale is not None or args.per_ctc_bonus is not None):
+        p.error("--per-ctc-lm-tune excludes --per-ctc-lm-scale and --per-ctc-bonus")
+    if ((args.per_ctc_lm_scale is not None and not 0 <= args.per_ctc_lm_scale < float("inf"))
+            or (args.per_ctc_bonus is not None and not np.isfinite(args.per_ctc_bonus))):
+        p.error("--per-ctc-lm-scale must be finite and not negative, --per-ctc-bonus finite")
+    if not args.per_ctc_class_beam >= 0 or not args.per_ctc_lm_smooth >= 0:
+        p.error("--per-ctc-class-beam and --per-ctc-lm-smooth must not be negative")
     if not np.isfinite(args.per_phone_penalty):
         p.error("--per-phone-penalty must be finite")
     if args.baseline_name is not None and args.baseline_feat_scp is None:
@@ -450,8 +472,18 @@ def per_phones(args, model, T, dev):
             import ctc
 
             train_refs = [refs[u] for u in probe.split_utterances(len(pool.lengths), args.probe_holdout, args.probe_seed)[0]]
-            block[on]["ctc"] = ctc.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, l2=args.probe_l2,
-                                             iters=args.probe_iters, context=args.per_ctc_context, phone_table=table)[1]
+            ctc_out = ctc.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, l2=args.probe_l2,
+                                    iters=args.probe_iters, context=args.per_ctc_context, phone_table=table)
+            block[on]["ctc"] = ctc_out[1]
+            if args.per_ctc_beam is not None:
+                import ctcbeam
+
+                tuned = args.per_ctc_lm_tune
+                block[on]["ctc_beam"] = ctcbeam.recognise(
+                    train[0], train[2], train_refs, test[0], test[2], test[3], names, beam=args.per_ctc_beam,
+                    scale=None if tuned else (1.0 if args.per_ctc_lm_scale is None else args.per_ctc_lm_scale),
+                    bonus=None if tuned else (0.0 if args.per_ctc_bonus is None else args.per_ctc_bonus),
+                    class_beam=args.per_ctc_class_beam, smooth=args.per_ctc_lm_smooth, phone_table=table, model=ctc_out[0])[1]
         del rows
     block.update({"holdout": args.probe_holdout, "seed": args.probe_seed, "frame_shift": args.abx_frame_shift,
                   "frame_offset": args.abx_frame_offset, "phone_penalty": args.per_phone_penalty})

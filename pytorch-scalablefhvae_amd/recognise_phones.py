@@ -7,7 +7,8 @@ sequence, which is scored against the transcription by the phone error rate (pho
         [--data-format numpy|kaldi] [--mvn-path P] [--on z1|feats] [--probe FILE.npz] [--phone-map FILE]
         [--acoustic-scale 1] [--prior-scale 1] [--phone-penalty 0] [--smooth 1]
         [--l2 1e-4] [--iters 200] [--gtol 1e-5] [--frame-shift 0.010] [--frame-offset 0.0] [--batch-size B]
-        [--compute-dtype f32|bf16] [--ctc [--ctc-context K] [--ctc-init zero|probe]]
+        [--compute-dtype f32|bf16] [--ctc [--ctc-context K] [--ctc-init zero|probe]
+        [--ctc-beam W [--ctc-lm-scale S --ctc-bonus B | --ctc-lm-tune] [--ctc-class-beam G] [--ctc-lm-smooth A]]]
 
   --checkpoint CK  optional.  Without it only --on feats is allowed: the archive's rows as read (the MFCC baseline)
   --item ITEM      the alignment (abx.read_items): it labels the training frames and, in onset order, is the transcription.  An
@@ -26,6 +27,8 @@ sequence, which is scored against the transcription by the phone error rate (pho
 It writes under --out: probe.npz, hyp.txt and ref.txt (`key p1 p2 ...`, folded) and phonerec.json: on, per, sub, del, ins, cor,
 ref_tokens, utterances, per_argmax (the collapsed per-frame arg-max instead of the Viterbi path), frame_accuracy,
 frame_accuracy_argmax, classes, folded_classes, train_frames, test_frames, iterations, converged and the settings.
+With --ctc --ctc-beam W also hyp_ctc_beam.txt, ctc_lm.npy (the bigram of the training transcriptions, ctcbeam.bigram) and a
+"ctc_beam" block: the error rate's keys, beam, lm_scale, bonus, class_beam, smooth and the tuning grid (null unless --ctc-lm-tune).
 With --ctc also ctc.npz and hyp_ctc.txt, and a "ctc" block in phonerec.json: per, sub, del, ins, cor, objective, iterations,
 converged, context, dropped_infeasible (and ref_tokens, utterances, l2, init).
 """
@@ -70,6 +73,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ctc", action="store_true", help="also train by CTC on the transcriptions alone and decode greedily")
     p.add_argument("--ctc-context", type=int, default=0, metavar="K", help="frames spliced per side")
     p.add_argument("--ctc-init", default="zero", choices=["zero", "probe"], help="start from zero or from the frame probe's rows")
+    p.add_argument("--ctc-beam", type=int, default=None, metavar="W", help="with --ctc: also decode by prefix beam search of this width with a phone bigram (ctcbeam.py)")
+    p.add_argument("--ctc-lm-scale", type=float, default=None, metavar="S", help="the bigram's weight (default 1)")
+    p.add_argument("--ctc-bonus", type=float, default=None, metavar="B", help="added per phone put out (default 0)")
+    p.add_argument("--ctc-lm-tune", action="store_true", help="choose the weight and the bonus on the training utterances instead")
+    p.add_argument("--ctc-class-beam", type=float, default=float("inf"), metavar="G", help="classes further than this below the frame's best are not extended into")
+    p.add_argument("--ctc-lm-smooth", type=float, default=1.0, metavar="A", help="added to every bigram count")
     return p
 
 
@@ -104,6 +113,17 @@ def parse_args(argv=None):
         p.error("--ctc-context and --ctc-init need --ctc")
     if args.ctc_context < 0 or (args.ctc_init == "probe" and args.ctc_context != 0):
         p.error("--ctc-context must not be negative, and --ctc-init probe needs --ctc-context 0")
+    beam_flags = args.ctc_lm_scale is not None or args.ctc_bonus is not None or args.ctc_lm_tune or args.ctc_class_beam != float("inf") or args.ctc_lm_smooth != 1.0
+    if args.ctc_beam is None and beam_flags:
+        p.error("--ctc-lm-scale, --ctc-bonus, --ctc-lm-tune, --ctc-class-beam and --ctc-lm-smooth need --ctc-beam")
+    if args.ctc_beam is not None and (not args.ctc or not 1 <= args.ctc_beam <= 64):
+        p.error("--ctc-beam needs --ctc and a width from 1 to 64")
+    if args.ctc_lm_tune and (args.ctc_lm_scale is not None or args.ctc_bonus is not None):
+        p.error("--ctc-lm-tune excludes --ctc-lm-scale and --ctc-bonus")
+    if (args.ctc_lm_scale is not None and not 0 <= args.ctc_lm_scale < float("inf")) or (args.ctc_bonus is not None and not np.isfinite(args.ctc_bonus)):
+        p.error("--ctc-lm-scale must be finite and not negative, --ctc-bonus finite")
+    if not args.ctc_class_beam >= 0 or not args.ctc_lm_smooth >= 0:
+        p.error("--ctc-class-beam and --ctc-lm-smooth must not be negative")
     return p, args
 
 
@@ -207,6 +227,15 @@ def main(argv=None) -> int:
             ctc_out = ctc.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, l2=args.l2, iters=args.iters,
                                     gtol=args.gtol, context=args.ctc_context, init=fitted if args.ctc_init == "probe" else None,
                                     phone_table=table)
+            beam_out = None
+            if args.ctc and args.ctc_beam is not None:
+                import ctcbeam
+
+                tuned = args.ctc_lm_tune
+                beam_out = ctcbeam.recognise(train[0], train[2], train_refs, test[0], test[2], test[3], names, beam=args.ctc_beam,
+                                             scale=None if tuned else (1.0 if args.ctc_lm_scale is None else args.ctc_lm_scale),
+                                             bonus=None if tuned else (0.0 if args.ctc_bonus is None else args.ctc_bonus),
+                                             class_beam=args.ctc_class_beam, smooth=args.ctc_lm_smooth, phone_table=table, model=ctc_out[0])
     except (ValueError, OSError, RuntimeError) as e:
         print("recognise_phones: %s" % e, file=sys.stderr)
         return 1
@@ -225,6 +254,10 @@ def main(argv=None) -> int:
         info["ctc"] = dict(ctc_out[1], init=args.ctc_init)
         ctc.save(os.path.join(args.out, "ctc.npz"), ctc_out[0])
         write_tokens(os.path.join(args.out, "hyp_ctc.txt"), test[4], ctc_out[2], folded)
+        if beam_out is not None:
+            info["ctc_beam"] = beam_out[1]
+            write_tokens(os.path.join(args.out, "hyp_ctc_beam.txt"), test[4], beam_out[2], folded)
+            np.save(os.path.join(args.out, "ctc_lm.npy"), beam_out[4])
     with open(os.path.join(args.out, "phonerec.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps(info))
