@@ -5,7 +5,7 @@
 // NS contiguous states l NS .. l NS + NS - 1 (NS = 1, 2, 4 or 9 by S: one kernel each), alpha
 // (forward) or beta (backward) in float64 registers.  The two left (right) neighbours of a lane's first (last) states arrive by
 // cross-lane moves.  Per frame the wave computes the row's log-softmax once (lane c owns the classes c and c + 64, butterfly
-// maximum and butterfly float64 sum: every lane ends with the same bits), parks it in LDS and every state gathers lp[l'_s] from
+// maximum and butterfly float64 sum: every lane ends with the same bits; trellis.h), parks it in LDS and every state gathers lp[l'_s] from
 // there; the logits are loaded a frame ahead.  The forward sweep stores the alpha rows to the workspace; the backward sweep
 // reads them back a frame ahead (a lane reads the cells it wrote itself), keeps beta in registers, recomputes the row's
 // log-softmax and writes each gradient row once.
@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "trellis.h"
 
 #include "../../include/fhvae_ctc.h"
 
@@ -28,62 +29,15 @@ constexpr int kCtcCP = FHVAE_CTC_MAX_CLASSES;
 constexpr int kCtcPostL = 264;  // where the labels' half of CtcLds::post begins (the blanks' half holds at most 257)
 constexpr int kCtcLP = kCtcCP + 2;  // a half of the log-softmax buffer
 
-static_assert(FHVAE_CTC_MAX_CLASSES == 128, "a lane owns two classes");
+static_assert(FHVAE_CTC_MAX_CLASSES == kTrMaxClasses && FHVAE_CTC_MAX_LABELS == kTrMaxLabels, "the lane layout of trellis.h");
 static_assert(kCtcMaxS <= 64 * 9, "a lane owns at most nine states");
 static_assert(kCtcPostL >= FHVAE_CTC_MAX_LABELS + 1 && kCtcPostL + FHVAE_CTC_MAX_LABELS <= kCtcMaxS + 7, "the two halves of post");
 
-__device__ __forceinline__ bool ctc_utt_ok(int64_t a, int64_t b, int64_t n_frames) {
-  return a >= 0 && b >= a && b <= n_frames && b - a <= 0x7fffffffLL;
-}
-
-// the cells utterance (T, L) needs: T (2 L + 1); an over-long transcription is refused and needs none
-__device__ __forceinline__ int64_t ctc_cells(int64_t T, int64_t L) { return L > FHVAE_CTC_MAX_LABELS ? 0 : T * (2 * L + 1); }
-
-// one thread per utterance: the rules of the header
-__global__ void ctc_check_kernel(const int64_t* __restrict__ utt_ptr, const int64_t* __restrict__ lab_ptr,
-                                 const int64_t* __restrict__ cell_ptr, int64_t U, int64_t n_frames, int64_t ws_cells, int32_t* status) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < U) {
-    const int64_t a = utt_ptr[t], b = utt_ptr[t + 1], la = lab_ptr[t], lb = lab_ptr[t + 1];
-    bool ok = ctc_utt_ok(a, b, n_frames) && la >= 0 && lb >= la;
-    if (t == 0) ok = ok && a == 0 && la == 0;
-    if (t == U - 1) ok = ok && b == n_frames;
-    if (ok && cell_ptr != nullptr) {
-      const int64_t c0 = cell_ptr[t], c1 = cell_ptr[t + 1];
-      ok = c0 >= 0 && c1 >= c0 && c1 <= ws_cells && c1 - c0 >= ctc_cells(b - a, lb - la);
-      if (t == 0) ok = ok && c0 == 0;
-    }
-    if (!ok) atomicOr(status, FHVAE_CTC_BAD_PTR);
-  }
-}
-
-// lse of two or three values, branch-free: with every value -inf the maximum is replaced by 0, the sum is 0 and log gives -inf
-__device__ __forceinline__ double ctc_lse2(double a, double b) {
-  const double m = fmax(a, b), mm = m == -INFINITY ? 0.0 : m;
-  return mm + log(exp(a - mm) + exp(b - mm));
-}
-__device__ __forceinline__ double ctc_lse3(double a, double b, double c) {
-  const double m = fmax(fmax(a, b), c), mm = m == -INFINITY ? 0.0 : m;
-  return mm + log(exp(a - mm) + exp(b - mm) + exp(c - mm));
-}
-
-__device__ __forceinline__ void ctc_load_row(const float* row, int C, int lane, float& z0, float& z1) {
-  z0 = lane < C ? row[lane] : -INFINITY;
-  z1 = lane + 64 < C ? row[lane + 64] : -INFINITY;
-}
-
-// the row's log-softmax into out[0 .. C): every lane computes the same maximum and the same float64 sum
+// the row's log-softmax into out[0 .. C)
 __device__ __forceinline__ void ctc_log_softmax(float z0, float z1, int C, int lane, double* out) {
-  float m = fmaxf(z0, z1);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  const double d0 = (double)z0 - (double)m, d1 = (double)z1 - (double)m;
-  double s = exp(d0) + exp(d1);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-  const double lg = log(s);
-  if (lane < C) out[lane] = d0 - lg;
-  if (lane + 64 < C) out[lane + 64] = d1 - lg;
+  const TrLogSoftmax r = tr_log_softmax(z0, z1);
+  if (lane < C) out[lane] = r.l0;
+  if (lane + 64 < C) out[lane + 64] = r.l1;
 }
 
 struct CtcLds {
@@ -99,25 +53,19 @@ template <int NS>
 __device__ __forceinline__ double ctc_sweeps(CtcLds& sm, const float* __restrict__ z, int64_t ldz, int T, int C, int blank, int L,
                                              double* __restrict__ arow, float* __restrict__ g, int64_t ldg, int lane) {
   const int S = 2 * L + 1;
-  // cls: l'_s; a state past the end reads the -inf entry of lp, so its alpha and beta are -inf with no test in the loops.
-  // pen: 0 where the skip into the state is allowed, else -inf (added to the candidate: exact).  nv: the lane's states that exist
+  // cls, pen: trellis.h; a state past the end reads the -inf entry of lp, so its alpha and beta are -inf with no test in the
+  // loops.  nv: the lane's states that exist
   int cls[NS];
   double pen[NS];
   const int nv = S - lane * NS;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const int s = lane * NS + k, li = (s - 1) >> 1;
-    const bool odd = s < S && (s & 1);
-    cls[k] = s < S ? (odd ? sm.lab[li] : blank) : kCtcCP;
-    pen[k] = (odd && s >= 3 && sm.lab[li] != sm.lab[li - 1]) ? 0.0 : -INFINITY;
-  }
+  tr_state_classes<NS>(sm.lab, lane, S, true, blank, kCtcCP, cls, pen);
   if (lane == 0) sm.lp[kCtcCP] = -INFINITY, sm.lp[kCtcLP + kCtcCP] = -INFINITY;
 #define CTC_VAL(k) ((k) < nv)
   // ---- forward
   double a[NS];
   float z0, z1, n0 = 0.f, n1 = 0.f;
-  ctc_load_row(z, C, lane, z0, z1);
-  if (T > 1) ctc_load_row(z + ldz, C, lane, n0, n1);
+  tr_load_row(z, C, lane, z0, z1);
+  if (T > 1) tr_load_row(z + ldz, C, lane, n0, n1);
   ctc_log_softmax(z0, z1, C, lane, sm.lp);
   __syncthreads();
 #pragma unroll
@@ -128,20 +76,18 @@ __device__ __forceinline__ double ctc_sweeps(CtcLds& sm, const float* __restrict
   }
   for (int t = 1; t < T; ++t) {
     z0 = n0, z1 = n1;
-    if (t + 1 < T) ctc_load_row(z + (int64_t)(t + 1) * ldz, C, lane, n0, n1);  // the next frame's row flies under this frame
+    if (t + 1 < T) tr_load_row(z + (int64_t)(t + 1) * ldz, C, lane, n0, n1);  // the next frame's row flies under this frame
     double* lp = sm.lp + (t & 1) * kCtcLP;
     ctc_log_softmax(z0, z1, C, lane, lp);
     __syncthreads();  // (the frame before read the other half of lp)
-    double up1 = __shfl_up(a[NS - 1], 1, 64);                                       // state lane NS - 1
-    double up2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1, 64) : __shfl_up(a[0], 2, 64);  // state lane NS - 2
-    if (lane < 1) up1 = -INFINITY;
-    if (lane < (NS >= 2 ? 1 : 2)) up2 = -INFINITY;
+    double up1, up2;
+    tr_left<NS>(a, lane, up1, up2);
     double b[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const double p1 = k >= 1 ? a[k >= 1 ? k - 1 : 0] : up1;
       const double p2 = k >= 2 ? a[k >= 2 ? k - 2 : 0] : (k == 1 ? up1 : up2);
-      b[k] = ctc_lse3(a[k], p1, p2 + pen[k]) + lp[cls[k]];
+      b[k] = tr_lse3(a[k], p1, p2 + pen[k]) + lp[cls[k]];
     }
     double* row = arow != nullptr ? arow + (int64_t)t * S : nullptr;
 #pragma unroll
@@ -155,7 +101,7 @@ __device__ __forceinline__ double ctc_sweeps(CtcLds& sm, const float* __restrict
   for (int k = 0; k < NS; ++k)
     if (CTC_VAL(k)) sm.post[lane * NS + k] = a[k];
   __syncthreads();
-  const double ll = ctc_lse2(sm.post[S - 1], S >= 2 ? sm.post[S - 2] : -INFINITY);
+  const double ll = tr_lse2(sm.post[S - 1], S >= 2 ? sm.post[S - 2] : -INFINITY);
   __syncthreads();
   if (g == nullptr || arow == nullptr || ll == -INFINITY) return ll;
 
@@ -169,11 +115,11 @@ __device__ __forceinline__ double ctc_sweeps(CtcLds& sm, const float* __restrict
     beta[k] = (CTC_VAL(k) && s >= S - 2) ? 0.0 : -INFINITY;
     an[k] = 0.0;
   }
-  ctc_load_row(z + (int64_t)(T - 1) * ldz, C, lane, n0, n1);
+  tr_load_row(z + (int64_t)(T - 1) * ldz, C, lane, n0, n1);
   for (int t = T - 1; t >= 0; --t) {
     z0 = n0, z1 = n1;
     if (t > 0) {
-      ctc_load_row(z + (int64_t)(t - 1) * ldz, C, lane, n0, n1);
+      tr_load_row(z + (int64_t)(t - 1) * ldz, C, lane, n0, n1);
       const double* prow = arow + (int64_t)(t - 1) * S;
 #pragma unroll
       for (int k = 0; k < NS; ++k) an[k] = CTC_VAL(k) ? prow[lane * NS + k] : -INFINITY;
@@ -230,18 +176,13 @@ __device__ __forceinline__ double ctc_sweeps(CtcLds& sm, const float* __restrict
     for (int k = 0; k < NS; ++k) {
       const double q1 = k + 1 < NS ? gk[k + 1 < NS ? k + 1 : 0] : dn1;
       const double q2 = k + 2 < NS ? gs[k + 2 < NS ? k + 2 : 0] : (k + 2 == NS ? ds0 : ds1);
-      beta[k] = ctc_lse3(gk[k], q1, q2);
+      beta[k] = tr_lse3(gk[k], q1, q2);
       a[k] = an[k];
     }
     __syncthreads();  // post and this half of lp are free again
   }
   return ll;
 #undef CTC_VAL
-}
-
-// the states a lane owns for a transcription of L labels (a refused one goes with the smallest)
-__device__ __forceinline__ int ctc_states_per_lane(int64_t L) {
-  return (L > FHVAE_CTC_MAX_LABELS || 2 * L + 1 <= 64) ? 1 : (2 * L + 1 <= 128 ? 2 : (2 * L + 1 <= 256 ? 4 : 9));
 }
 
 // NS: the states a lane owns.  The call launches the kernel once per NS and a workgroup whose utterance belongs to another NS
@@ -259,10 +200,10 @@ __global__ void __launch_bounds__(64)
   const int64_t u = blockIdx.x;
   if (u >= U || C < 2 || C > kCtcCP || blank < 0 || blank >= C) return;
   const int64_t u0 = utt_ptr[u], u1 = utt_ptr[u + 1], l0 = lab_ptr[u], l1 = lab_ptr[u + 1];
-  if (!ctc_utt_ok(u0, u1, n_frames) || l0 < 0 || l1 < l0) return;
+  if (!tr_utt_ok(u0, u1, n_frames) || l0 < 0 || l1 < l0) return;
   const int T = (int)(u1 - u0);
   const int64_t L64 = l1 - l0;
-  if (ctc_states_per_lane(L64) != NS) return;
+  if (tr_states_per_lane(L64, tr_num_states(L64, true)) != NS) return;
   float* g = grad != nullptr ? grad + u0 * ldg : nullptr;
   int bits = 0;
   int L = 0;
@@ -270,19 +211,13 @@ __global__ void __launch_bounds__(64)
     bits = FHVAE_CTC_BAD_LABEL;
   } else {
     L = (int)L64;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) {
-      const int v = labels[l0 + i];
-      bad = bad || v < 0 || v >= C || v == blank;
-      sm.lab[i] = v;
-    }
-    if (__any(bad)) bits = FHVAE_CTC_BAD_LABEL;
+    if (tr_load_labels(labels, l0, L, C, blank, lane, sm.lab)) bits = FHVAE_CTC_BAD_LABEL;
   }
   const int S = 2 * L + 1;
   double* arow = nullptr;
   if (bits == 0 && g != nullptr && ws != nullptr && cell_ptr != nullptr) {
     const int64_t c0 = cell_ptr[u];
-    if (c0 < 0 || c0 > ws_cells || (int64_t)T * S > ws_cells - c0) return;  // (the check kernel has refused this already)
+    if (!tr_cells_fit(c0, T, S, ws_cells)) return;  // (the check kernel has refused this already)
     arow = ws + c0;
   }
   double ll = -INFINITY;
@@ -365,8 +300,8 @@ extern "C" int fhvae_ctc_loss(const float* logits, int64_t ldz, int64_t n_frames
     return FHVAE_ERR_ALIGN;
   if (grad == nullptr) cell_ptr = nullptr, ws = nullptr, ws_bytes = 0, ldg = 0;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(ctc_check_kernel, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, lab_ptr, cell_ptr, U, n_frames,
-                     ws_bytes / 8, status);
+  hipLaunchKernelGGL(tr_label_check_kernel<FHVAE_CTC_BAD_PTR>, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, lab_ptr,
+                     cell_ptr, U, n_frames, true, ws_bytes / 8, status);
 #define CTC_LAUNCH(NS)                                                                                                          \
   hipLaunchKernelGGL(ctc_loss_kernel<NS>, dim3((unsigned)U), dim3(64), 0, st, logits, ldz, n_frames, (int)C, (int)blank, utt_ptr, \
                      labels, lab_ptr, cell_ptr, U, nll, grad, ldg, status, (double*)ws, ws_bytes / 8)

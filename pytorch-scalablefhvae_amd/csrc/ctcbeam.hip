@@ -3,7 +3,7 @@
 //
 // One workgroup of four waves per utterance; the search is sequential in t and parallel over the at most W + W C candidates of a
 // frame.  The beam (pb, pnb, lm, node, parent node, last label, length) lives in LDS in two halves, the frame's log-softmax too
-// (every wave computes it as ctc.hip does, wave 0 parks it; the row is loaded a frame ahead).  A thread owns stay(tid) and the
+// (every wave computes it with trellis.h's tr_log_softmax, as ctc.hip does, wave 0 parks it; the row is loaded a frame ahead).  A thread owns stay(tid) and the
 // extensions tid + 256 r: at most 33 candidates, each an order-preserving 64-bit key of its score.
 // Selection: the W best under (score, index) by a radix select over the digits of (key, 65535 - index), eight bits a pass with an
 // LDS histogram, starting at the first byte in which the keys differ and stopping as soon as a bin holds exactly what is still
@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "trellis.h"
 
 #include "../../include/fhvae_ctcbeam.h"
 
@@ -29,35 +30,13 @@ constexpr int kCbC = FHVAE_CB_MAX_CLASSES;
 constexpr int kCbThreads = 256;
 constexpr int kCbRounds = (kCbW + kCbW * kCbC + kCbThreads - 1) / kCbThreads;  // 33 candidates a thread at most
 
-static_assert(FHVAE_CB_MAX_CLASSES == 128, "a lane owns two classes");
+static_assert(FHVAE_CB_MAX_CLASSES == kTrMaxClasses, "a lane owns two classes (trellis.h)");
 static_assert(FHVAE_CB_MAX_BEAM == 64, "a lane of wave 0 owns a beam position");
 static_assert(kCbRounds <= 64, "a thread's candidates are one bit each of a 64-bit mask");
 static_assert(kCbW + kCbW * kCbC <= 0xffff, "a candidate index is two digits");
 static_assert(FHVAE_CB_NODE_BYTES == 16, "a node is an int4");
 
 typedef unsigned long long cb_u64;
-
-__device__ __forceinline__ bool cb_utt_ok(int64_t a, int64_t b, int64_t n_frames) {
-  return a >= 0 && b >= a && b <= n_frames && b - a <= 0x7fffffffLL;
-}
-
-// one thread per utterance: the rules of the header
-__global__ void cb_check_kernel(const int64_t* __restrict__ utt_ptr, int64_t U, int64_t n_frames, int32_t* status) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < U) {
-    const int64_t a = utt_ptr[t], b = utt_ptr[t + 1];
-    bool ok = cb_utt_ok(a, b, n_frames);
-    if (t == 0) ok = ok && a == 0;
-    if (t == U - 1) ok = ok && b == n_frames;
-    if (!ok) atomicOr(status, FHVAE_CB_BAD_PTR);
-  }
-}
-
-// lse of two values as ctc.hip's: with both -inf the maximum is replaced by 0, the sum is 0 and log gives -inf
-__device__ __forceinline__ double cb_lse2(double a, double b) {
-  const double m = fmax(a, b), mm = m == -INFINITY ? 0.0 : m;
-  return mm + log(exp(a - mm) + exp(b - mm));
-}
 
 // larger score, larger key; -0 and +0 share a key; 0 is kept for "no candidate" (also a score of -inf)
 __device__ __forceinline__ cb_u64 cb_key(double s) {
@@ -129,7 +108,7 @@ __global__ void __launch_bounds__(kCbThreads)
   const int64_t u = blockIdx.x;
   if (u >= U || C < 2 || C > kCbC || blank < 0 || blank >= C || W < 1 || W > kCbW) return;
   const int64_t u0 = utt_ptr[u], u1 = utt_ptr[u + 1];
-  if (!cb_utt_ok(u0, u1, n_frames)) return;
+  if (!tr_utt_ok(u0, u1, n_frames)) return;
   const int T = (int)(u1 - u0);
   if (u0 > ws_nodes / W || (int64_t)T > ws_nodes / W - u0) return;  // (the host has refused a workspace this small already)
   int4* nodes = ws + u0 * W;                                      // node id v >= 1 is nodes[v - 1]; node 0 is the empty prefix
@@ -147,41 +126,26 @@ __global__ void __launch_bounds__(kCbThreads)
   }
   sm.hist[tid] = 0;
   float n0 = 0.f, n1 = 0.f;
-  if (T > 0) {
-    n0 = lane < C ? z[lane] : -INFINITY;
-    n1 = lane + 64 < C ? z[lane + 64] : -INFINITY;
-  }
+  if (T > 0) tr_load_row(z, C, lane, n0, n1);
   __syncthreads();
 
   for (int t = 0; t < T; ++t) {
-    // ---- the row's log-softmax (ctc.hip's expressions: every lane of every wave ends with the same bits) and the open classes
+    // ---- the row's log-softmax (the one ctc.hip trains with: every lane of every wave ends with the same bits) and the open classes
     const float z0 = n0, z1 = n1;
-    if (t + 1 < T) {
-      const float* row = z + (int64_t)(t + 1) * ldz;
-      n0 = lane < C ? row[lane] : -INFINITY;
-      n1 = lane + 64 < C ? row[lane + 64] : -INFINITY;
-    }
+    if (t + 1 < T) tr_load_row(z + (int64_t)(t + 1) * ldz, C, lane, n0, n1);
     {
-      float m = fmaxf(z0, z1);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-      const double d0 = (double)z0 - (double)m, d1 = (double)z1 - (double)m;
-      double s = exp(d0) + exp(d1);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-      const double lg = log(s);
-      const double l0 = d0 - lg, l1 = d1 - lg;
-      const double thr = (0.0 - lg) - class_beam;  // (the largest lp is that of the row maximum: 0 - lg)
-      const cb_u64 o0 = __ballot(lane < C && l0 >= thr), o1 = __ballot(lane + 64 < C && l1 >= thr);
+      const TrLogSoftmax r = tr_log_softmax(z0, z1);
+      const double thr = (0.0 - r.lg) - class_beam;  // (the largest lp is that of the row maximum: 0 - lg)
+      const cb_u64 o0 = __ballot(lane < C && r.l0 >= thr), o1 = __ballot(lane + 64 < C && r.l1 >= thr);
       if (wave == 0) {
-        if (lane < C) sm.lp[lane] = l0;
-        if (lane + 64 < C) sm.lp[lane + 64] = l1;
+        if (lane < C) sm.lp[lane] = r.l0;
+        if (lane + 64 < C) sm.lp[lane + 64] = r.l1;
         if (lane == 0) sm.open[0] = o0, sm.open[1] = o1;
       }
     }
     // ---- per entry: tot, where its parent sits, which of its children sit in the beam
     if (tid < n) {
-      sm.tot[tid] = cb_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]);
+      sm.tot[tid] = tr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]);
       const int me = sm.node[cur][tid], mypar = sm.par[cur][tid];
       int pp = -1;
       cb_u64 e0 = 0, e1 = 0;
@@ -202,10 +166,10 @@ __global__ void __launch_bounds__(kCbThreads)
       double pnb = li < C ? sm.pnb[cur][tid] + sm.lp[li] : -INFINITY;
       if (j >= 0 && li < C && ((sm.open[li >> 6] >> (li & 63)) & 1)) {
         const double ext = (li == sm.last[cur][j] ? sm.pb[cur][j] : sm.tot[j]) + sm.lp[li];
-        pnb = cb_lse2(pnb, ext);
+        pnb = tr_lse2(pnb, ext);
       }
       sm.spb[tid] = pb, sm.spnb[tid] = pnb;
-      sm.sscore[tid] = cb_lse2(pb, pnb) + sm.lm[cur][tid];
+      sm.sscore[tid] = tr_lse2(pb, pnb) + sm.lm[cur][tid];
     }
     if (tid == 0) sm.nsurv = 0;
     __syncthreads();
@@ -366,7 +330,7 @@ __global__ void __launch_bounds__(kCbThreads)
   // ---- the best final score, the first position that has it; its labels through the trie, written forward
   if (tid < n) {
     const int li = sm.last[cur][tid];
-    sm.fin[tid] = (cb_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + sm.lm[cur][tid]) + (lm != nullptr ? lm[(int64_t)li * (C + 1) + C] : 0.0);
+    sm.fin[tid] = (tr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + sm.lm[cur][tid]) + (lm != nullptr ? lm[(int64_t)li * (C + 1) + C] : 0.0);
   }
   __syncthreads();
   if (tid == 0) {
@@ -418,7 +382,7 @@ extern "C" int fhvae_cb_decode(const float* logits, int64_t ldz, int64_t n_frame
       ((uintptr_t)score & 7) != 0 || ((uintptr_t)status & 3) != 0)
     return FHVAE_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cb_check_kernel, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, U, n_frames, status);
+  hipLaunchKernelGGL(tr_check_kernel<FHVAE_CB_BAD_PTR>, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, U, n_frames, status);
   hipLaunchKernelGGL(cb_decode_kernel, dim3((unsigned)U), dim3(kCbThreads), 0, st, logits, ldz, n_frames, (int)C, (int)blank, utt_ptr, U,
                      (int)W, class_beam, lm, hyp, hyp_len, score, status, (int4*)ws, ws_bytes / FHVAE_CB_NODE_BYTES);
   return fh_launch_status();

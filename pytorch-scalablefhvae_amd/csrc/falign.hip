@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "trellis.h"
 
 #include "../../include/fhvae_falign.h"
 
@@ -33,49 +34,7 @@ constexpr int kFaCP = FHVAE_FA_MAX_CLASSES;  // entry kFaCP of each half of FaLd
 constexpr int kFaZP = kFaCP + 4;             // a half of the row buffer
 constexpr int kFaFrames = 64;                // frames per trace-back chunk
 
-static_assert(FHVAE_FA_MAX_CLASSES == 128, "a lane owns two classes");
-static_assert(2 * FHVAE_FA_MAX_LABELS + 1 <= 64 * 9, "a lane owns at most nine states");
-
-__device__ __forceinline__ bool fa_utt_ok(int64_t a, int64_t b, int64_t n_frames) {
-  return a >= 0 && b >= a && b <= n_frames && b - a <= 0x7fffffffLL;
-}
-
-// the trellis states of a transcription of L labels
-__device__ __forceinline__ int64_t fa_states(int64_t L, int blank) { return blank >= 0 ? 2 * L + 1 : L; }
-
-// the cells utterance (T, L) needs: T S; an over-long transcription is refused and needs none
-__device__ __forceinline__ int64_t fa_cells(int64_t T, int64_t L, int blank) {
-  return L > FHVAE_FA_MAX_LABELS ? 0 : T * fa_states(L, blank);
-}
-
-// one thread per utterance: the rules of the header
-__global__ void fa_check_kernel(const int64_t* __restrict__ utt_ptr, const int64_t* __restrict__ lab_ptr,
-                                const int64_t* __restrict__ cell_ptr, int64_t U, int64_t n_frames, int blank, int64_t ws_bytes,
-                                int32_t* status) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < U) {
-    const int64_t a = utt_ptr[t], b = utt_ptr[t + 1], la = lab_ptr[t], lb = lab_ptr[t + 1];
-    bool ok = fa_utt_ok(a, b, n_frames) && la >= 0 && lb >= la;
-    if (t == 0) ok = ok && a == 0 && la == 0;
-    if (t == U - 1) ok = ok && b == n_frames;
-    if (ok) {
-      const int64_t c0 = cell_ptr[t], c1 = cell_ptr[t + 1];
-      ok = c0 >= 0 && c1 >= c0 && c1 <= ws_bytes && c1 - c0 >= fa_cells(b - a, lb - la, blank);
-      if (t == 0) ok = ok && c0 == 0;
-    }
-    if (!ok) atomicOr(status, FHVAE_FA_BAD_PTR);
-  }
-}
-
-__device__ __forceinline__ void fa_load_row(const float* row, int C, int lane, float& z0, float& z1) {
-  z0 = lane < C ? row[lane] : -INFINITY;
-  z1 = lane + 64 < C ? row[lane + 64] : -INFINITY;
-}
-
-// the states a lane owns for a trellis of S states (a refused transcription goes with the smallest)
-__device__ __forceinline__ int fa_states_per_lane(int64_t L, int64_t S) {
-  return (L > FHVAE_FA_MAX_LABELS || S <= 64) ? 1 : (S <= 128 ? 2 : (S <= 256 ? 4 : 9));
-}
+static_assert(FHVAE_FA_MAX_CLASSES == kTrMaxClasses && FHVAE_FA_MAX_LABELS == kTrMaxLabels, "the lane layout of trellis.h");
 
 // bytes of a frame's packed back-pointers, at most (NS = 1: S <= 64 of them)
 template <int NS>
@@ -108,31 +67,25 @@ __global__ void __launch_bounds__(64)
   const int64_t u = blockIdx.x;
   if (u >= U || C < 2 || C > kFaCP || blank < -1 || blank >= C) return;
   const int64_t u0 = utt_ptr[u], u1 = utt_ptr[u + 1], l0 = lab_ptr[u], l1 = lab_ptr[u + 1];
-  if (!fa_utt_ok(u0, u1, n_frames) || l0 < 0 || l1 < l0) return;
+  if (!tr_utt_ok(u0, u1, n_frames) || l0 < 0 || l1 < l0) return;
   const int T = (int)(u1 - u0);
   const int64_t L64 = l1 - l0;
-  if (fa_states_per_lane(L64, fa_states(L64, blank)) != NS) return;
   const bool ctc = blank >= 0;
+  if (tr_states_per_lane(L64, tr_num_states(L64, ctc)) != NS) return;
   int bits = 0;
   int L = 0;
   if (L64 > FHVAE_FA_MAX_LABELS) {
     bits = FHVAE_FA_BAD_LABEL;
   } else {
     L = (int)L64;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) {
-      const int v = labels[l0 + i];
-      bad = bad || v < 0 || v >= C || v == blank;
-      sm.lab[i] = v;
-    }
-    if (__any(bad)) bits = FHVAE_FA_BAD_LABEL;
+    if (tr_load_labels(labels, l0, L, C, blank, lane, sm.lab)) bits = FHVAE_FA_BAD_LABEL;
   }
-  const int S = (int)fa_states(L, blank);
+  const int S = (int)tr_num_states(L, ctc);
   const int rs = NS == 1 ? S : fa_max_row_bytes<NS>();  // bytes of a frame's back-pointers
   int64_t bp0 = 0;                                       // where the utterance's back-pointers begin in ws
   if (bits == 0 && T > 0) {
     const int64_t c0 = cell_ptr[u];
-    if (c0 < 0 || c0 > ws_bytes || (int64_t)T * S > ws_bytes - c0) return;  // (the check kernel has refused this already)
+    if (!tr_cells_fit(c0, T, S, ws_bytes)) return;  // (the check kernel has refused this already; a cell is a byte)
     bp0 = NS == 9 ? (c0 + 3) & ~(int64_t)3 : c0;  // (T - 1) rs + 3 <= T S for S >= 257: the dword stores stay in the utterance's bytes
   }
   for (int64_t i = lane; i < 2 * L64; i += 64) seg[2 * l0 + i] = -1;
@@ -143,24 +96,17 @@ __global__ void __launch_bounds__(64)
     if (L == 0) best = 0.0;
   } else if (bits == 0 && S > 0) {
     __syncthreads();
-    // cls: l'_s; a state past the end reads the -inf entry of z, so its delta is -inf with no test in the loop.
-    // pen: 0 where the skip into the state is allowed, else -inf (added to the candidate: exact)
+    // cls, pen: trellis.h; a state past the end reads the -inf entry of z, so its delta is -inf with no test in the loop
     int cls[NS];
     double pen[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      const int s = lane * NS + k, li = (s - 1) >> 1;
-      const bool odd = ctc && s < S && (s & 1);
-      cls[k] = s < S ? (ctc ? (odd ? sm.lab[li] : blank) : sm.lab[s]) : kFaCP;
-      pen[k] = (odd && s >= 3 && sm.lab[li] != sm.lab[li - 1]) ? 0.0 : -INFINITY;
-    }
+    tr_state_classes<NS>(sm.lab, lane, S, ctc, blank, kFaCP, cls, pen);
     if (lane == 0) sm.z[kFaCP] = -INFINITY, sm.z[kFaZP + kFaCP] = -INFINITY;
     const float* z = scores + u0 * lds;
     // ---- forward.  n0, n1: the row two frames ahead at the top of the loop; e: this frame's scores of the lane's states
     float n0, n1;
-    fa_load_row(z, C, lane, n0, n1);
+    tr_load_row(z, C, lane, n0, n1);
     sm.z[lane] = n0, sm.z[lane + 64] = n1;
-    if (T > 1) fa_load_row(z + lds, C, lane, n0, n1);
+    if (T > 1) tr_load_row(z + lds, C, lane, n0, n1);
     __syncthreads();
     double a[NS];
     float e[NS];
@@ -169,7 +115,7 @@ __global__ void __launch_bounds__(64)
     for (int k = 0; k < NS; ++k) a[k] = lane * NS + k < n_start ? (double)sm.z[cls[k]] : -INFINITY;
     if (T > 1) {
       sm.z[kFaZP + lane] = n0, sm.z[kFaZP + lane + 64] = n1;
-      if (T > 2) fa_load_row(z + 2 * lds, C, lane, n0, n1);
+      if (T > 2) tr_load_row(z + 2 * lds, C, lane, n0, n1);
     }
     __syncthreads();
 #pragma unroll
@@ -179,16 +125,14 @@ __global__ void __launch_bounds__(64)
       float* zn = sm.z + ((t + 1) & 1) * kFaZP;
       if (t + 1 < T) {
         zn[lane] = n0, zn[lane + 64] = n1;
-        if (t + 2 < T) fa_load_row(z + (int64_t)(t + 2) * lds, C, lane, n0, n1);  // two frames ahead
+        if (t + 2 < T) tr_load_row(z + (int64_t)(t + 2) * lds, C, lane, n0, n1);  // two frames ahead
       }
       __syncthreads();
       float en[NS];
 #pragma unroll
       for (int k = 0; k < NS; ++k) en[k] = zn[cls[k]];  // the next frame's scores: not needed before the next turn
-      double up1 = __shfl_up(a[NS - 1], 1, 64);                                                    // state lane NS - 1
-      double up2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1, 64) : __shfl_up(a[0], 2, 64);  // state lane NS - 2
-      if (lane < 1) up1 = -INFINITY;
-      if (lane < (NS >= 2 ? 1 : 2)) up2 = -INFINITY;
+      double up1, up2;
+      tr_left<NS>(a, lane, up1, up2);
       uint32_t code = 0;
 #pragma unroll
       for (int k = NS - 1; k >= 0; --k) {  // downwards: a[k - 1] and a[k - 2] are still the frame before's
@@ -319,8 +263,8 @@ extern "C" int fhvae_fa_align(const float* scores, int64_t lds, int64_t n_frames
       ((uintptr_t)state & 3) != 0 || ((uintptr_t)seg & 3) != 0 || ((uintptr_t)score & 7) != 0 || ((uintptr_t)status & 3) != 0)
     return FHVAE_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(fa_check_kernel, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, lab_ptr, cell_ptr, U, n_frames,
-                     (int)blank, ws_bytes, status);
+  hipLaunchKernelGGL(tr_label_check_kernel<FHVAE_FA_BAD_PTR>, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, lab_ptr,
+                     cell_ptr, U, n_frames, blank >= 0, ws_bytes, status);  // (a back-pointer cell is one byte)
 #define FA_LAUNCH(NS)                                                                                                           \
   hipLaunchKernelGGL(fa_align_kernel<NS>, dim3((unsigned)U), dim3(64), 0, st, scores, lds, n_frames, (int)C, (int)blank, utt_ptr, \
                      labels, lab_ptr, cell_ptr, U, state, seg, score, status, (uint8_t*)ws, ws_bytes)

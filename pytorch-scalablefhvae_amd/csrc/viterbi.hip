@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "trellis.h"
 
 #include "../../include/fhvae_viterbi.h"
 
@@ -40,22 +41,6 @@ constexpr int kEdRing = 128;    // hyp tokens in the ring: two tiles of 64
 
 static_assert(FHVAE_VIT_MAX_STATES == 128, "a lane owns one or two states");
 static_assert(kEdRows * 64 == FHVAE_EDIT_MAX_REF && FHVAE_EDIT_MAX_REF < 65536, "S and D share a word, 16 bits each");
-
-__device__ __forceinline__ bool vit_utt_ok(int64_t a, int64_t b, int64_t n_frames) {
-  return a >= 0 && b >= a && b <= n_frames && b - a <= 0x7fffffffLL;
-}
-
-// one thread per utterance: the rules of the header
-__global__ void vit_check_kernel(const int64_t* __restrict__ utt_ptr, int64_t U, int64_t n_frames, int32_t* status) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < U) {
-    const int64_t a = utt_ptr[t], b = utt_ptr[t + 1];
-    bool ok = vit_utt_ok(a, b, n_frames);
-    if (t == 0) ok = ok && a == 0;
-    if (t == U - 1) ok = ok && b == n_frames;
-    if (!ok) atomicOr(status, FHVAE_VIT_BAD_PTR);
-  }
-}
 
 __device__ __forceinline__ float vit_lane_read(float v, int p) {  // v of lane p; p is wave-uniform
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), p));
@@ -115,7 +100,7 @@ __global__ void __launch_bounds__(kVitThreads)
   const int64_t u = blockIdx.x;
   if (u >= U || C < 1 || C > CP) return;
   const int64_t u0 = utt_ptr[u], u1 = utt_ptr[u + 1];
-  if (!vit_utt_ok(u0, u1, n_frames)) return;
+  if (!tr_utt_ok(u0, u1, n_frames)) return;
   const int m = (int)(u1 - u0);
   if (m == 0) {
     if (tid == 0) score[u] = -INFINITY;
@@ -329,7 +314,7 @@ extern "C" int fhvae_vit_decode(const float* emit, int64_t lde, int64_t n_frames
     return FHVAE_ERR_ALIGN;
   if (ws_bytes < vit_ws(n_frames, C)) return FHVAE_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(vit_check_kernel, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, U, n_frames, status);
+  hipLaunchKernelGGL(tr_check_kernel<FHVAE_VIT_BAD_PTR>, dim3((unsigned)fh_cdiv(U, 256)), dim3(256), 0, st, utt_ptr, U, n_frames, status);
   hipLaunchKernelGGL(C <= 64 ? vit_decode_kernel<1> : vit_decode_kernel<2>, dim3((unsigned)U), dim3(kVitThreads), 0, st, emit, lde, n_frames, (int)C, trans, init, fin, utt_ptr, U,
                      path, score, status, (uint8_t*)ws);
   return fh_launch_status();

@@ -47,55 +47,15 @@ def _device(op, name, t, dtype, dim):
     return hip_ext.device_tensor(op, name, t, "the CTC pass", dtype, dim)
 
 
-def _host_ptr(op, name, p):
-    """A (U + 1,) pointer array as int64 numpy (a device tensor is copied: one sync), monotone from 0."""
-    a = np.asarray(p.cpu() if hasattr(p, "cpu") else p)
-    if a.ndim != 1 or a.shape[0] < 1 or a.dtype.kind not in "iu":
-        raise RuntimeError("%s: %s must hold U + 1 integers" % (op, name))
-    a = a.astype(np.int64)
-    if a[0] != 0 or (np.diff(a) < 0).any():
-        raise RuntimeError("%s: %s is not monotone from 0" % (op, name))
-    return a
-
-
 def cells(utt_ptr, lab_ptr):
     """The float64 alpha cells every utterance needs: T_u (2 L_u + 1); an utterance the kernel refuses (L_u above 256) needs none."""
     T, L = np.diff(np.asarray(utt_ptr, dtype=np.int64)), np.diff(np.asarray(lab_ptr, dtype=np.int64))
     return np.where(L > CTC_MAX_LABELS, 0, T * (2 * L + 1))
 
 
-def groups(need, ws_limit):
-    """Consecutive groups [(a, b)] of utterances whose summed workspace bytes (8 per cell) fit ws_limit; an utterance larger than
-    the limit gets a group of its own."""
-    out, a, run = [], 0, 0
-    for u, n in enumerate(8 * np.asarray(need, dtype=np.int64)):
-        if u > a and run + n > ws_limit:
-            out.append((a, u))
-            a, run = u, 0
-        run += int(n)
-    if len(need) > a:
-        out.append((a, len(need)))
-    return out
-
-
-class _Plan:
-    """The host side of a batch, built once: the groups and their rebased pointer arrays on the device."""
-
-    def __init__(self, op, utt_ptr, lab_ptr, device, want_grad, ws_limit):
-        import torch
-
-        self.utt, self.lab = _host_ptr(op, "utt_ptr", utt_ptr), _host_ptr(op, "lab_ptr", lab_ptr)
-        if self.utt.shape != self.lab.shape:
-            raise RuntimeError("%s: utt_ptr holds %d entries, lab_ptr %d" % (op, self.utt.shape[0], self.lab.shape[0]))
-        self.U = int(self.utt.shape[0]) - 1
-        need = cells(self.utt, self.lab)
-        self.parts = []
-        self.ws_cells = 0
-        for a, b in (groups(need, int(ws_limit)) if want_grad else ([(0, self.U)] if self.U else [])):
-            cell = np.concatenate([[0], np.cumsum(need[a:b])]).astype(np.int64)
-            ptrs = np.stack([self.utt[a:b + 1] - self.utt[a], self.lab[a:b + 1] - self.lab[a], cell])
-            self.parts.append((a, b, torch.from_numpy(ptrs).to(device)))
-            self.ws_cells = max(self.ws_cells, int(cell[-1]))
+def _plan(op, utt_ptr, lab_ptr, device, want_grad, ws_limit):
+    """hip_ext.BatchPlan of a batch: groups whose float64 alpha cells fit ws_limit bytes; without the gradient one group."""
+    return hip_ext.BatchPlan(op, utt_ptr, lab_ptr, device, cells, 8, ws_limit if want_grad else None)
 
 
 def _enqueue(lib, plan, logits, n_classes, labels, blank, nll, grad, status):
@@ -125,19 +85,6 @@ def _enqueue(lib, plan, logits, n_classes, labels, blank, nll, grad, status):
                  ws.numel() if g is not None else 0)
 
 
-def _padded_rows(op, logits):
-    """(N, C) f32 device rows -> rows the kernel takes as they are: unit column stride, a leading dimension that is a multiple
-    of 4 and at least C, 16-byte aligned."""
-    import torch
-
-    n_classes = int(logits.shape[1])
-    if n_classes < 2 or n_classes > CTC_MAX_CLASSES:
-        raise RuntimeError("%s: %d classes, the CTC kernel takes 2 to %d (the blank included)" % (op, n_classes, CTC_MAX_CLASSES))
-    if logits.shape[0] and not hip_ext.rows_dense(logits, n_classes):
-        logits = torch.nn.functional.pad(logits, (0, -n_classes % 4)) if n_classes % 4 else logits.contiguous()
-    return logits
-
-
 def loss(logits, utt_ptr, labels, lab_ptr, blank, want_grad=True, ws_limit=1 << 30):
     """fhvae_ctc_loss.  logits (N, C) f32, utt_ptr (U + 1,) int64, labels int32, lab_ptr (U + 1,) int64, all on the device ->
     (nll (U,) float64, grad (N, C) f32 or None, status: the OR of CTC_BAD_LABEL and CTC_INFEASIBLE over the utterances).
@@ -153,10 +100,10 @@ def loss(logits, utt_ptr, labels, lab_ptr, blank, want_grad=True, ws_limit=1 << 
     labels = _device(op, "labels", labels, torch.int32, 1).contiguous()
     _device(op, "lab_ptr", lab_ptr, torch.int64, 1)
     n_classes, blank = int(logits.shape[1]), int(blank)
-    logits = _padded_rows(op, logits)
+    logits = hip_ext.class_rows(op, logits, "the CTC kernel", CTC_MAX_CLASSES)
     if not 0 <= blank < n_classes:
         raise RuntimeError("%s: blank = %d lies outside the %d classes" % (op, blank, n_classes))
-    plan = _Plan(op, utt_ptr, lab_ptr, logits.device, want_grad, ws_limit)
+    plan = _plan(op, utt_ptr, lab_ptr, logits.device, want_grad, ws_limit)
     N = int(logits.shape[0])
     if plan.utt[-1] != N or plan.lab[-1] > labels.shape[0]:
         raise RuntimeError("%s: the pointers end at %d rows and %d labels, the arrays hold %d and %d"
@@ -205,7 +152,7 @@ class _Prepared:
 
         self.x = _device(op, "x", x, torch.float32, 2).contiguous()
         self.labels = _device(op, "labels", labels, torch.int32, 1).contiguous()
-        self.plan = _Plan(op, utt_ptr, lab_ptr, x.device, True, ws_limit)
+        self.plan = _plan(op, utt_ptr, lab_ptr, x.device, True, ws_limit)
         if self.plan.utt[-1] != x.shape[0] or self.plan.lab[-1] > self.labels.shape[0]:
             raise RuntimeError("%s: the pointers end at %d rows and %d labels, the arrays hold %d and %d"
                                % (op, self.plan.utt[-1], self.plan.lab[-1], x.shape[0], self.labels.shape[0]))
@@ -313,7 +260,7 @@ def fit(x, utt_ptr, refs, n_phones, l2=1e-4, iters=200, gtol=1e-5, context=0, in
     if iters < 0 or not l2 >= 0:
         raise ValueError("fit: iters = %r and l2 = %r must not be negative" % (iters, l2))
     x = _device("fit", "x", x, torch.float32, 2)
-    utt = _host_ptr("fit", "utt_ptr", utt_ptr)
+    utt = hip_ext.host_ptr("fit", "utt_ptr", utt_ptr)
     if utt[-1] != x.shape[0] or len(refs) != utt.shape[0] - 1:
         raise ValueError("fit: utt_ptr and refs do not describe the %d rows" % int(x.shape[0]))
     for r in refs:

@@ -57,7 +57,7 @@ def decode(logits, utt_ptr, blank, beam=16, lm=None, class_beam=float("inf"), ws
     op, noun = "decode", "the CTC beam search"
     logits = hip_ext.device_tensor(op, "logits", logits, noun, torch.float32, 2)
     n_classes, blank, beam, class_beam = int(logits.shape[1]), int(blank), int(beam), float(class_beam)
-    logits = ctc._padded_rows(op, logits)
+    logits = hip_ext.class_rows(op, logits, noun, CB_MAX_CLASSES)
     if not 0 <= blank < n_classes:
         raise RuntimeError("%s: blank = %d lies outside the %d classes" % (op, blank, n_classes))
     if not 1 <= beam <= CB_MAX_BEAM:
@@ -73,8 +73,10 @@ def decode(logits, utt_ptr, blank, beam=16, lm=None, class_beam=float("inf"), ws
         if not on_device and (bool(torch.isnan(lm).any()) or bool((lm == float("inf")).any())):
             raise RuntimeError("%s: lm holds NaN or +inf" % op)
         lm = lm.to(dev).contiguous()
-    utt = ctc._host_ptr(op, "utt_ptr", utt_ptr)
-    U, N = int(utt.shape[0]) - 1, int(logits.shape[0])
+    # a cell is the beam's trie nodes of one frame
+    plan = hip_ext.BatchPlan(op, utt_ptr, None, dev, lambda utt, lab: np.diff(utt), beam * CB_NODE_BYTES, ws_limit)
+    utt = plan.utt
+    U, N = plan.U, int(logits.shape[0])
     if utt[-1] != N:
         raise RuntimeError("%s: utt_ptr ends at %d rows, logits holds %d" % (op, utt[-1], N))
     lib = load_library()
@@ -84,16 +86,12 @@ def decode(logits, utt_ptr, blank, beam=16, lm=None, class_beam=float("inf"), ws
     if U == 0:
         res = (hyp[:0], torch.zeros(1, dtype=torch.int64, device=dev), score)
         return res + (0,) if with_status else res
-    T = np.diff(utt)
-    parts = ctc.groups(T * (beam * CB_NODE_BYTES // 8), int(ws_limit))  # (ctc.groups counts 8 bytes per cell)
-    need = max(int(lib.fhvae_cb_ws_bytes(int(utt[b] - utt[a]), beam)) for a, b in parts)
-    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.fhvae_cb_ws_bytes(plan.ws_cells, beam)), 256), dtype=torch.uint8, device=dev)
     no_rows = torch.zeros(1, (n_classes + 3) // 4 * 4, dtype=torch.float32, device=dev)  # (an empty array has no address)
-    for a, b in parts:
+    for a, b, ptrs in plan.parts:
         f0, f1 = int(utt[a]), int(utt[b])
-        ptr = torch.from_numpy(utt[a:b + 1] - f0).to(dev)
         z = logits[f0:f1] if f1 > f0 else no_rows
-        hb._call("fhvae_cb_decode", hb._p(z), z.stride(0), f1 - f0, n_classes, blank, hb._p(ptr), b - a, beam, class_beam,
+        hb._call("fhvae_cb_decode", hb._p(z), z.stride(0), f1 - f0, n_classes, blank, hb._p(ptrs[0]), b - a, beam, class_beam,
                  hb._p(lm) if lm is not None else None, hb._p(hyp[f0:] if f1 > f0 else hyp), hb._p(out[1 + a:]), hb._p(score[a:b]),
                  hb._p(out), hb._p(ws), ws.numel())
     host = out.cpu().numpy()  # the one sync

@@ -69,32 +69,27 @@ def align(scores, utt_ptr, labels, lab_ptr, blank, ws_limit=1 << 30):
     labels = hip_ext.device_tensor(op, "labels", labels, noun, torch.int32, 1).contiguous()
     hip_ext.device_tensor(op, "lab_ptr", lab_ptr, noun, torch.int64, 1)
     n_classes, blank = int(scores.shape[1]), int(blank)
-    scores = ctc._padded_rows(op, scores)
+    scores = hip_ext.class_rows(op, scores, noun, FA_MAX_CLASSES)
     if not -1 <= blank < n_classes:
         raise RuntimeError("%s: blank = %d is neither a class of the %d nor -1" % (op, blank, n_classes))
-    utt, lab = ctc._host_ptr(op, "utt_ptr", utt_ptr), ctc._host_ptr(op, "lab_ptr", lab_ptr)
-    if utt.shape != lab.shape:
-        raise RuntimeError("%s: utt_ptr holds %d entries, lab_ptr %d" % (op, utt.shape[0], lab.shape[0]))
-    U, N, n_labels = int(utt.shape[0]) - 1, int(scores.shape[0]), int(lab[-1])
+    dev = scores.device
+    plan = hip_ext.BatchPlan(op, utt_ptr, lab_ptr, dev, lambda utt, lab: cells(utt, lab, blank), 1, ws_limit)  # (a cell is a byte)
+    utt, lab = plan.utt, plan.lab
+    U, N, n_labels = plan.U, int(scores.shape[0]), int(lab[-1])
     if utt[-1] != N or n_labels > labels.shape[0]:
         raise RuntimeError("%s: the pointers end at %d rows and %d labels, the arrays hold %d and %d" % (op, utt[-1], n_labels, N, labels.shape[0]))
     lib = load_library()
-    dev = scores.device
     state = torch.empty(N, dtype=torch.int32, device=dev)
     seg = torch.empty(n_labels, 2, dtype=torch.int32, device=dev)
     score = torch.empty(U, dtype=torch.float64, device=dev)
     if U == 0:
         return state, seg, score, 0
-    need = cells(utt, lab, blank)
-    parts = ctc.groups(need, 8 * int(ws_limit))  # (ctc.groups counts 8 bytes per cell, a back-pointer cell is one byte)
-    ws = torch.empty(max(int(lib.fhvae_fa_ws_bytes(max(int(need[a:b].sum()) for a, b in parts))), 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.fhvae_fa_ws_bytes(plan.ws_cells)), 256), dtype=torch.uint8, device=dev)
     status = hip_ext.status_word(dev)
     no_rows = torch.zeros(1, (n_classes + 3) // 4 * 4, dtype=torch.float32, device=dev)  # (an empty array has no address)
     no_int = torch.zeros(2, dtype=torch.int32, device=dev)
-    for a, b in parts:
+    for a, b, ptrs in plan.parts:
         f0, f1, l0, l1 = int(utt[a]), int(utt[b]), int(lab[a]), int(lab[b])
-        cell = np.concatenate([[0], np.cumsum(need[a:b])]).astype(np.int64)
-        ptrs = torch.from_numpy(np.stack([utt[a:b + 1] - f0, lab[a:b + 1] - l0, cell])).to(dev)
         z = scores[f0:f1] if f1 > f0 else no_rows
         hb._call("fhvae_fa_align", hb._p(z), z.stride(0), f1 - f0, n_classes, blank, hb._p(ptrs[0]), hb._p(labels[l0:l1] if l1 > l0 else no_int),
                  hb._p(ptrs[1]), hb._p(ptrs[2]), b - a, hb._p(state[f0:f1] if f1 > f0 else no_int), hb._p(seg[l0:l1] if l1 > l0 else no_int),

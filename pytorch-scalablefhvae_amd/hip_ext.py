@@ -7,10 +7,13 @@ hip_binding._call; this module is the rest:
   load             the library with a module's table bound
   rows_dense, pad_rows, padded_rows   the (N, D) f32 row operand: the one stride / alignment rule, the zero padding
   device_tensor    the "device tensor of this dtype / rank / shape" check with the module's noun in the message
+  class_rows       the (N, C) f32 rows of per-frame class scores the trellis kernels take (ctc, falign, ctcbeam)
+  host_ptr, groups, BatchPlan         a ragged batch: its (U + 1,) pointers on the host, the consecutive groups whose
+                   workspace fits a byte limit, and the groups' rebased pointer rows on the device
   workspace        a grow-only byte buffer per owner and device
   status_word, check_status           the int32 device status word and its one read
 
-Plain functions; importing it needs neither a GPU nor torch.cuda.
+Plain functions and one plain class; importing it needs neither a GPU nor torch.cuda.
 """
 from __future__ import annotations
 
@@ -82,6 +85,77 @@ def device_tensor(op, name, t, noun, dtype=None, dim=None, shape=None, contiguou
         want += ["of shape %s" % (tuple(shape),)] if shape is not None else []
         raise RuntimeError("%s: %s must be %s (got %s %s)" % (op, name, " ".join(w for w in want if w), t.dtype, tuple(t.shape)))
     return t
+
+
+def class_rows(op, logits, noun, max_classes):
+    """(N, C) f32 device rows of per-frame class scores -> rows the kernels take as they are: unit column stride, a leading
+    dimension that is a multiple of 4 and at least C, 16-byte aligned.  `noun` names the feature in the message."""
+    import torch
+
+    n_classes = int(logits.shape[1])
+    if n_classes < 2 or n_classes > max_classes:
+        raise RuntimeError("%s: %d classes, %s takes 2 to %d" % (op, n_classes, noun, max_classes))
+    if logits.shape[0] and not rows_dense(logits, n_classes):
+        logits = torch.nn.functional.pad(logits, (0, -n_classes % 4)) if n_classes % 4 else logits.contiguous()
+    return logits
+
+
+# ------------------------------------------------------------------------------------------------------------ ragged batches
+def host_ptr(op, name, p):
+    """A (U + 1,) pointer array as int64 numpy (a device tensor is copied: one sync), monotone from 0."""
+    import numpy as np
+
+    a = np.asarray(p.cpu() if hasattr(p, "cpu") else p)
+    if a.ndim != 1 or a.shape[0] < 1 or a.dtype.kind not in "iu":
+        raise RuntimeError("%s: %s must hold U + 1 integers" % (op, name))
+    a = a.astype(np.int64)
+    if a[0] != 0 or (np.diff(a) < 0).any():
+        raise RuntimeError("%s: %s is not monotone from 0" % (op, name))
+    return a
+
+
+def groups(need_bytes, ws_limit):
+    """Consecutive groups [(a, b)] of utterances whose summed workspace bytes fit ws_limit; an utterance larger than the limit
+    gets a group of its own."""
+    out, a, run = [], 0, 0
+    for u, n in enumerate(need_bytes):
+        if u > a and run + n > ws_limit:
+            out.append((a, u))
+            a, run = u, 0
+        run += int(n)
+    if len(need_bytes) > a:
+        out.append((a, len(need_bytes)))
+    return out
+
+
+class BatchPlan:
+    """The host side of a ragged batch, built once: the groups and their rebased pointer arrays on the device.
+
+      utt, lab   the (U + 1,) int64 host pointers of host_ptr (lab is None for a batch without labels); U
+      parts      [(a, b, ptrs)]: the utterances a .. b - 1 go in one call; ptrs is an int64 device tensor whose rows are
+                 utt[a : b + 1] - utt[a], then (with labels) lab[a : b + 1] - lab[a], then the group's cumulative cells from 0
+      ws_cells   the cells of the largest group
+
+    need(utt, lab) gives the workspace cells per utterance, cell_bytes the bytes of one; ws_limit None puts all utterances
+    into one group."""
+
+    def __init__(self, op, utt_ptr, lab_ptr, device, need, cell_bytes, ws_limit):
+        import numpy as np
+        import torch
+
+        self.utt = host_ptr(op, "utt_ptr", utt_ptr)
+        self.lab = host_ptr(op, "lab_ptr", lab_ptr) if lab_ptr is not None else None
+        if self.lab is not None and self.utt.shape != self.lab.shape:
+            raise RuntimeError("%s: utt_ptr holds %d entries, lab_ptr %d" % (op, self.utt.shape[0], self.lab.shape[0]))
+        self.U = int(self.utt.shape[0]) - 1
+        cells = np.asarray(need(self.utt, self.lab), dtype=np.int64)
+        self.parts = []
+        self.ws_cells = 0
+        for a, b in (groups(int(cell_bytes) * cells, int(ws_limit)) if ws_limit is not None else ([(0, self.U)] if self.U else [])):
+            cell = np.concatenate([[0], np.cumsum(cells[a:b])]).astype(np.int64)
+            rows = [p[a:b + 1] - p[a] for p in (self.utt, self.lab) if p is not None] + [cell]
+            self.parts.append((a, b, torch.from_numpy(np.stack(rows)).to(device)))
+            self.ws_cells = max(self.ws_cells, int(cell[-1]))
 
 
 def workspace(owner, device, need):

@@ -157,10 +157,7 @@ def test_groups_and_cells():
     import ctc
 
     need = ctc.cells([0, 10, 10, 40, 45], [0, 3, 3, 3, 300])
-    assert need.tolist() == [70, 0, 30, 0]
-    assert ctc.groups([5, 5, 5], 80) == [(0, 2), (2, 3)]
-    assert ctc.groups([5, 50, 5, 0], 80) == [(0, 1), (1, 2), (2, 4)]
-    assert ctc.groups([], 80) == [] and ctc.groups([1, 1], 1 << 30) == [(0, 2)]
+    assert need.tolist() == [70, 0, 30, 0]  # (the groups of such needs: test_hip_ext_cpu.py, test_groups_by_bytes)
     assert ctc.feasible(5, [0, 0, 1, 2]) and not ctc.feasible(4, [0, 0, 1, 2]) and ctc.feasible(0, [])
 
 

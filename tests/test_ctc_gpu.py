@@ -15,6 +15,7 @@ import torch
 
 import ctc_ref as R
 import viterbi_ref as VR
+from trellis_cases import bits32, bits64, blank_of, dev, labels_for, ptr_of
 
 pytestmark = pytest.mark.gpu
 
@@ -35,38 +36,6 @@ def ctc():
     assert torch.cuda.is_available()
     ctc.load_library()
     return ctc
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def ptr_of(lengths):
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-
-
-def bits64(a):
-    return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).view(np.int64)
-
-
-def bits32(a):
-    return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).view(np.int32)
-
-
-def labels_for(rng, L, C, blank, repeats):
-    """L labels without the blank, neighbours different where C allows, then `repeats` neighbours made equal."""
-    classes = [c for c in range(C) if c != blank]
-    lab = []
-    for _ in range(L):
-        pick = [c for c in classes if not lab or c != lab[-1]] or classes
-        lab.append(int(pick[rng.integers(len(pick))]))
-    for i in rng.permutation(max(L - 1, 0))[:repeats]:
-        lab[i + 1] = lab[i]
-    return lab
-
-
-def blank_of(C, where):
-    return {"first": 0, "middle": C // 2, "last": C - 1}[where]
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,6 +13,7 @@ import torch
 import ctcbeam_cases as K
 import ctcbeam_ref as R
 import viterbi_ref as VR
+from trellis_cases import bits64, dev, ptr_of
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -28,18 +29,6 @@ def cb():
     assert torch.cuda.is_available()
     ctcbeam.load_library()
     return ctcbeam
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def ptr_of(lengths):
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-
-
-def bits64(a):
-    return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).view(np.int64)
 
 
 def hyps_of(tokens, ptr):

@@ -108,6 +108,49 @@ def test_padded_rows_and_device_tensor_refuse():
             hip_ext.device_tensor("op", "y", bad, "the mixture", torch.float32, shape=(3,))
 
 
+def test_groups_by_bytes():
+    # (the cases ctc.groups was held to, its needs of 5, 50 .. float64 cells given in bytes)
+    assert hip_ext.groups([40, 40, 40], 80) == [(0, 2), (2, 3)]
+    assert hip_ext.groups([40, 400, 40, 0], 80) == [(0, 1), (1, 2), (2, 4)]
+    assert hip_ext.groups([], 80) == [] and hip_ext.groups([8, 8], 1 << 30) == [(0, 2)]
+
+
+def test_batch_plan_rebases_the_groups_and_counts_cells():
+    import numpy as np
+
+    def need(utt, lab):
+        return np.diff(utt) * (2 * np.diff(lab) + 1)
+
+    utt, lab = [0, 5, 5, 8, 9], torch.tensor([0, 2, 2, 3, 3])
+    plan = hip_ext.BatchPlan("op", utt, lab, "cpu", need, 8, 8 * 25)
+    assert plan.U == 4 and plan.utt.tolist() == utt and plan.lab.tolist() == [0, 2, 2, 3, 3] and plan.ws_cells == 25
+    assert [(a, b) for a, b, _ in plan.parts] == [(0, 2), (2, 4)]
+    assert plan.parts[0][2].tolist() == [[0, 5, 5], [0, 2, 2], [0, 25, 25]] and plan.parts[0][2].dtype == torch.int64
+    assert plan.parts[1][2].tolist() == [[0, 3, 4], [0, 1, 1], [0, 9, 10]]
+    one = hip_ext.BatchPlan("op", utt, lab, "cpu", need, 8, None)  # no limit: one group
+    assert [(a, b) for a, b, _ in one.parts] == [(0, 4)] and one.ws_cells == 35
+    bare = hip_ext.BatchPlan("op", utt, None, "cpu", lambda utt, lab: np.diff(utt), 16, 1 << 30)  # no labels: two rows
+    assert bare.lab is None and bare.parts[0][2].tolist() == [[0, 5, 5, 8, 9], [0, 5, 5, 8, 9]] and bare.ws_cells == 9
+    assert hip_ext.BatchPlan("op", [0], [0], "cpu", need, 8, 80).parts == []
+    with pytest.raises(RuntimeError, match="op: utt_ptr holds 5 entries, lab_ptr 4"):
+        hip_ext.BatchPlan("op", utt, [0, 2, 2, 3], "cpu", need, 8, 80)
+    with pytest.raises(RuntimeError, match="op: utt_ptr is not monotone from 0"):
+        hip_ext.BatchPlan("op", [0, 5, 4], [0, 1, 1], "cpu", need, 8, 80)
+    with pytest.raises(RuntimeError, match="op: lab_ptr must hold U \\+ 1 integers"):
+        hip_ext.BatchPlan("op", utt, np.zeros(5), "cpu", need, 8, 80)
+
+
+def test_class_rows_names_the_feature():
+    with pytest.raises(RuntimeError, match="op: 129 classes, forced alignment takes 2 to 128"):
+        hip_ext.class_rows("op", torch.zeros(3, 129), "forced alignment", 128)
+    with pytest.raises(RuntimeError, match="op: 1 classes, the CTC kernel takes 2 to 128"):
+        hip_ext.class_rows("op", torch.zeros(3, 1), "the CTC kernel", 128)
+    x = torch.zeros(5, 8)
+    assert hip_ext.class_rows("op", x, "the CTC kernel", 128) is x  # dense rows are taken as they are
+    y = hip_ext.class_rows("op", torch.ones(5, 6), "the CTC kernel", 128)
+    assert tuple(y.shape) == (5, 8) and y.stride(0) == 8 and bool((y[:, 6:] == 0).all()) and bool((y[:, :6] == 1).all())
+
+
 def test_workspace_grows_only_and_owners_do_not_share():
     a = hip_ext.workspace("test-owner-a", "cpu", 1024)
     assert a.dtype == torch.uint8 and a.numel() == 1024 and a.device.type == "cpu"

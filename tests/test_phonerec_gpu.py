@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import viterbi_ref as R
+from trellis_cases import dev, ptr_of
 
 pytestmark = pytest.mark.gpu
 
@@ -35,14 +36,6 @@ def pr():
 def bits(a):
     a = np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
     return a.view(np.int32) if a.dtype == np.float32 else a
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def ptr_of(lengths):
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
 
 
 @functools.lru_cache(maxsize=None)

@@ -75,6 +75,7 @@ def loss_cases(reps, out):
     import torch
 
     import ctc
+    import hip_ext
 
     dev = torch.device("cuda:0")
     for C in (40, 62):
@@ -98,7 +99,7 @@ def loss_cases(reps, out):
             times, outs, errors = host_rounds(fns, torch.cuda.synchronize, reps)
             cells = int(T * (2 * lens + 1).sum())
             line = {"case": "ctc_" + name, "C": C, "utterances": U, "frames": U * T, "labels": int(lens.sum()), "cells": cells,
-                    "ws_groups": len(ctc.groups(ctc.cells(ptr.cpu().numpy(), lab_ptr.cpu().numpy()), 1 << 30))}
+                    "ws_groups": len(hip_ext.groups(8 * ctc.cells(ptr.cpu().numpy(), lab_ptr.cpu().numpy()), 1 << 30))}
             for k in ("hip_nll", "hip_grad", "torch_f32", "torch_f64"):
                 line[k + "_ms"] = stats(times[k]) if times[k] else None
             line["torch_errors"] = errors
