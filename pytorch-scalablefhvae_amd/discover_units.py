@@ -4,17 +4,23 @@ checkpoint (or on the input features, the baseline), one unit per frame (units.p
     python pytorch-scalablefhvae_amd/discover_units.py --checkpoint CK --feat-scp S --len-scp S [--data-format numpy|kaldi]
         [--mvn-path P] --out DIR (--k K | --codebook FILE.npy) [--on z1|feats] [--iters 100] [--tol 1e-4] [--n-init 1] [--seed 0]
         [--batch-size B] [--compute-dtype f32|bf16] [--item FILE [--frame-shift 0.010] [--frame-offset 0.0]]
+        [--segment [--dur-penalty LAMBDA] [--max-seg-frames L] [--boundary-tol 0.020]]
 
   --k K            fit K centroids on this corpus (units.fit: Lloyd's algorithm from K rows drawn with --seed)
   --codebook FILE  apply a (K, width) table fitted elsewhere (units_centroids.npy of another run); the width must match
   --on z1          frames.encode_frames at shift 1: row f is frame f.  --on feats: the normalised input; a width that is no
                    multiple of 16 is zero-padded on the device, one above 128 is an error
   --item FILE      a phone alignment (abx.read_items): cluster purity, phone purity and PNMI of the units against it
+  --segment        also cut every utterance into segments of at most --max-seg-frames frames, one unit each, that minimise the
+                   quantisation error plus --dur-penalty per segment (segment.py)
 
 It writes under --out: units_centroids.npy (K, width), units_counts.npy (K,), units.txt and units_collapsed.txt (one line
 `key u0 u1 ...` per utterance in --feat-scp order; collapsed: runs of equal units merged) and units.json: on, k, frames,
 iterations, converged, inertia, reseeded, seed, bitrate, bitrate_collapsed and, with --item, cluster_purity, phone_purity, pnmi,
-labelled_frames, overlaps and phones.
+labelled_frames, overlaps and phones.  With --segment also segments.item (one item per segment, #phone `u<k>`), segments.txt
+(`key u0 u1 ...`, one unit per segment) and in units.json "segments": dur_penalty, max_seg_frames, segments, mean_frames, cost,
+bitrate_segments and, with --item, precision, recall, f, os, r_value of the boundaries (within --boundary-tol seconds), their
+counts, and cluster_purity, phone_purity, pnmi of the segments' units per frame.  Without --segment nothing changes.
 """
 from __future__ import annotations
 
@@ -47,6 +53,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--item", default=None, metavar="FILE", help="phone alignment to score the units against")
     p.add_argument("--frame-shift", type=float, default=0.010, help="seconds between frames")
     p.add_argument("--frame-offset", type=float, default=0.0, help="time of frame 0 in seconds")
+    p.add_argument("--segment", action="store_true", help="also segment every utterance over the codebook (segment.py)")
+    p.add_argument("--dur-penalty", type=float, default=1.0, metavar="LAMBDA", help="--segment: the penalty per segment")
+    p.add_argument("--max-seg-frames", type=int, default=32, metavar="L", help="--segment: frames per segment, at most (1 .. 64)")
+    p.add_argument("--boundary-tol", type=float, default=0.020, help="--segment with --item: seconds within which a boundary is hit")
     return p
 
 
@@ -61,6 +71,8 @@ def parse_args(argv=None):
         p.error("--seed %d (+ --n-init) must lie in [0, 2^32)" % args.seed)
     if not args.frame_shift > 0:
         p.error("--frame-shift %g must be positive" % args.frame_shift)
+    if not args.dur_penalty >= 0 or not 1 <= args.max_seg_frames <= 64 or not args.boundary_tol >= 0:
+        p.error("--dur-penalty and --boundary-tol must be at least 0 and --max-seg-frames lie in [1, 64]")
     return p, args
 
 
@@ -94,6 +106,12 @@ def main(argv=None) -> int:
         info, cent, counts, seqs = units.discover(rows, width, pool.keys, pool.lengths, args.on, k=args.k, codebook=codebook,
                                                   iters=args.iters, tol=args.tol, n_init=args.n_init, seed=args.seed, items=items,
                                                   frame_shift=args.frame_shift, frame_offset=args.frame_offset)
+        if args.segment:
+            import segment
+
+            info["segments"], segs, seg_items = segment.discover(rows, cent, pool.keys, pool.lengths, args.dur_penalty, args.max_seg_frames,
+                                                                 info["k"], items=items, frame_shift=args.frame_shift,
+                                                                 frame_offset=args.frame_offset, tol=args.boundary_tol)
     except (ValueError, OSError) as e:
         print("discover_units: %s" % e, file=sys.stderr)
         return 1
@@ -105,6 +123,9 @@ def main(argv=None) -> int:
     np.save(os.path.join(args.out, "units_counts.npy"), counts)
     units.write_units(os.path.join(args.out, "units.txt"), pool.keys, seqs)
     units.write_units(os.path.join(args.out, "units_collapsed.txt"), pool.keys, [units.collapse(s) for s in seqs])
+    if args.segment:
+        abx.write_items(os.path.join(args.out, "segments.item"), seg_items)
+        units.write_units(os.path.join(args.out, "segments.txt"), pool.keys, [un for _, un in segs])
     with open(os.path.join(args.out, "units.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps(info))

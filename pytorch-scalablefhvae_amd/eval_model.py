@@ -43,7 +43,9 @@ With --units K (needs --feat-scp data) the frames are turned into discrete units
 fitted on the frame-level z1 and, as the baseline, on the normalised input features (--units-on chooses; --units-iters,
 --units-seed), one unit per frame.  units_<on>.txt holds one line `key u0 u1 ...` per utterance, units_centroids_<on>.npy the
 codebook, and summary.json gains "units": {"z1": {on, k, frames, iterations, converged, inertia, reseeded, seed, bitrate,
-bitrate_collapsed}, "feats": {...}}; with --units-item FILE (a .item phone alignment; the frame grid is --abx-frame-shift /
+bitrate_collapsed}, "feats": {...}}; --units-segment [--units-dur-penalty LAMBDA] [--units-max-seg-frames L] adds the
+duration-penalised segmentation over each codebook (segment.py): segments_<on>.item, segments_<on>.txt (one unit per segment) and
+a "segments" entry in each block; with --units-item FILE (a .item phone alignment; the frame grid is --abx-frame-shift /
 --abx-frame-offset) every sub-block also holds cluster_purity, phone_purity, pnmi, labelled_frames, overlaps and phones.
 
 With --qbe-queries ITEM --qbe-item ITEM (needs --feat-scp data) spoken terms are searched for by example (qbe.py): the queries are
@@ -144,6 +146,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--units-iters", type=int, default=100, help="Lloyd iterations, at most")
     p.add_argument("--units-seed", type=int, default=0, help="seed of the rows the first centroids are copied from")
     p.add_argument("--units-item", default=None, metavar="FILE", help="phone alignment (.item) to score the units against")
+    p.add_argument("--units-segment", action="store_true", help="with --units: segment every utterance over the codebook (segment.py)")
+    p.add_argument("--units-dur-penalty", type=float, default=1.0, metavar="LAMBDA", help="--units-segment: the penalty per segment")
+    p.add_argument("--units-max-seg-frames", type=int, default=32, metavar="L", help="--units-segment: frames per segment, at most (1 .. 64)")
     p.add_argument("--qbe-queries", default=None, metavar="ITEM",
                    help="query-by-example search: the examples (.item, the #phone column is the term) cut from and searched in --feat-scp data")
     p.add_argument("--qbe-item", default=None, metavar="ITEM", help="the term tokens of the corpus the search is scored against")
@@ -202,6 +207,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--units quantises the frames of --feat-scp data: give --feat-scp")
     if args.units is not None and args.units < 1:
         p.error("--units %d must be at least 1" % args.units)
+    if args.units_segment and args.units is None:
+        p.error("--units-segment segments over the codebook of --units: give --units K")
+    if not args.units_dur_penalty >= 0 or not 1 <= args.units_max_seg_frames <= 64:
+        p.error("--units-dur-penalty must be at least 0 and --units-max-seg-frames lie in [1, 64]")
     if args.units_iters < 1:
         p.error("--units-iters %d must be at least 1" % args.units_iters)
     if args.units_seed < 0 or args.units_seed >= 2 ** 32:
@@ -408,6 +417,14 @@ def discover_units(args, model, T, out_dir, dev):
                                              frame_offset=args.abx_frame_offset)
         np.save(os.path.join(out_dir, "units_centroids_%s.npy" % on), cent)
         units.write_units(os.path.join(out_dir, "units_%s.txt" % on), pool.keys, seqs)
+        if args.units_segment:
+            import segment
+
+            info["segments"], segs, seg_items = segment.discover(rows, cent, pool.keys, pool.lengths, args.units_dur_penalty,
+                                                                 args.units_max_seg_frames, info["k"], items=items,
+                                                                 frame_shift=args.abx_frame_shift, frame_offset=args.abx_frame_offset)
+            abx.write_items(os.path.join(out_dir, "segments_%s.item" % on), seg_items)
+            units.write_units(os.path.join(out_dir, "segments_%s.txt" % on), pool.keys, [un for _, un in segs])
         block[on] = info
         del rows
     return block
