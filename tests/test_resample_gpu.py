@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import audio_compare
 import feats_ref
 import resample_ref as R
 from test_resample_cpu import PAIRS, speechlike
@@ -62,15 +63,11 @@ def _batch(F, sr_in, sr_out):
 
 def _units(got, y, sr_in, sr_out, terms):
     want, cond, taps = R.resample(y, sr_in, sr_out)
-    assert got.dtype == np.float32 and got.shape == want.shape
-    u = 2.0 ** -24 * cond
-    err = np.abs(got.astype(np.float64) - want)
-    hard = (terms + 2) * u
-    assert np.all(err <= hard), "worst |got - want| / bound = %g" % (err[hard > 0] / hard[hard > 0]).max()
+    # |got - want| <= (terms + 2) u per element (the comparator all audio kernels share; derivation in its docstring)
+    units = audio_compare.dense_units(got, want, 2.0 ** -24 * cond, terms, c=2, what="resample %d -> %d" % (sr_in, sr_out))
     n_calc = R.lengths(len(y), sr_in, sr_out)[0]
     assert not got[n_calc:].any()  # librosa's zero tail past resampy's int(n * ratio)
-    m = u > 0
-    return err[m] / u[m]
+    return units
 
 
 @pytest.mark.parametrize("sr_in,sr_out", PAIRS)
