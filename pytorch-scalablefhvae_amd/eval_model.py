@@ -23,6 +23,11 @@ speaker verification (verification.py): every sequence against every other by th
 as the control, of their z1_mean (the mean of the sequence's segments' z1_mu); summary.json gains "speaker_verification" with the
 equal error rate of both, and sv_hist_mu2.npy / sv_hist_z1_mean.npy hold the (2, --sv-bins) target / non-target score histograms
 (a DET curve can be drawn from them).  A factorized model gives a low EER on mu2 and a high one on z1_mean.
+With --sv-backend lda and / or plda (spk_backend.py; --sv-train-feat-scp / --sv-train-len-scp name the training sequences, whose
+speakers follow the same --utt2spk / --spk-key-sep rule; --sv-lda-dim K, --sv-plda-iters N, --sv-no-length-norm) a back end is
+trained on the training sequences' embeddings and both entries gain "lda" (the cosine after the LDA) and / or "plda" (the PLDA
+log-likelihood ratio): eer, threshold, min_dcf, crossing_mass, n_target, n_nontarget, lo, hi; sv_hist_<name>_<backend>.npy and
+sv_backend_<name>.npz are written.  Without it, or with cosine alone, every output is what it was.
 
 With --tsne (needs --feat-scp data; --tsne-perplexity, --tsne-iters, --tsne-seed) the same two embeddings are also drawn: exact
 t-SNE maps (tsne.py) go to tsne_mu2.npy and tsne_z1_mean.npy, both (sequences, 2), and to tsne.tsv, one line per sequence: the
@@ -130,6 +135,14 @@ def build_parser() -> argparse.ArgumentParser:
     spk.add_argument("--spk-key-sep", default=None,
                      help="speaker verification: the speaker is the sequence key up to the first SEP (needs --feat-scp)")
     p.add_argument("--sv-bins", type=int, default=4096, help="score bins of the verification histograms (a power of two, 64..8192)")
+    p.add_argument("--sv-backend", nargs="+", default=None, choices=["cosine", "lda", "plda"],
+                   help="speaker verification: besides the raw cosine, score after an LDA (lda) and by a PLDA log-likelihood ratio (plda) "
+                        "trained on the sequences of --sv-train-feat-scp (spk_backend.py)")
+    p.add_argument("--sv-train-feat-scp", default=None, metavar="SCP", help="--sv-backend lda / plda: the training sequences (same format as --feat-scp)")
+    p.add_argument("--sv-train-len-scp", default=None, metavar="SCP")
+    p.add_argument("--sv-lda-dim", type=int, default=None, metavar="K", help="columns the LDA keeps (needed by lda; plda alone: no LDA in front)")
+    p.add_argument("--sv-plda-iters", type=int, default=10, metavar="N", help="EM iterations of the PLDA")
+    p.add_argument("--sv-no-length-norm", action="store_true", help="no length normalisation between the LDA and the PLDA")
     p.add_argument("--tsne", action="store_true", help="write exact t-SNE maps of mu2 and of the sequences' mean z1 (needs --feat-scp)")
     p.add_argument("--tsne-perplexity", type=float, default=30.0, help="at most (sequences - 1) / 3")
     p.add_argument("--tsne-iters", type=int, default=1000)
@@ -189,6 +202,19 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--utt2spk / --spk-key-sep name the speakers of --feat-scp data: give --feat-scp")
     if args.sv_bins < 64 or args.sv_bins > 8192 or args.sv_bins & (args.sv_bins - 1):
         p.error("--sv-bins %d must be a power of two in [64, 8192]" % args.sv_bins)
+    args.sv_trained = [b for b in ("lda", "plda") if b in (args.sv_backend or [])]
+    if args.sv_trained:
+        if args.utt2spk is None and args.spk_key_sep is None:
+            p.error("--sv-backend scores the trials of --utt2spk / --spk-key-sep: give one of them")
+        if args.sv_train_feat_scp is None or args.sv_train_len_scp is None:
+            p.error("--sv-backend %s is trained on --sv-train-feat-scp / --sv-train-len-scp: give both" % " ".join(args.sv_trained))
+        if "lda" in args.sv_trained and args.sv_lda_dim is None:
+            p.error("--sv-backend lda needs --sv-lda-dim")
+        if (args.sv_lda_dim is not None and args.sv_lda_dim < 1) or args.sv_plda_iters < 0:
+            p.error("--sv-lda-dim must be at least 1 and --sv-plda-iters not negative")
+    elif (args.sv_train_feat_scp is not None or args.sv_train_len_scp is not None or args.sv_lda_dim is not None or args.sv_plda_iters != 10
+          or args.sv_no_length_norm):
+        p.error("--sv-train-feat-scp, --sv-train-len-scp, --sv-lda-dim, --sv-plda-iters and --sv-no-length-norm need --sv-backend lda or plda")
     if args.tsne and args.feat_scp is None:
         p.error("--tsne draws the sequences of --feat-scp data: give --feat-scp")
     if not args.tsne_perplexity >= 1.0:
@@ -280,9 +306,34 @@ def sequence_means(z1_mu, seq_pos, n, dev):
     return z1_sum / count.clamp(min=1.0).unsqueeze(1)
 
 
-def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
+def sv_train_embeddings(args, model, T, dev):
+    """--sv-train-feat-scp / --sv-train-len-scp: the training sequences through the model -> (keys, {"mu2": (n, D) numpy, "z1_mean":
+    (n, D) numpy}), the embeddings verify_speakers scores, of the sequences the back end is trained on."""
+    import utils
+    from datasets import KaldiDataset, NumpyDataset, ResidentSegmentPool
+
+    Dataset = NumpyDataset if args.data_format == "numpy" else KaldiDataset
+    ds = Dataset(args.sv_train_feat_scp, args.sv_train_len_scp, args.min_len if args.min_len is not None else T, args.mvn_path, T,
+                 args.seg_shift, False)
+    pool = ResidentSegmentPool(ds, dev)
+    z1s, ids = [], []
+    with torch.no_grad():
+        for idxs, x, _ in pool.epoch(args.batch_size, shuffle=False):
+            z1s.append(model.encode(x)[0].cpu().numpy()), ids.append(torch.as_tensor(idxs).cpu().numpy())
+        mu2 = utils.estimate_mu2_dict(model, pool.epoch(args.batch_size, shuffle=False), len(ds))
+    seqs = sorted(mu2)
+    if not seqs:
+        raise ValueError("%s holds no sequence long enough" % args.sv_train_feat_scp)
+    seq_pos = np.searchsorted(np.asarray(seqs, dtype=np.int64), np.concatenate(ids).astype(np.int64))
+    z1_mean = sequence_means(np.concatenate(z1s), seq_pos, len(seqs), dev).cpu().numpy()
+    return [ds.seq_keys[y] for y in seqs], {"mu2": np.stack([mu2[y].cpu().numpy() for y in seqs]), "z1_mean": z1_mean}
+
+
+def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev, train=None):
     """--utt2spk / --spk-key-sep: the "speaker_verification" block of summary.json (see the module docstring).  keys: the key of
-    every row of mu2_rows; z1_mu (segments, D) with seq_pos the row each segment belongs to."""
+    every row of mu2_rows; z1_mu (segments, D) with seq_pos the row each segment belongs to.  train: sv_train_embeddings' pair
+    for --sv-backend lda / plda: every embedding's entry gains "lda" / "plda" (spk_backend.Backend.score_all_pairs' figures), and
+    sv_hist_<name>_<backend>.npy and sv_backend_<name>.npz are written."""
     import verification as V
 
     labels, n_spk = V.labels_from_speakers(speakers_of(args, keys))
@@ -292,6 +343,16 @@ def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev):
         r = V.speaker_verification(emb, labels, n_bins=args.sv_bins, device=dev)
         np.save(os.path.join(out_dir, "sv_hist_%s.npy" % name), r.pop("hist"))
         block[name] = r
+        if train is not None:
+            import spk_backend as SB
+
+            train_labels, _ = V.labels_from_speakers(speakers_of(args, train[0]))
+            backend = SB.fit(train[1][name], train_labels, args.sv_lda_dim, not args.sv_no_length_norm, args.sv_plda_iters)
+            for b in args.sv_trained:
+                rb = backend.score_all_pairs(emb, labels, n_bins=args.sv_bins, backend=b, device=dev)
+                np.save(os.path.join(out_dir, "sv_hist_%s_%s.npy" % (name, b)), rb.pop("hist"))
+                r[b] = rb
+            backend.save(os.path.join(out_dir, "sv_backend_%s.npz" % name))
     block.update({"speakers": n_spk, "unlabelled": int((labels < 0).sum()), "bins": args.sv_bins})
     return block
 
@@ -667,7 +728,8 @@ def main(argv=None) -> int:
     if args.utt2spk is not None or args.spk_key_sep is not None:
         seq_pos = np.searchsorted(np.asarray(seqs, dtype=np.int64), np.concatenate(ids).astype(np.int64))  # (mu2 covers every segment's sequence)
         try:
-            sv = verify_speakers(args, [ds.seq_keys[y] for y in seqs], mu2_rows, np.concatenate(z1s), seq_pos, args.out, dev)
+            train = sv_train_embeddings(args, model, T, dev) if args.sv_trained else None
+            sv = verify_speakers(args, [ds.seq_keys[y] for y in seqs], mu2_rows, np.concatenate(z1s), seq_pos, args.out, dev, train)
         except (ValueError, OSError) as e:
             print("speaker verification: %s" % e, file=sys.stderr)
             return 1
