@@ -7,7 +7,7 @@ archive as the papers' baseline.
         --backend cosine lda plda [--lda-dim K] [--no-length-norm] [--plda-iters 10] [--model FILE.npz] [--trials FILE]
         [--bins 4096] --out DIR
 
-An archive is a directory with mu2.npy + keys.txt, a directory with feats.scp (what extract_latents.py --out-format kaldi
+An archive is a directory with mu2.npy + keys.txt (or ivectors.npy + keys.txt, what extract_ivectors.py writes), a directory with feats.scp (what extract_latents.py --out-format kaldi
 writes: one-row matrices), or an scp file whose entries are one-row matrices or vectors.  --utt2spk / --spk-key-sep name the
 speakers of both archives.  --trials lines are `<enrol-key> <test-key> target|nontarget` over the evaluation archive.
 
@@ -39,6 +39,14 @@ def read_archive(path):
                 keys = [line.strip() for line in fh if line.strip()]
             if rows.ndim != 2 or rows.shape[0] != len(keys):
                 raise ValueError("%s: mu2.npy has shape %s, keys.txt %d keys" % (path, rows.shape, len(keys)))
+            return _unique(path, keys), np.ascontiguousarray(rows, dtype=np.float32)
+        ivec = os.path.join(path, "ivectors.npy")  # (what extract_ivectors.py writes)
+        if os.path.exists(ivec) and os.path.exists(txt):
+            rows = np.load(ivec)
+            with open(txt) as fh:
+                keys = [line.strip() for line in fh if line.strip()]
+            if rows.ndim != 2 or rows.shape[0] != len(keys):
+                raise ValueError("%s: ivectors.npy has shape %s, keys.txt %d keys" % (path, rows.shape, len(keys)))
             return _unique(path, keys), np.ascontiguousarray(rows, dtype=np.float32)
         if not os.path.exists(scp):
             raise ValueError("%s: neither mu2.npy + keys.txt nor feats.scp" % path)
