@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libfhvae_hip.so")
-SOURCES = ["gemm.hip", "lstm.hip", "lstm_cluster.hip", "lstm_bwd_rs.hip", "lstm_fwd_wr.hip", "proj.hip", "loss.hip", "disc.hip", "disc_mfma.hip", "data.hip", "trace.hip", "wgrad.hip", "disc_lp.hip", "lstm_cell.hip", "hs.hip", "feats.hip", "synth.hip", "resample.hip", "melinv.hip", "kaldi_fbank.hip", "kaldi_cm.hip", "flac.hip", "sv.hip", "tsne.hip", "frames.hip", "vad.hip", "abx.hip", "kmeans.hip", "kaldi_post.hip", "qbe.hip", "gmm.hip", "probe.hip", "viterbi.hip", "ctc.hip", "falign.hip", "ctcbeam.hip", "segment.hip", "spk.hip", "ivector.hip"]
+SOURCES = ["gemm.hip", "lstm.hip", "lstm_cluster.hip", "lstm_bwd_rs.hip", "lstm_fwd_wr.hip", "proj.hip", "loss.hip", "disc.hip", "disc_mfma.hip", "data.hip", "trace.hip", "wgrad.hip", "disc_lp.hip", "lstm_cell.hip", "hs.hip", "feats.hip", "synth.hip", "resample.hip", "melinv.hip", "kaldi_fbank.hip", "kaldi_cm.hip", "flac.hip", "sv.hip", "tsne.hip", "frames.hip", "vad.hip", "abx.hip", "kmeans.hip", "kaldi_post.hip", "qbe.hip", "gmm.hip", "probe.hip", "viterbi.hip", "ctc.hip", "falign.hip", "ctcbeam.hip", "segment.hip", "spk.hip", "ivector.hip", "snorm.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results stay in VGPRs.  By default the backend puts accumulators in AGPRs and copies them
 # around every non-MFMA use (v_accvgpr_read/write, 4 issue cycles each): 288 such moves in the long-K GEMM's loop, none with
 # this form; measured 791 -> 810 k segments/s at B=2048, 275 -> 284 k at B=256.
@@ -38,6 +38,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", 
 # spk.hip: its chains are the explicit fmaf of include/fhvae_spk.h, every other f32 operation is rounded once, and its one division
 # and its square roots are correctly rounded (the row transform's length normalisation), as kaldi_post.hip
 # ivector.hip: its f32 and float64 sums and its explicit fma chains are the expressions of include/fhvae_ivector.h, as gmm.hip
+# snorm.hip: its f32 additions, its float64 sums and its one f32 division are the expressions of include/fhvae_snorm.h, one rounding
+# each, as spk.hip (which holds the normalised score itself)
 EXTRA_FLAGS = {"kaldi_cm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
                "sv.hip": ["-fhip-fp32-correctly-rounded-divide-sqrt"],
                "frames.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
@@ -54,7 +56,8 @@ EXTRA_FLAGS = {"kaldi_cm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-round
                "ctcbeam.hip": ["-ffp-contract=off"],
                "segment.hip": ["-ffp-contract=off"],
                "spk.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
-               "ivector.hip": ["-ffp-contract=off"]}
+               "ivector.hip": ["-ffp-contract=off"],
+               "snorm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 
 
 def _newer(a, b):
@@ -63,7 +66,7 @@ def _newer(a, b):
 
 def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("fhvae_hip.h", "fhvae_frames.h", "fhvae_vad.h", "fhvae_abx.h", "fhvae_kmeans.h", "fhvae_kaldi_post.h", "fhvae_qbe.h", "fhvae_gmm.h", "fhvae_probe.h", "fhvae_viterbi.h", "fhvae_ctc.h", "fhvae_falign.h", "fhvae_ctcbeam.h", "fhvae_segment.h", "fhvae_spk.h", "fhvae_ivector.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("fhvae_hip.h", "fhvae_frames.h", "fhvae_vad.h", "fhvae_abx.h", "fhvae_kmeans.h", "fhvae_kaldi_post.h", "fhvae_qbe.h", "fhvae_gmm.h", "fhvae_probe.h", "fhvae_viterbi.h", "fhvae_ctc.h", "fhvae_falign.h", "fhvae_ctcbeam.h", "fhvae_segment.h", "fhvae_spk.h", "fhvae_ivector.h", "fhvae_snorm.h")]
     return hdrs
 
 

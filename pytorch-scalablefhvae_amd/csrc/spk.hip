@@ -11,6 +11,9 @@
 //   HistEpi    turns a score into a bin (one subtraction, one product: no division) and counts it in a per-workgroup LDS
 //              histogram (ds_add_u32), flushed with vector 64-bit global atomic adds as sv_hist_kernel does
 // Both results are free of any order of arrival (a minimum in a total order, integer counts).
+// What a trial's score is, is a second policy: LlrScore, the s above (the default), or NormScore, the normalised score of
+// include/fhvae_snorm.h, sn = 0.5 ((s - mu_i) r_i + (s - mu_j) r_j), with mu and r of the stationary rows in registers and of
+// the streamed rows beside ya / yl in LDS.
 //
 // Symmetry, bit for bit: the dot is symmetric (allpairs_f32.h, THE ORDER) and a[i] + a[j] commutes.
 // The file is built with -ffp-contract=off (every f32 operation below is rounded once unless it is written fmaf) and with
@@ -20,6 +23,7 @@
 
 #include "allpairs_f32.h"
 
+#include "../../include/fhvae_snorm.h"
 #include "../../include/fhvae_spk.h"
 
 namespace fh {
@@ -49,6 +53,8 @@ struct SpkArgs {
   int64_t ld;
   float c, lo, scale;
   int S, NB, chunk;
+  const float* mu;  // NormScore: (S)
+  const float* r;   // NormScore: (S)
 };
 
 struct RangeEpi {
@@ -101,15 +107,52 @@ struct HistEpi {
   }
 };
 
+// the plain score: nothing beside the tile, nothing in registers
+struct LlrScore {
+  static constexpr int kSide = 0;  // bytes of LDS per streamed row
+  __device__ __forceinline__ LlrScore(const SpkArgs&, int, float*) {}
+  __device__ __forceinline__ void side(const SpkArgs&, int, int, int) {}
+  __device__ __forceinline__ void block(int, int) {}
+  __device__ __forceinline__ float operator()(float s, int, int) const { return s; }
+};
+
+struct NormScore {
+  static constexpr int kSide = 8;
+  float xmu[4], xr[4], ymur[4], yrr[4];
+  float *ymu, *yr;  // [YT] each
+  __device__ __forceinline__ NormScore(const SpkArgs& a, int x0, float* lds) : ymu(lds), yr(lds + kSpkYT) {
+    const int i = threadIdx.x & 15;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int x = x0 + t * 16 + i;
+      xmu[t] = x < a.S ? a.mu[x] : 0.f;
+      xr[t] = x < a.S ? a.r[x] : 0.f;
+    }
+  }
+  __device__ __forceinline__ void side(const SpkArgs& a, int tid, int y, int y_end) {
+    ymu[tid] = y < y_end ? a.mu[y] : 0.f;
+    yr[tid] = y < y_end ? a.r[y] : 0.f;
+  }
+  __device__ __forceinline__ void block(int yb, int g) {
+    const float4 m = *(const float4*)(ymu + yb * 16 + 4 * g), q = *(const float4*)(yr + yb * 16 + 4 * g);
+    ymur[0] = m.x, ymur[1] = m.y, ymur[2] = m.z, ymur[3] = m.w;
+    yrr[0] = q.x, yrr[1] = q.y, yrr[2] = q.z, yrr[3] = q.w;
+  }
+  __device__ __forceinline__ float operator()(float s, int t, int r) const {
+    return 0.5f * ((s - xmu[t]) * xr[t] + (s - ymur[r]) * yrr[r]);
+  }
+};
+
 // (D > 96: 128 and more registers of stationary fragments; two workgroups per CU would spill -- as sv_hist_kernel)
-template <int D, class Epi>
+template <int D, class Epi, class Score = LlrScore>
 __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a) {
   constexpr int YT = kSpkYT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ytile = smem;                        // [YT][D] f32, swizzled
   float* ya = (float*)(smem + YT * D * 4);   // [YT]
   int* yl = (int*)(ya + YT);                 // [YT]
-  unsigned* h = (unsigned*)(yl + YT);        // HistEpi: [2][NB]
+  float* ys = (float*)(yl + YT);             // Score: [YT] per array of its own
+  unsigned* h = (unsigned*)((char*)ys + YT * Score::kSide);  // HistEpi: [2][NB]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, i = lane & 15;
@@ -122,6 +165,7 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a)
   const float c = a.c;
 
   Epi epi(a, h);
+  Score score(a, x0, ys);
   bool nan = false;
 
   uint4 xf[4][D / 16];
@@ -142,6 +186,7 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a)
           const int y = y0 + tid;
           ya[tid] = y < y_end ? a.a[y] : 0.f;
           yl[tid] = y < y_end ? a.label[y] : -1;
+          score.side(a, tid, y, y_end);
         }
       },
       // a block whose every j <= every i of this wave is skipped; the few blocks that straddle the diagonal are computed whole
@@ -152,6 +197,7 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a)
         const int4 ylv = *(const int4*)(yl + yb * 16 + 4 * g);
         const float yar[4] = {yav.x, yav.y, yav.z, yav.w};
         const int ylr[4] = {ylv.x, ylv.y, ylv.z, ylv.w};
+        score.block(yb, g);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int x = x0 + t * 16 + i;
@@ -159,7 +205,7 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a)
           for (int r = 0; r < 4; ++r) {
             const int y = y0 + yb * 16 + 4 * g + r;
             if (xl[t] >= 0 && ylr[r] >= 0 && x < y) {
-              const float s = (acc[t][r] + (xa[t] + yar[r])) + c;
+              const float s = score((acc[t][r] + (xa[t] + yar[r])) + c, t, r);
               if (s != s)
                 nan = true;
               else
@@ -173,21 +219,21 @@ __global__ __launch_bounds__(256, D > 96 ? 1 : 2) void spk_llr_kernel(SpkArgs a)
   if (nan) atomicOr(a.status, (int32_t)FHVAE_SPK_NAN);
 }
 
-template <int D, class Epi>
+template <int D, class Epi, class Score>
 int spk_launch(const SpkArgs& a, dim3 grid, hipStream_t st) {
-  const int smem = kSpkYT * D * 4 + kSpkYT * 8 + (Epi::kHist ? 2 * a.NB * 4 : 0);
-  hipError_t e = hipFuncSetAttribute((const void*)spk_llr_kernel<D, Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  const int smem = kSpkYT * D * 4 + kSpkYT * (8 + Score::kSide) + (Epi::kHist ? 2 * a.NB * 4 : 0);
+  hipError_t e = hipFuncSetAttribute((const void*)spk_llr_kernel<D, Epi, Score>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((spk_llr_kernel<D, Epi>), grid, dim3(256), (size_t)smem, st, a);
+  hipLaunchKernelGGL((spk_llr_kernel<D, Epi, Score>), grid, dim3(256), (size_t)smem, st, a);
   return fh_launch_status();
 }
 
-template <class Epi>
+template <class Epi, class Score = LlrScore>
 int spk_pairs(SpkArgs a, int64_t D, hipStream_t st) {
   const int64_t nxb = fh_cdiv(a.S, 256);
   a.chunk = (int)fh_allpairs_chunk(a.S, std::max<int64_t>(1, kSpkWorkgroups / nxb), kSpkMinChunk);
   dim3 grid((unsigned)fh_cdiv(a.S, a.chunk), (unsigned)nxb);
-  return fh_allpairs_dispatch(D, [&](auto d) { return spk_launch<decltype(d)::value, Epi>(a, grid, st); });
+  return fh_allpairs_dispatch(D, [&](auto d) { return spk_launch<decltype(d)::value, Epi, Score>(a, grid, st); });
 }
 
 __global__ void spk_range_init_kernel(unsigned* keys) {
@@ -239,8 +285,11 @@ __global__ __launch_bounds__(64) void spk_project_kernel(const float* __restrict
   if (q != nullptr) a[s] = -qa;
 }
 
+// kNorm: the normalised score of include/fhvae_snorm.h from mu, r (S); else the plain one (mu, r unused)
+template <bool kNorm>
 __global__ void spk_trials_kernel(const float* __restrict__ v, int64_t ld, const float* __restrict__ a, int S, int D, float c,
-                                  const int32_t* __restrict__ pairs, int64_t n, float* __restrict__ out, int32_t* status) {
+                                  const int32_t* __restrict__ pairs, int64_t n, float* __restrict__ out, int32_t* status,
+                                  const float* __restrict__ mu, const float* __restrict__ r) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const int i = pairs[2 * t], j = pairs[2 * t + 1];
@@ -253,13 +302,14 @@ __global__ void spk_trials_kernel(const float* __restrict__ v, int64_t ld, const
   const float* vj = v + (int64_t)j * ld;
   float acc = 0.f;
   for (int d = 0; d < D; d += 4) {
-    const float4 p = *(const float4*)(vi + d), r = *(const float4*)(vj + d);
-    acc = __builtin_fmaf(p.x, r.x, acc);
-    acc = __builtin_fmaf(p.y, r.y, acc);
-    acc = __builtin_fmaf(p.z, r.z, acc);
-    acc = __builtin_fmaf(p.w, r.w, acc);
+    const float4 p = *(const float4*)(vi + d), q = *(const float4*)(vj + d);
+    acc = __builtin_fmaf(p.x, q.x, acc);
+    acc = __builtin_fmaf(p.y, q.y, acc);
+    acc = __builtin_fmaf(p.z, q.z, acc);
+    acc = __builtin_fmaf(p.w, q.w, acc);
   }
-  out[t] = (acc + (a[i] + a[j])) + c;
+  const float s = (acc + (a[i] + a[j])) + c;
+  out[t] = kNorm ? 0.5f * ((s - mu[i]) * r[i] + (s - mu[j]) * r[j]) : s;
 }
 
 // what the three scoring calls check alike
@@ -305,9 +355,14 @@ extern "C" int fhvae_spk_project(const float* x, int64_t ldx, int64_t S, int64_t
   return fh_launch_status();
 }
 
-extern "C" int fhvae_spk_llr_range(const float* v, int64_t ld, const float* a, const int32_t* label, int64_t S, int64_t D, float c,
-                                   void* ws, int64_t ws_bytes, float* range, int32_t* status, void* stream) {
-  using namespace fh;
+namespace fh {
+
+namespace {
+
+// the three scoring calls, shared by the plain score (mu = r = nullptr) and the normalised one
+template <class Score>
+int spk_range_call(const float* v, int64_t ld, const float* a, const float* mu, const float* r, const int32_t* label, int64_t S, int64_t D,
+                   float c, void* ws, int64_t ws_bytes, float* range, int32_t* status, void* stream) {
   FH_CHECK_PTR(label);
   FH_CHECK_PTR(ws);
   FH_CHECK_PTR(range);
@@ -325,20 +380,22 @@ extern "C" int fhvae_spk_llr_range(const float* v, int64_t ld, const float* a, c
   g.ld = ld;
   g.c = c;
   g.S = (int)S;
+  g.mu = mu;
+  g.r = r;
   hipLaunchKernelGGL(spk_range_init_kernel, dim3(1), dim3(64), 0, st, g.keys);
   rc = fh_launch_status();
   if (rc != FHVAE_OK) return rc;
   if (S > 1) {  // (one row: no trial)
-    rc = spk_pairs<RangeEpi>(g, D, st);
+    rc = spk_pairs<RangeEpi, Score>(g, D, st);
     if (rc != FHVAE_OK) return rc;
   }
   hipLaunchKernelGGL(spk_range_done_kernel, dim3(1), dim3(64), 0, st, g.keys, range);
   return fh_launch_status();
 }
 
-extern "C" int fhvae_spk_llr_hist(const float* v, int64_t ld, const float* a, const int32_t* label, int64_t S, int64_t D, float c,
-                                  float lo, float hi, int64_t n_bins, uint64_t* hist, int32_t* status, void* stream) {
-  using namespace fh;
+template <class Score>
+int spk_hist_call(const float* v, int64_t ld, const float* a, const float* mu, const float* r, const int32_t* label, int64_t S, int64_t D,
+                  float c, float lo, float hi, int64_t n_bins, uint64_t* hist, int32_t* status, void* stream) {
   FH_CHECK_PTR(label);
   FH_CHECK_PTR(hist);
   int rc = spk_check(v, ld, a, S, D, status);
@@ -362,12 +419,14 @@ extern "C" int fhvae_spk_llr_hist(const float* v, int64_t ld, const float* a, co
   g.scale = hi == lo ? 0.f : (float)n_bins / (hi - lo);
   g.S = (int)S;
   g.NB = (int)n_bins;
-  return spk_pairs<HistEpi>(g, D, st);
+  g.mu = mu;
+  g.r = r;
+  return spk_pairs<HistEpi, Score>(g, D, st);
 }
 
-extern "C" int fhvae_spk_llr_trials(const float* v, int64_t ld, const float* a, int64_t S, int64_t D, float c, const int32_t* pairs,
-                                    int64_t n, float* out, int32_t* status, void* stream) {
-  using namespace fh;
+template <bool kNorm>
+int spk_trials_call(const float* v, int64_t ld, const float* a, const float* mu, const float* r, int64_t S, int64_t D, float c,
+                    const int32_t* pairs, int64_t n, float* out, int32_t* status, void* stream) {
   FH_CHECK_PTR(pairs);
   FH_CHECK_PTR(out);
   int rc = spk_check(v, ld, a, S, D, status);
@@ -375,7 +434,61 @@ extern "C" int fhvae_spk_llr_trials(const float* v, int64_t ld, const float* a, 
   FH_CHECK_POS(n);
   if ((((uintptr_t)pairs | (uintptr_t)out) & 3) != 0) return FHVAE_ERR_ALIGN;
   FH_CHECK_I32(n);
-  hipLaunchKernelGGL(spk_trials_kernel, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, v, ld, a, (int)S, (int)D, c, pairs,
-                     n, out, status);
+  hipLaunchKernelGGL(spk_trials_kernel<kNorm>, dim3((unsigned)fh_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, v, ld, a, (int)S, (int)D, c,
+                     pairs, n, out, status, mu, r);
   return fh_launch_status();
+}
+
+// mu and r of the normalised calls: given, 4-byte aligned
+int sn_check(const float* mu, const float* r) {
+  FH_CHECK_PTR(mu);
+  FH_CHECK_PTR(r);
+  return (((uintptr_t)mu | (uintptr_t)r) & 3) != 0 ? FHVAE_ERR_ALIGN : FHVAE_OK;
+}
+
+}  // namespace
+
+}  // namespace fh
+
+extern "C" int fhvae_spk_llr_range(const float* v, int64_t ld, const float* a, const int32_t* label, int64_t S, int64_t D, float c,
+                                   void* ws, int64_t ws_bytes, float* range, int32_t* status, void* stream) {
+  return fh::spk_range_call<fh::LlrScore>(v, ld, a, nullptr, nullptr, label, S, D, c, ws, ws_bytes, range, status, stream);
+}
+
+extern "C" int fhvae_spk_llr_hist(const float* v, int64_t ld, const float* a, const int32_t* label, int64_t S, int64_t D, float c,
+                                  float lo, float hi, int64_t n_bins, uint64_t* hist, int32_t* status, void* stream) {
+  return fh::spk_hist_call<fh::LlrScore>(v, ld, a, nullptr, nullptr, label, S, D, c, lo, hi, n_bins, hist, status, stream);
+}
+
+extern "C" int fhvae_spk_llr_trials(const float* v, int64_t ld, const float* a, int64_t S, int64_t D, float c, const int32_t* pairs,
+                                    int64_t n, float* out, int32_t* status, void* stream) {
+  return fh::spk_trials_call<false>(v, ld, a, nullptr, nullptr, S, D, c, pairs, n, out, status, stream);
+}
+
+// ---- include/fhvae_snorm.h: the same three with the normalised score (its status bits are this file's, value for value)
+static_assert((int)FHVAE_SN_NAN == (int)FHVAE_SPK_NAN && (int)FHVAE_SN_BAD_INDEX == (int)FHVAE_SPK_BAD_INDEX &&
+                  FHVAE_SN_MAX_ROWS == FHVAE_SPK_MAX_ROWS,
+              "fhvae_snorm.h mirrors fhvae_spk.h");
+
+extern "C" int64_t fhvae_sn_ws_bytes(int64_t S, int64_t D) { return fhvae_spk_ws_bytes(S, D); }
+
+extern "C" int fhvae_sn_range(const float* v, int64_t ld, const float* a, const float* mu, const float* r, const int32_t* label, int64_t S,
+                              int64_t D, float c, void* ws, int64_t ws_bytes, float* range, int32_t* status, void* stream) {
+  const int rc = fh::sn_check(mu, r);
+  if (rc != FHVAE_OK) return rc;
+  return fh::spk_range_call<fh::NormScore>(v, ld, a, mu, r, label, S, D, c, ws, ws_bytes, range, status, stream);
+}
+
+extern "C" int fhvae_sn_hist(const float* v, int64_t ld, const float* a, const float* mu, const float* r, const int32_t* label, int64_t S,
+                             int64_t D, float c, float lo, float hi, int64_t n_bins, uint64_t* hist, int32_t* status, void* stream) {
+  const int rc = fh::sn_check(mu, r);
+  if (rc != FHVAE_OK) return rc;
+  return fh::spk_hist_call<fh::NormScore>(v, ld, a, mu, r, label, S, D, c, lo, hi, n_bins, hist, status, stream);
+}
+
+extern "C" int fhvae_sn_trials(const float* v, int64_t ld, const float* a, const float* mu, const float* r, int64_t S, int64_t D, float c,
+                               const int32_t* pairs, int64_t n, float* out, int32_t* status, void* stream) {
+  const int rc = fh::sn_check(mu, r);
+  if (rc != FHVAE_OK) return rc;
+  return fh::spk_trials_call<true>(v, ld, a, mu, r, S, D, c, pairs, n, out, status, stream);
 }

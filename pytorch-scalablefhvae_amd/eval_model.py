@@ -28,6 +28,9 @@ speakers follow the same --utt2spk / --spk-key-sep rule; --sv-lda-dim K, --sv-pl
 trained on the training sequences' embeddings and both entries gain "lda" (the cosine after the LDA) and / or "plda" (the PLDA
 log-likelihood ratio): eer, threshold, min_dcf, crossing_mass, n_target, n_nontarget, lo, hi; sv_hist_<name>_<backend>.npy and
 sv_backend_<name>.npz are written.  Without it, or with cosine alone, every output is what it was.
+With --sv-snorm (and a trained back end) each of these entries gains a "snorm" block: the same scores normalised against the
+speakers' means of the training sequences, adaptive S-norm with the --sv-snorm-top largest cohort scores (score_norm.py; 0: the
+whole cohort), and sv_hist_<name>_<backend>_snorm.npy.
 
 With --tsne (needs --feat-scp data; --tsne-perplexity, --tsne-iters, --tsne-seed) the same two embeddings are also drawn: exact
 t-SNE maps (tsne.py) go to tsne_mu2.npy and tsne_z1_mean.npy, both (sequences, 2), and to tsne.tsv, one line per sequence: the
@@ -143,6 +146,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sv-lda-dim", type=int, default=None, metavar="K", help="columns the LDA keeps (needed by lda; plda alone: no LDA in front)")
     p.add_argument("--sv-plda-iters", type=int, default=10, metavar="N", help="EM iterations of the PLDA")
     p.add_argument("--sv-no-length-norm", action="store_true", help="no length normalisation between the LDA and the PLDA")
+    p.add_argument("--sv-snorm", action="store_true", help="--sv-backend lda / plda: also the scores normalised against the training speakers' means")
+    p.add_argument("--sv-snorm-top", type=int, default=200, metavar="K", help="cohort scores kept per side (0: the whole cohort)")
     p.add_argument("--tsne", action="store_true", help="write exact t-SNE maps of mu2 and of the sequences' mean z1 (needs --feat-scp)")
     p.add_argument("--tsne-perplexity", type=float, default=30.0, help="at most (sequences - 1) / 3")
     p.add_argument("--tsne-iters", type=int, default=1000)
@@ -212,9 +217,13 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error("--sv-backend lda needs --sv-lda-dim")
         if (args.sv_lda_dim is not None and args.sv_lda_dim < 1) or args.sv_plda_iters < 0:
             p.error("--sv-lda-dim must be at least 1 and --sv-plda-iters not negative")
+        if args.sv_snorm_top < 0:
+            p.error("--sv-snorm-top %d must not be negative" % args.sv_snorm_top)
     elif (args.sv_train_feat_scp is not None or args.sv_train_len_scp is not None or args.sv_lda_dim is not None or args.sv_plda_iters != 10
           or args.sv_no_length_norm):
         p.error("--sv-train-feat-scp, --sv-train-len-scp, --sv-lda-dim, --sv-plda-iters and --sv-no-length-norm need --sv-backend lda or plda")
+    elif args.sv_snorm or args.sv_snorm_top != 200:
+        p.error("--sv-snorm and --sv-snorm-top need --sv-backend lda or plda")
     if args.tsne and args.feat_scp is None:
         p.error("--tsne draws the sequences of --feat-scp data: give --feat-scp")
     if not args.tsne_perplexity >= 1.0:
@@ -351,6 +360,13 @@ def verify_speakers(args, keys, mu2_rows, z1_mu, seq_pos, out_dir, dev, train=No
             for b in args.sv_trained:
                 rb = backend.score_all_pairs(emb, labels, n_bins=args.sv_bins, backend=b, device=dev)
                 np.save(os.path.join(out_dir, "sv_hist_%s_%s.npy" % (name, b)), rb.pop("hist"))
+                if args.sv_snorm:
+                    import score_norm as SN
+
+                    cohort = SN.make_cohort(train[1][name], train_labels, "speaker-means")
+                    rn = SN.score_all_pairs(backend, emb, labels, cohort, top=args.sv_snorm_top, which=b, n_bins=args.sv_bins, device=dev)
+                    np.save(os.path.join(out_dir, "sv_hist_%s_%s_snorm.npy" % (name, b)), rn.pop("hist"))
+                    rb["snorm"] = rn
                 r[b] = rb
             backend.save(os.path.join(out_dir, "sv_backend_%s.npz" % name))
     block.update({"speakers": n_spk, "unlabelled": int((labels < 0).sum()), "bins": args.sv_bins})

@@ -6,6 +6,7 @@ archive as the papers' baseline.
     python score_speakers.py --train-emb DIR|SCP --eval-emb DIR|SCP (--utt2spk FILE | --spk-key-sep SEP)
         --backend cosine lda plda [--lda-dim K] [--no-length-norm] [--plda-iters 10] [--model FILE.npz] [--trials FILE]
         [--bins 4096] --out DIR
+        [--snorm [--snorm-top 200] [--snorm-cohort DIR|SCP] [--snorm-cohort-mode speaker-means|rows] [--snorm-max-cohort N]]
 
 An archive is a directory with mu2.npy + keys.txt (or ivectors.npy + keys.txt, what extract_ivectors.py writes), a directory with feats.scp (what extract_latents.py --out-format kaldi
 writes: one-row matrices), or an scp file whose entries are one-row matrices or vectors.  --utt2spk / --spk-key-sep name the
@@ -14,6 +15,12 @@ speakers of both archives.  --trials lines are `<enrol-key> <test-key> target|no
 Writes speakers.json (per back end: eer, threshold, min_dcf, crossing_mass, n_target, n_nontarget, lo, hi; with --trials a
 "trials" entry with the exact EER by sorting), hist_<backend>.npy, backend.npz (with lda or plda; --model reads one instead of
 training) and, with --trials (which the PLDA scores), scores.txt (`<enrol-key> <test-key> <LLR>` per line).
+
+--snorm scores every back end a second time, normalised against a cohort (score_norm.py): adaptive S-norm with the
+--snorm-top largest cohort scores of either side (0: the whole cohort, S-norm).  The cohort is made from --snorm-cohort (default:
+the training archive): its speakers' means, or its rows with --snorm-cohort-mode rows (an archive without speakers gives rows), at
+most --snorm-max-cohort of them.  Per back end speakers.json gains a "snorm" block (the same figures plus "top" and "cohort"),
+hist_<backend>_snorm.npy is written and, with --trials, scores_snorm.txt.  Without --snorm every output is what it was.
 """
 from __future__ import annotations
 
@@ -121,6 +128,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model", default=None, metavar="FILE.npz", help="a backend.npz of an earlier run, instead of training")
     p.add_argument("--trials", default=None, metavar="FILE")
     p.add_argument("--bins", type=int, default=4096, help="score bins of the histograms (a power of two, 64..8192)")
+    p.add_argument("--snorm", action="store_true", help="score a second time, normalised against a cohort (S-norm / AS-norm)")
+    p.add_argument("--snorm-top", type=int, default=200, metavar="K", help="cohort scores kept per side (0: the whole cohort)")
+    p.add_argument("--snorm-cohort", default=None, metavar="DIR|SCP", help="the cohort's embeddings (default: --train-emb)")
+    p.add_argument("--snorm-cohort-mode", default="speaker-means", choices=("speaker-means", "rows"))
+    p.add_argument("--snorm-max-cohort", type=int, default=None, metavar="N", help="at most N cohort rows (a random subset)")
     p.add_argument("--out", required=True)
     return p
 
@@ -142,6 +154,13 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("--lda-dim %d must be at least 1" % args.lda_dim)
     if "lda" in args.backend and args.model is None and args.lda_dim is None:
         p.error("--backend lda needs --lda-dim")
+    if args.snorm:
+        if args.snorm_cohort is None and args.train_emb is None:
+            p.error("--snorm needs a cohort: --snorm-cohort (or --train-emb)")
+        if args.snorm_top < 0:
+            p.error("--snorm-top %d must not be negative" % args.snorm_top)
+        if args.snorm_max_cohort is not None and args.snorm_max_cohort < 1:
+            p.error("--snorm-max-cohort %d must be at least 1" % args.snorm_max_cohort)
     return args
 
 
@@ -152,6 +171,22 @@ def speakers_of(args, keys):
         table = V.read_utt2spk(args.utt2spk)
         return [table.get(k) for k in keys]
     return V.speakers_from_keys(keys, args.spk_key_sep)
+
+
+def read_cohort(args, dim):
+    """The cohort rows of --snorm -> (Nc, dim) f32: the speakers' means of the cohort archive, or its rows (--snorm-cohort-mode
+    rows, or an archive none of whose keys has a speaker)."""
+    import score_norm as SN
+    import verification as V
+
+    path = args.snorm_cohort if args.snorm_cohort is not None else args.train_emb
+    ckeys, cemb = read_archive(path)
+    if cemb.shape[1] != dim:
+        raise ValueError("the cohort %s has %d columns, %s has %d" % (path, cemb.shape[1], args.eval_emb, dim))
+    speakers = speakers_of(args, ckeys)
+    if args.snorm_cohort_mode == "rows" or all(s is None for s in speakers):
+        return SN.make_cohort(cemb, None, "rows", args.snorm_max_cohort)
+    return SN.make_cohort(cemb, V.labels_from_speakers(speakers)[0], "speaker-means", args.snorm_max_cohort)
 
 
 def run(args) -> dict:
@@ -173,7 +208,8 @@ def run(args) -> dict:
     trials = read_trials(args.trials, keys) if args.trials is not None else None
     os.makedirs(args.out, exist_ok=True)
     report = {"sequences": len(keys), "speakers": n_spk, "unlabelled": int((labels < 0).sum()), "bins": args.bins}
-    columns = []
+    columns, norm_columns = [], []
+    cohort = read_cohort(args, emb.shape[1]) if args.snorm else None
     for name in args.backend:
         if name == "cosine":
             r = V.speaker_verification(emb, labels, n_bins=args.bins)
@@ -188,12 +224,27 @@ def run(args) -> dict:
             columns.append(s)
             t = SB.exact_eer(s, trials[1])
             r["trials"] = {"eer": t["eer"], "threshold": t["threshold"], "n_target": t["n_target"], "n_nontarget": t["n_nontarget"]}
+        if cohort is not None:
+            import score_norm as SN
+
+            rn = SN.score_all_pairs(backend, emb, labels, cohort, top=args.snorm_top, which=name, n_bins=args.bins)
+            np.save(os.path.join(args.out, "hist_%s_snorm.npy" % name), rn.pop("hist"))
+            if trials is not None and name == "plda":
+                s = SN.score_trials(backend, emb, trials[0], cohort, top=args.snorm_top, which=name)
+                norm_columns.append(s)
+                t = SB.exact_eer(s, trials[1])
+                rn["trials"] = {"eer": t["eer"], "threshold": t["threshold"], "n_target": t["n_target"], "n_nontarget": t["n_nontarget"]}
+            r["snorm"] = rn
         report[name] = r
     if backend is not None:
         backend.save(os.path.join(args.out, "backend.npz"))
     if trials is not None and columns:
         with open(os.path.join(args.out, "scores.txt"), "w") as fh:
             for (i, j), s in zip(trials[0], columns[0]):
+                fh.write("%s %s %.9g\n" % (keys[int(i)], keys[int(j)], float(s)))
+    if trials is not None and norm_columns:
+        with open(os.path.join(args.out, "scores_snorm.txt"), "w") as fh:
+            for (i, j), s in zip(trials[0], norm_columns[0]):
                 fh.write("%s %s %.9g\n" % (keys[int(i)], keys[int(j)], float(s)))
     with open(os.path.join(args.out, "speakers.json"), "w") as fh:
         json.dump(report, fh, indent=1)
